@@ -4,29 +4,37 @@
   python bench.py --gpus N --steps K --warmup W          (N > 1: spawns its N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W             (the same, launched from outside)
+  python bench.py ... --full                             (+ every other leg listed below)
+  python bench.py ... --dump-outputs DIR                 (+ the state the timed steps left, DIR/state.npy)
 
 A "step" is one CA step (one dispatch of the reference's compute pass, main_pathtraced.js:1796-1809) over the whole
-grid. The batch of K steps is repeated (`reps`) until at least 1 s is timed (every CA leg). At N = 1 the K-step calls are ENCODED
-(`ca3d_set_option("queue")`) and handed to the GPU 2048 steps at a time (`ca3d_flush`) — what the reference does with its
-command encoder and one queue.submit (main_pathtraced.js:1833-1850) — so the value does not depend on K: the resident
-multi-step kernel runs a submission as one launch. `--submit call` makes every K-step call its own submission.
+grid. After W warm-up steps exactly K steps are timed. At N = 1 the host issues them as ca3d_step(--call-steps) calls that are
+ENCODED (`ca3d_set_option("queue")`) and handed to the GPU about 2048 steps at a time (`ca3d_flush`) — what the reference does with
+its command encoder and one queue.submit (main_pathtraced.js:1833-1850) — so the resident multi-step kernel runs a submission as one
+launch; before the warm-up one such submission is run and the bench state uploaded again (kernels loaded, buffers and graphs made
+outside the timed region). `--submit call` makes every call its own submission. At N > 1 the K steps are one call of the slab
+engine (halo exchange every `--ghost` steps), after one untimed call of K steps and the bench state uploaded again.
 --config picks the BASELINE configuration:
   3 (default at N = 1)  512^3, default rule, + the 1920x1080 @ 4 spp render leg          BASELINE configs[2]
   4 (default at N > 1)  1024^3, default rule, Z-slabs over the ranks, RCCL halo exchange   BASELINE configs[3]
   5                     2048^3, clustered rule-set, halo overlapped with compute, + the 3840x2160 frame   configs[4]
 Configs 4 and 5 at N = 1 run the same grid on one GPU: the base of the scaling curve (the N = 1 line of config 3 also
-carries it as `scaling_base`, measured in the same run). The state is resident in HBM before the timed region; the
+carries it as `scaling_base` with --full). The state is resident in HBM before the timed region; the
 timed region is bracketed by barrier + synchronize and the max over ranks is taken.
 
-Prints ONE JSON line on rank 0 with `roofline` and, at N = 1, `cpu_baseline` (the CPU oracle timed on this host's cores on a
-bounded sample). `roofline` names the limiter of the kernel that ran: per-step kernels read and write the state every step —
-algorithmic bytes per launch / launch duration (HIP events on the engine's stream around the timed region) against the
-8 TB/s HBM peak; the resident multi-step kernels keep the state on chip, what bounds them is vector-instruction issue —
-wave-instructions per second (count per wave and step from the committed rocprofv3 SQ pass of this command, profiles/) against
-1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction — with the algorithmic-byte rate beside it as `hbm_equivalent`.
-The N = 1 line also carries: `per_step_kernels` (the same grid with every step through memory: the HBM-path fraction),
-`per_call` (every K-step call its own submission), `grid_256` (BASELINE configs[1]'s grid), `grid_64` (the UI's start-up grid), `render` / `render_4k`,
-`scaling_base` (1024^3 on one GPU).
+Prints ONE JSON line on rank 0 with the headline (`value`, `ms_per_step` = wall milliseconds per timed step) and `roofline`:
+per-step kernels read and write the state every step — algorithmic bytes per launch / launch duration (HIP events on the engine's
+stream around the timed region) against the 8 TB/s HBM peak; the resident multi-step kernels keep the state on chip, what bounds
+them is vector-instruction issue — wave-instructions per second (count per wave and step from the committed rocprofv3 SQ pass of
+this command, profiles/) against 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction — with the algorithmic-byte rate beside it
+as `hbm_equivalent`.
+A plain run does nothing else. With --full the state is first checked against the CPU oracle (`verified`), and the N = 1 line also
+carries: `copy_ceiling`, `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample) and `cpu_baseline_js`,
+`per_step_kernels` (the same grid with every step through memory: the HBM-path fraction), `per_call` (every --call-steps call its
+own submission), `grid_256` (BASELINE configs[1]'s grid), `grid_64` (the UI's start-up grid), `render` / `render_4k` /
+`interactive_frame`, `scaling_base` (1024^3 on one GPU); the N > 1 line `schedules` (the other batch schedule timed as well) and,
+with --config 5, the frame shared between the ranks. `per_call`, `other_submission`, `grid_256` and `grid_64` issue --call-steps
+steps per call (20; before --steps set the number of timed steps it was also their call size). The extra legs repeat their batches until --min-seconds are timed.
 """
 import argparse
 import json
@@ -43,6 +51,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 INFINITY_CACHE_BYTES = 256 << 20
 MIN_TIMED_SECONDS = 1.0
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 VALU_PEAK_GWIPS = 1024 * 2.4 / 2.0  # G wave-instructions/s: 256 CUs x 4 SIMD-32, a wave64 VALU instruction issues over 2 cycles (MI355X_MICROARCH.md, Wave scheduling), 2.4 GHz
 
 RULES = {
@@ -63,15 +72,19 @@ CONFIGS = {  # BASELINE.json configs[2..4]
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2048)
-    ap.add_argument("--warmup", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=2048, help="timed CA steps (exactly this many)")
+    ap.add_argument("--warmup", type=int, default=256, help="CA steps run before the timed ones")
+    ap.add_argument("--call-steps", type=int, default=20, help="N=1: steps per ca3d_step call of the timed region and of the extra legs")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline (oracle check, baselines, other grids, render, ...)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the state the timed steps left to DIR/state.npy (N>1: DIR/state_rank<r>.npy): the packed words as float64")
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=0, help="BASELINE configuration (default: 3 at N=1, 4 at N>1)")
     ap.add_argument("--grid", type=int, default=0, help="grid edge (overrides the configuration's)")
     ap.add_argument("--rule", choices=sorted(RULES), default="", help="rule-set (overrides the configuration's)")
     ap.add_argument("--density-rounds", type=int, default=0, help="AND rounds of the hashed fill: density 2^-(1+r)")
     ap.add_argument("--ghost", type=int, default=0, help="ghost planes per side = steps between halo exchanges (N>1); 0: 32, or the deepest of 32 / 16 / 8 "
                     "with which a rank's share of a 1024^3 default-rule grid still runs the resident slab kernel (8 ranks: 32; 4 ranks: 16)")
-    ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS, help="repeat the batch until this much is timed")
+    ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS, help="--full: repeat the batches of the extra legs until this much is timed")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-render", action="store_true", help="skip the renderer legs (N=1)")
@@ -82,7 +95,7 @@ def parse(argv=None):
     ap.add_argument("--no-grid-256", action="store_true", help="N=1, config 3: skip the 256^3 leg (BASELINE configs[1]'s grid)")
     ap.add_argument("--multi-render", action="store_true",
                     help="N>1: also time the frame shared between the ranks (volume all-gather + bands of image rows); "
-                         "off by default (on for --config 5) so that the scaling run times the CA step alone")
+                         "off by default (on for --config 5 with --full) so that the scaling run times the CA step alone")
     ap.add_argument("--render-size", default="")
     ap.add_argument("--render-spp", type=int, default=4)
     ap.add_argument("--render-frames", type=int, default=100)
@@ -96,9 +109,9 @@ def parse(argv=None):
     ap.add_argument("--resident", type=int, choices=[0, 1], default=1,
                     help="0: per-step kernels only (every step reads and writes the state through memory); 1: batches run as one launch of the resident kernel where one exists")
     ap.add_argument("--submit", choices=["queued", "call"], default="queued",
-                    help="N=1: queued = the K-step calls are ENCODED and handed to the GPU --queue steps at a time (ca3d_flush; the reference's "
-                         "commandEncoder + one queue.submit), so the resident kernel runs them as one launch whatever K is; call = every "
-                         "K-step call is its own submission")
+                    help="N=1: queued = the --call-steps calls are ENCODED and handed to the GPU --queue steps at a time (ca3d_flush; the reference's "
+                         "commandEncoder + one queue.submit), so the resident kernel runs them as one launch whatever the call size is; call = every "
+                         "call is its own submission")
     ap.add_argument("--compare-submission", action="store_true",
                     help="N=1: also time the same calls under the other submission mode (`other_submission` in the JSON line; off by default so "
                          "that a profile of the default command holds launches of one length only)")
@@ -107,19 +120,23 @@ def parse(argv=None):
     ap.add_argument("--check", action="store_true", help="verify the final state against the oracle (small grids)")
     ap.add_argument("--verify-steps", type=int, default=-1,
                     help="before the timed region run this many steps from the bench state through the headline path and compare the state (N>1: every "
-                         "rank's slab) with the CPU oracle; a mismatch fails the run. Default: N=1 warm-up + 40 steps on grids up to 512^3; N>1 ghost + 8 steps — "
-                         "past one halo exchange — on grids up to 1024^3; 0 = off. The state is uploaded again afterwards")
+                         "rank's slab) with the CPU oracle; a mismatch fails the run. Default: 0 (off); with --full N=1 warm-up + 40 steps on grids up to "
+                         "512^3, N>1 ghost + 8 steps — past one halo exchange — on grids up to 1024^3. The state is uploaded again afterwards")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.call_steps < 1:
+        ap.error("--steps and --call-steps must be >= 1")
     a.config = a.config or (3 if a.gpus == 1 else 4)
     cfg = CONFIGS[a.config]
     a.grid = a.grid or cfg["grid"]
     a.rule = a.rule or cfg["rule"]
     a.render_size = a.render_size or cfg["render_size"]
     a.overlap = a.overlap or cfg.get("overlap", "auto")
-    if a.config == 5 and a.gpus > 1:
+    if a.config == 5 and a.gpus > 1 and a.full:
         a.multi_render = True
     if a.ghost <= 0:
         a.ghost = auto_ghost(a.grid, a.rule, a.gpus)
+    if a.verify_steps < 0 and not a.full:
+        a.verify_steps = 0
     if a.verify_steps < 0:
         # N = 1: warm-up + 40 steps through the headline path (one queued submission: the resident kernel where there is one) on grids
         # the oracle steps in about a second; N > 1: past one halo exchange
@@ -586,9 +603,38 @@ def rule_payload(rule_kw):
     return offs, s, b
 
 
+def timed_window(run, stream, total, chunk, barrier, world, backend, flush=None, launch_count=None):
+    """`total` steps as calls run(<= chunk) between barrier + synchronize, HIP events on `stream` around them. Returns (wall
+    seconds, max over ranks; HIP-event ms between the first and the last enqueue on the engine's stream; kernel launches inside
+    the window by `launch_count`, the engine's own counter, or None)."""
+    import torch
+    import torch.distributed as dist
+
+    flush = flush or (lambda: None)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    barrier()
+    n0 = launch_count() if launch_count else 0
+    t0 = time.perf_counter()
+    e0.record(stream)
+    left = total
+    while left > 0:
+        k = min(chunk, left)
+        run(k)
+        left -= k
+    flush()
+    e1.record(stream)
+    barrier()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    return dt, e0.elapsed_time(e1), (launch_count() - n0 if launch_count else None)
+
+
 def timed_region(run, stream, steps, warmup, min_seconds, barrier, world, backend, flush=None, group=1, launch_count=None):
-    """W warm-up steps, then `reps` batches of K steps between barrier + synchronize; reps is chosen (the same on every
-    rank) so that at least `min_seconds` are timed. `flush` submits what `run` only encoded (queued submission); `group`
+    """The extra legs' timing (--full): W warm-up steps, then `reps` batches of K steps between barrier + synchronize; reps is chosen
+    (the same on every rank) so that at least `min_seconds` are timed. `flush` submits what `run` only encoded (queued submission); `group`
     batches make one submission, the calibration runs one group and reps is a multiple of it, so every launch of the
     calibration and of the timed region has the same length. Returns (wall seconds, max over ranks; reps; HIP-event ms
     between the first and the last enqueue of the timed region on the engine's stream; batches run before the timed ones;
@@ -612,22 +658,20 @@ def timed_region(run, stream, steps, warmup, min_seconds, barrier, world, backen
         t = torch.tensor([reps], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         reps = int(t.item())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    barrier()
-    n0 = launch_count() if launch_count else 0
-    t0 = time.perf_counter()
-    e0.record(stream)
-    for _ in range(reps):
-        run(steps)
-    flush()
-    e1.record(stream)
-    barrier()
-    dt = time.perf_counter() - t0
-    if world > 1:
-        t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-    return dt, reps, e0.elapsed_time(e1), group, (launch_count() - n0 if launch_count else None)
+    dt, ev_ms, launches = timed_window(run, stream, reps * steps, steps, barrier, world, backend, flush, launch_count)
+    return dt, reps, ev_ms, group, launches
+
+
+def dump_state(directory, name, words, budget):
+    """--dump-outputs: the state words the timed steps left (what ca3d_read_state hands a caller) as float64, exact for uint32, in
+    directory/<name>.npy. More words than `budget` bytes hold: a fixed sample of them (seed 0, in index order), the same in every run."""
+    import numpy as np
+
+    n = budget // 8
+    if words.size > n:
+        words = words[np.sort(np.random.default_rng(0).choice(words.size, n, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), words.astype(np.float64))
 
 
 def oracle_verify(eng, G, full, rule, nsteps, queued):
@@ -651,10 +695,12 @@ def oracle_verify(eng, G, full, rule, nsteps, queued):
     return rec
 
 
-def single_gpu_leg(device, G, rule, steps, warmup, min_seconds, density_rounds=0, resident=1, queue=0, verify_steps=0):
+def single_gpu_leg(device, G, rule, steps, warmup, min_seconds, density_rounds=0, resident=1, queue=0, verify_steps=0, total=0):
     """One GPU, whole grid: returns the numbers of the timed region plus the engine (state = the bench state advanced).
-    queue > 0: the K-step calls are encoded and submitted `queue` steps at a time. verify_steps > 0: the path is checked against
-    the oracle first (eng.verified)."""
+    The host calls ca3d_step(steps); queue > 0: the calls are encoded and submitted about `queue` steps at a time. verify_steps > 0:
+    the path is checked against the oracle first (eng.verified). total > 0 (the headline): one submission is run and the bench
+    state uploaded again, then W warm-up steps and exactly `total` timed steps (reps = 1, no calibration batches); otherwise
+    timed_region's batches until `min_seconds` are timed."""
     import torch
 
     from cellularautomatons3d_amd import Engine, host
@@ -682,9 +728,19 @@ def single_gpu_leg(device, G, rule, steps, warmup, min_seconds, density_rounds=0
     if queue > 0:
         group = max(1, -(-queue // steps))
         eng.set_option("queue", group * steps)  # a submission = `group` whole calls
-    dt, reps, ev_ms, cal, launches = timed_region(eng.step, stream, steps, warmup, min_seconds, barrier, 1, "nccl", eng.flush, group,
-                                                  lambda: eng.info().launches_total)
-    return eng, full, dt, reps, ev_ms, cal, launches
+    launch_count = lambda: eng.info().launches_total
+    if not total:
+        dt, reps, ev_ms, cal, launches = timed_region(eng.step, stream, steps, warmup, min_seconds, barrier, 1, "nccl", eng.flush, group, launch_count)
+        return eng, full, dt, reps, ev_ms, cal, launches
+    for _ in range(group):
+        eng.step(steps)
+    eng.flush()
+    eng.upload_state(full)
+    if warmup > 0:
+        eng.step(warmup)
+    eng.flush()
+    dt, ev_ms, launches = timed_window(eng.step, stream, total, steps, barrier, 1, "nccl", eng.flush, launch_count)
+    return eng, full, dt, 1, ev_ms, 0, launches
 
 
 def roofline_block(kernel, G, bytes_per_step, total_steps, ev_ms, state_bytes, launches=None, variant=None):
@@ -781,7 +837,8 @@ def main():
     single_verified = None
     if world == 1:
         queue = a.queue if a.submit == "queued" else 0
-        eng, full, dt, reps, ev_ms, cal, launches = single_gpu_leg(local_rank, G, a.rule, a.steps, a.warmup, a.min_seconds, a.density_rounds, a.resident, queue, a.verify_steps)
+        eng, full, dt, _, ev_ms, _, launches = single_gpu_leg(local_rank, G, a.rule, a.call_steps, a.warmup, a.min_seconds, a.density_rounds, a.resident, queue,
+                                                             a.verify_steps, total=a.steps)
         core = eng
         single_verified = eng.verified
     else:
@@ -821,13 +878,20 @@ def main():
             verified = bool(flag.item())
             del want, got
             se.upload_state(full[se.z0 * pw:(se.z0 + se.nz) * pw])
-        dt, reps, ev_ms, cal, launches = timed_region(se.run, se.stream, a.steps, a.warmup, a.min_seconds, barrier, world, a.backend)
+        se.run(a.steps)  # untimed: the batch lengths of the timed call (graphs, first exchange) exist before the clock starts
+        se.upload_state(full[se.z0 * pw:(se.z0 + se.nz) * pw])
+        if a.warmup > 0:
+            se.run(a.warmup)
+        dt, ev_ms, launches = timed_window(se.run, se.stream, a.steps, a.steps, barrier, world, a.backend)
 
-    total_steps = a.steps * reps
+    total_steps = a.steps
     info = core.info()
     kernel = info.kernel_name.decode()
     cells = float(G) ** 3
     value = cells * total_steps / dt / 1e9
+    final = core.read_state() if a.check or a.dump_outputs else None
+    if a.dump_outputs:
+        dump_state(a.dump_outputs, "state" if world == 1 else f"state_rank{rank}", final, DUMP_BYTES // world)
 
     ok = None
     if a.check:
@@ -835,8 +899,8 @@ def main():
         import numpy as np
         import oracle_lib as ol
 
-        want = ol.packed_run(G, full, ol.Rules.from_strings(**rule_kw), a.warmup + a.steps * (reps + cal))
-        got = core.read_state()
+        want = ol.packed_run(G, full, ol.Rules.from_strings(**rule_kw), a.warmup + a.steps)
+        got = final
         lo = 0 if world == 1 else se.z0 * pw
         ok = bool(np.array_equal(got, want[lo:lo + got.size]))
         if world > 1:
@@ -845,7 +909,7 @@ def main():
             ok = bool(flag.item())
 
     schedules = None
-    if world > 1 and not a.no_schedule_compare:
+    if world > 1 and a.full and not a.no_schedule_compare:
         # The same slabs under the OTHER batch schedule, timed right behind the headline (state carried on): overlap on = edge zones,
         # exchange posted, interior under it; off = exchange, then the whole slab in one launch. On one GPU's loopback the split form
         # measured slower (two smaller launches per step) — whether the transfer it hides pays for that is a property of the real links,
@@ -855,7 +919,7 @@ def main():
         dt_o, reps_o, _, _, _ = timed_region(se.run, se.stream, a.steps, a.steps, a.min_seconds / 2, barrier, world, a.backend)
         se.overlap = first
         rec = lambda d, r: {"ms_per_step": round(d * 1e3 / (a.steps * r), 6), "value": round(cells * a.steps * r / d / 1e9, 3), "unit": "Gcells/s"}
-        schedules = {"overlap_on" if first else "overlap_off": rec(dt, reps), "overlap_off" if first else "overlap_on": rec(dt_o, reps_o),
+        schedules = {"overlap_on" if first else "overlap_off": rec(dt, 1), "overlap_off" if first else "overlap_on": rec(dt_o, reps_o),
                      "headline": "overlap_on" if first else "overlap_off",
                      "why_headline": ("BASELINE configs[4] names the overlapped schedule" if a.config == 5 else "--overlap / slab.py's automatic choice")}
     rccl_evidence = None
@@ -885,12 +949,12 @@ def main():
         own_cells = cells if world == 1 else float(G) * G * se.nz
         out = {
             "metric": "Gcells/s CA step at 512^3" if G == 512 else f"Gcells/s CA step at {G}^3",
-            "value": round(value, 3), "unit": "Gcells/s", "n_gpus": world, "steps": a.steps, "reps": reps, "warmup": a.warmup,
+            "value": round(value, 3), "unit": "Gcells/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(dt * 1e3 / total_steps, 6), "higher_is_better": True,
             "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
             "config": {"workload": f"{G}^3 uint32-packed grid, rule '{a.rule}' ({rule_kw['neighbourhood']} B{rule_kw['born']}/S{rule_kw['survive']}), "
                                    f"hashed fill seed 0xCA3D0001 density {2.0 ** -(1 + a.density_rounds):g}, one CA step per bench step, "
-                                   f"{reps} batches of {a.steps} steps timed",
+                                   f"{a.steps} steps timed after {a.warmup} warm-up steps",
                        "baseline_config": a.config, "grid": G, "layout": "packed32", "rule": a.rule,
                        "state_note": ("under this rule (S0-6: a live cell never dies) a density-0.5 fill reaches a fixed point within a few steps; the kernels are "
                                       "bit-sliced with no data-dependent path, so the rate does not depend on what the cells do (`--rule vn_b24_s135` keeps "
@@ -901,9 +965,10 @@ def main():
             "roofline": roofline_block(kernel, G, 0.25 * own_cells, total_steps, ev_ms, state_bytes, launches, core.kernel_variant()),
         }
         if world == 1:
-            out["config"]["submission"] = (f"queued: ca3d_step({a.steps}) encodes, ca3d_flush submits every {cal * a.steps} steps (the reference's commandEncoder + "
-                                           "queue.submit, main_pathtraced.js:1833-1850)" if queue else f"per call: every ca3d_step({a.steps}) is its own submission")
-        if world == 1:
+            K = a.call_steps
+            out["config"]["submission"] = (f"queued: ca3d_step({K}) encodes, ca3d_flush submits every {max(1, -(-queue // K)) * K} steps (the reference's commandEncoder + "
+                                           "queue.submit, main_pathtraced.js:1833-1850)" if queue else f"per call: every ca3d_step({K}) is its own submission")
+        if world == 1 and a.full:
             ceiling = copy_ceiling_gbs(eng)
             out["copy_ceiling"] = {"value": round(ceiling, 1), "unit": "GB/s",
                                    "how": "1 GiB float4-per-lane device-to-device copy, non-temporal stores (ca3d_measure_copy), bytes read + bytes written per second, measured in this run"}
@@ -947,38 +1012,39 @@ def main():
                     "roofline": roofline_block(e.info().kernel_name.decode(), Gx, 0.25 * float(Gx) ** 3, K * reps2, ev2, state_b, l2, e.kernel_variant())}
 
         resident_headline = world == 1 and kernel.startswith("ca_resident")
-        if world == 1 and resident_headline and (a.compare_submission or (queue and not a.no_per_call_leg)):
-            if queue:
-                out["per_call"] = per_call_leg(eng, G, state_bytes, a.steps)
+        per_call = world == 1 and a.full and queue and not a.no_per_call_leg
+        if world == 1 and resident_headline and (a.compare_submission or per_call):
+            if per_call:
+                out["per_call"] = per_call_leg(eng, G, state_bytes, K)
             if a.compare_submission:
                 # the same K-step calls under the other submission mode, for the record (same engine, state carried on)
                 q2 = 0 if queue else a.queue
-                g2 = max(1, -(-q2 // a.steps)) if q2 else 1
-                eng.set_option("queue", g2 * a.steps if q2 else 0)
-                dt2, reps2, ev2, _, l2 = timed_region(eng.step, eng.bench_stream, a.steps, 0, a.min_seconds, barrier, 1, "nccl", eng.flush, g2,
+                g2 = max(1, -(-q2 // K)) if q2 else 1
+                eng.set_option("queue", g2 * K if q2 else 0)
+                dt2, reps2, ev2, _, l2 = timed_region(eng.step, eng.bench_stream, K, 0, a.min_seconds, barrier, 1, "nccl", eng.flush, g2,
                                                       lambda: eng.info().launches_total)
-                out["other_submission"] = {"submission": "queued" if q2 else "per call", "value": round(cells * a.steps * reps2 / dt2 / 1e9, 3), "unit": "Gcells/s",
-                                           "ms_per_step": round(dt2 * 1e3 / (a.steps * reps2), 6), "reps": reps2,
-                                           "roofline": roofline_block(kernel, G, 0.25 * cells, a.steps * reps2, ev2, state_bytes, l2, eng.kernel_variant())}
-        if world == 1 and resident_headline and not a.no_per_step_leg:
+                out["other_submission"] = {"submission": "queued" if q2 else "per call", "value": round(cells * K * reps2 / dt2 / 1e9, 3), "unit": "Gcells/s",
+                                           "ms_per_step": round(dt2 * 1e3 / (K * reps2), 6), "reps": reps2,
+                                           "roofline": roofline_block(kernel, G, 0.25 * cells, K * reps2, ev2, state_bytes, l2, eng.kernel_variant())}
+        if world == 1 and a.full and resident_headline and not a.no_per_step_leg:
             out["per_step_kernels"] = per_step_leg(eng, G, state_bytes)
-        if world == 1 and not resident_headline:
+        if world == 1 and a.full and not resident_headline:
             out["roofline"]["frac_of_copy_ceiling"] = round(out["roofline"]["achieved"] / ceiling, 4)
-        if world == 1 and not a.no_render:
+        if world == 1 and a.full and not a.no_render:
             out["render"] = render_leg(eng, G, a)
             if a.config == 3 and a.render_size == "1920x1080":
                 out["render_4k"] = render_leg(eng, G, a, size="3840x2160", sparse=False, literal=False)  # BASELINE configs[4]'s frame size
             if a.config == 3 and not a.no_interactive:
                 out["interactive_frame"] = interactive_leg(eng, G, a)
-        if world == 1 and a.config == 3 and G == 512 and not a.no_grid_256:
+        if world == 1 and a.full and a.config == 3 and G == 512 and not a.no_grid_256:
             # BASELINE configs[1]'s grid (256^3): the resident kernel's 256^3 form under queued submission, and the per-step kernels
             eng.close()
-            e1, _, dt1, reps1, ev1, cal1, l1 = single_gpu_leg(local_rank, 256, "default", a.steps, a.warmup, a.min_seconds, 0, a.resident, a.queue if a.submit == "queued" else 0,
+            e1, _, dt1, reps1, ev1, cal1, l1 = single_gpu_leg(local_rank, 256, "default", K, a.warmup, a.min_seconds, 0, a.resident, a.queue if a.submit == "queued" else 0,
                                                               a.verify_steps)
             k1 = e1.info().kernel_name.decode()
-            out["grid_256"] = {"grid": 256, "rule": "default", "value": round(256.0 ** 3 * a.steps * reps1 / dt1 / 1e9, 3), "unit": "Gcells/s",
-                               "ms_per_step": round(dt1 * 1e3 / (a.steps * reps1), 6), "steps": a.steps, "reps": reps1,
-                               "roofline": roofline_block(k1, 256, 0.25 * 256.0 ** 3, a.steps * reps1, ev1, 2 << 20, l1, e1.kernel_variant())}
+            out["grid_256"] = {"grid": 256, "rule": "default", "value": round(256.0 ** 3 * K * reps1 / dt1 / 1e9, 3), "unit": "Gcells/s",
+                               "ms_per_step": round(dt1 * 1e3 / (K * reps1), 6), "steps": K, "reps": reps1,
+                               "roofline": roofline_block(k1, 256, 0.25 * 256.0 ** 3, K * reps1, ev1, 2 << 20, l1, e1.kernel_variant())}
             if e1.verified is not None:
                 out["grid_256"]["verified"] = e1.verified
                 if not e1.verified["oracle_match"]:
@@ -988,11 +1054,11 @@ def main():
             eng = e1
             # the reference UI's start-up grid (main_pathtraced.js:101): 64^3 — one workgroup holds the whole state (resident64_run)
             eng.close()
-            e0, _, dt0, reps0, ev0, cal0, l0 = single_gpu_leg(local_rank, 64, "default", a.steps, a.warmup, min(a.min_seconds, 0.2), 0, a.resident, a.queue if a.submit == "queued" else 0,
+            e0, _, dt0, reps0, ev0, cal0, l0 = single_gpu_leg(local_rank, 64, "default", K, a.warmup, min(a.min_seconds, 0.2), 0, a.resident, a.queue if a.submit == "queued" else 0,
                                                               a.verify_steps)
             k0 = e0.info().kernel_name.decode()
-            out["grid_64"] = {"grid": 64, "rule": "default", "value": round(64.0 ** 3 * a.steps * reps0 / dt0 / 1e9, 3), "unit": "Gcells/s",
-                              "ms_per_step": round(dt0 * 1e3 / (a.steps * reps0), 6), "steps": a.steps, "reps": reps0, "kernel": k0,
+            out["grid_64"] = {"grid": 64, "rule": "default", "value": round(64.0 ** 3 * K * reps0 / dt0 / 1e9, 3), "unit": "Gcells/s",
+                              "ms_per_step": round(dt0 * 1e3 / (K * reps0), 6), "steps": K, "reps": reps0, "kernel": k0,
                               "what": "the reference UI's start-up grid; batches through the one-workgroup resident kernel (the whole state in one CU's registers)"}
             if e0.verified is not None:
                 out["grid_64"]["verified"] = e0.verified
@@ -1005,7 +1071,7 @@ def main():
                 out["grid_64"]["per_step_kernels"] = {"ms_per_step": round(dtp * 1e3 / (256 * repsp), 6), "kernel": e0.info().kernel_name.decode()}
                 e0.set_option("resident", a.resident)
             eng = e0
-        if world == 1 and a.config == 3 and G == 512 and not a.no_scaling_base:
+        if world == 1 and a.full and a.config == 3 and G == 512 and not a.no_scaling_base:
             # the single-GPU point of the multi-GPU curve, on the multi-GPU grid, in the same run (N > 1 runs 1024^3)
             eng.close()
             e2, _, dt2, reps2, ev2, _, _ = single_gpu_leg(local_rank, 1024, "default", 256, 64, a.min_seconds)
@@ -1026,7 +1092,7 @@ def main():
             out["render"] = multi_render
             if multi_render.get("frame_match") is False:
                 ok = False
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(min(G, 512), rule_kw, a.cpu_seconds)
             out["cpu_baseline_js"] = cpu_baseline_js(G=min(G, 512))  # the JS stepper at G in {256, 512}
             if G == 512:

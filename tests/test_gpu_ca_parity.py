@@ -991,23 +991,23 @@ def test_queued_submission(eng):
 
 
 def test_bench_line_single_gpu_queued_and_per_call():
-    """bench.py at N = 1 as the driver runs it (a small grid): one JSON line and nothing else on stdout, the state checked
-    against the oracle after warm-up + calibration + timed steps, the K-step calls submitted together (`ca3d_flush`) with the
-    per-call figure beside it, `roofline` per launch of the resident kernel."""
+    """bench.py --full at N = 1 (a small grid): one JSON line and nothing else on stdout, the state checked against the oracle
+    after warm-up + timed steps, the 20-step calls submitted together (`ca3d_flush`) with the per-call figure beside it,
+    `roofline` per launch of the resident kernel."""
     import json
     import os
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--grid", "256", "--steps", "20", "--warmup", "5", "--queue", "256",
-           "--min-seconds", "0.0001", "--no-cpu-baseline", "--no-render", "--no-scaling-base", "--check", "--compare-submission"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--grid", "256", "--steps", "520", "--call-steps", "20", "--warmup", "5", "--queue", "256",
+           "--min-seconds", "0.0001", "--no-cpu-baseline", "--no-render", "--no-scaling-base", "--check", "--compare-submission", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
-    assert d["oracle_match"] is True and d["n_gpus"] == 1 and d["steps"] == 20 and d["unit"] == "Gcells/s"
+    assert d["oracle_match"] is True and d["n_gpus"] == 1 and d["steps"] == 520 and d["unit"] == "Gcells/s"
     rf = d["roofline"]
     # a resident kernel keeps the state on chip: its limiter is vector-instruction issue, the algorithmic-byte rate is kept as a
     # rate beside it; a fraction of a peak never exceeds 1
@@ -1015,7 +1015,8 @@ def test_bench_line_single_gpu_queued_and_per_call():
     assert rf["hbm_equivalent"]["achieved"] > 0 and "frac" not in rf["hbm_equivalent"]
     if rf["frac"] is not None:
         assert 0 < rf["frac"] <= 1 and abs(rf["achieved"] / rf["peak"] - rf["frac"]) < 1e-3 and os.path.exists(os.path.join(root, rf["counter_source"]))
-    assert d["config"]["submission"].startswith("queued") and d["reps"] % 13 == 0
+    # the timed steps are whole submissions of 13 calls: every launch holds 260 steps
+    assert d["config"]["submission"].startswith("queued") and rf["launches_timed"] * 260 == d["steps"]
     other = d["other_submission"]
     assert other["submission"] == "per call" and other["roofline"]["steps_per_launch"] == 20 and other["value"] > 0
     assert d["per_call"]["roofline"]["steps_per_launch"] == 20
@@ -1043,7 +1044,7 @@ def test_bench_scaling_base_names_both_single_gpu_paths():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-render",
-           "--no-per-step-leg", "--no-per-call-leg", "--no-grid-256", "--no-interactive", "--verify-steps", "0"]
+           "--no-per-step-leg", "--no-per-call-leg", "--no-grid-256", "--no-interactive", "--verify-steps", "0", "--full"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1063,7 +1064,7 @@ def test_bench_interactive_frame_leg():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--min-seconds", "0.0001", "--no-cpu-baseline", "--no-scaling-base",
-           "--no-per-step-leg", "--no-per-call-leg", "--no-grid-256", "--render-frames", "3"]
+           "--no-per-step-leg", "--no-per-call-leg", "--no-grid-256", "--render-frames", "3", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -1073,3 +1074,34 @@ def test_bench_interactive_frame_leg():
         assert 0 < it[scene]["ms_per_frame"] < 50 and it[scene]["step_kernel"].startswith("ca_packed_vn")
     assert it["frames"] == 200
     assert 0 < d["render"]["literal_frame"]["ms_per_frame"] < d["render"]["ms_per_frame"] * 2
+
+
+def test_bench_plain_line_times_exactly_its_steps_and_dumps_the_state(tmp_path):
+    """A plain bench.py run: the headline only (no oracle leg, baselines or other grids), exactly --steps timed steps, and
+    --dump-outputs writes the state those steps left — the packed words as float64 — equal to the oracle's after warm-up + steps.
+    The rule keeps changing every word of the state from step to step (the default rule reaches a fixed point within a few steps),
+    so one step too many or too few, a dropped chunk or the untimed submission left on the state would all show."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--grid", "256", "--rule", "vn_b24_s135", "--steps", "2100",
+           "--warmup", "7", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2100 and d["warmup"] == 7 and d["unit"] == "Gcells/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["ms_per_step"] > 0 and abs(256.0 ** 3 / (d["ms_per_step"] * 1e6) / d["value"] - 1) < 0.02  # ms_per_step carries 6 decimals
+    assert not {"verified", "copy_ceiling", "per_call", "per_step_kernels", "render", "grid_256", "scaling_base", "cpu_baseline"} & set(d)
+    # one resident launch per 2060 steps (103 calls of 20): 2100 timed steps are a full submission and a 40-step one
+    assert d["roofline"]["kernel"].startswith("ca_resident_vn") and d["roofline"]["launches_timed"] == 2
+    got = np.load(tmp_path / "out" / "state.npy")
+    assert got.dtype == np.float64 and got.size == host.words_per_buffer(256)
+    st = host.random_fill(host.words_per_buffer(256), seed=0xCA3D0001)
+    r = ol.Rules.from_strings(neighbourhood="von neumann", born="2,4", survive="1,3,5")
+    want = ol.packed_run(256, st, r, 2107)
+    assert not np.array_equal(want, ol.packed_step(256, want, r))  # the state still changes at the last step
+    np.testing.assert_array_equal(got.astype(np.uint32), want)

@@ -407,7 +407,7 @@ def test_bench_four_ranks_rehearsal_picks_the_ghost_depth():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "32", "--warmup", "16", "--resident", "0",
-           "--backend", "gloo", "--device-map", "0,0,0,0", "--no-cpu-baseline", "--min-seconds", "0", "--no-schedule-compare"]
+           "--backend", "gloo", "--device-map", "0,0,0,0", "--no-cpu-baseline", "--min-seconds", "0", "--no-schedule-compare", "--full"]
     import time
 
     t_run = time.perf_counter()
@@ -442,7 +442,7 @@ def test_bench_plain_invocation_spawns_its_ranks():
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 2 and d["oracle_match"] is True and d["reps"] == 1 and d["config"]["grid"] == 256
+    assert d["n_gpus"] == 2 and d["oracle_match"] is True and d["steps"] == 9 and d["config"]["grid"] == 256
 
 
 @pytest.mark.parametrize("name,G,P,K,steps", [("default", 256, 4, 8, (8, 13, 3)), ("clustered", 256, 8, 4, (9, 4)), ("default", 1024, 8, 16, (33,)),

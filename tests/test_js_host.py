@@ -87,11 +87,10 @@ def test_node_bench_drives_several_slabs_from_one_thread():
 
 
 def test_facade_runs_the_unmodified_reference_host_with_a_mock_engine():
-    """SURVEY 8(f) N2 (build container only): main_pathtraced.js + ui.js + MemoryManager.js, unmodified, drive the
-    navigator.gpu facade through init and five frames; a recording mock stands in for the engine."""
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("the reference sources are not mounted here")
-    r = _node("tests/js/facade_reference_mock.js", "/root/reference")
+    """the WebGPU calls main_pathtraced.js + ui.js + MemoryManager.js, unmodified, make through init and five
+    frames (recorded in tests/golden/reference_webgpu_calls.json) drive the navigator.gpu facade; a recording mock stands in
+    for the engine."""
+    r = _node("tests/js/facade_reference_mock.js")
     assert r.returncode == 0 and '"ok":true' in r.stdout, (r.stdout + r.stderr)[-3000:]
 
 

@@ -9,12 +9,12 @@ export TMPDIR=/tmp
 B512="bench.py --no-cpu-baseline --no-render --steps 512 --warmup 64"
 B1024="bench.py --no-cpu-baseline --no-render --grid 1024 --steps 128 --warmup 32"
 
-python bench.py > "$out/${tag}_bench512_default.json"
+python bench.py --full > "$out/${tag}_bench512_default.json"
 cat "$out/${tag}_bench512_default.json"
 
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats512" -o s -- python $B512 > "$out/${tag}_bench512_under_rocprof.json"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats1024" -o s -- python $B1024 > "$out/${tag}_bench1024_under_rocprof.json"
-rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats_render" -o s -- python bench.py --no-cpu-baseline --steps 64 --warmup 8 > "$out/${tag}_bench_render_under_rocprof.json"
+rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats_render" -o s -- python bench.py --full --no-cpu-baseline --steps 64 --warmup 8 > "$out/${tag}_bench_render_under_rocprof.json"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats_clustered" -o s -- python $B512 --rule clustered > "$out/${tag}_bench512_clustered_under_rocprof.json"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats_unpacked" -o s -- python tools/run_unpacked.py > "$out/${tag}_unpacked.log"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats_slab" -o s -- python tools/run_slab.py --ghost 16 --batches 50 > "$out/${tag}_slab.log"

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 Q="--no-cpu-baseline --no-render --no-scaling-base --no-per-step-leg"
 DRV="bench.py --steps 20 --warmup 5"          # the driver's own command
 python $DRV > "$out/${tag}_bench512_driver_cmd.json"
-python bench.py > "$out/${tag}_bench512_default.json"
+python bench.py --full > "$out/${tag}_bench512_default.json"
 python bench.py $Q --resident 0 --steps 512 --warmup 64 > "$out/${tag}_bench512_perstep.json"
 python $DRV $Q --compare-submission > "$out/${tag}_bench512_driver_cmd_both_submissions.json"
 python tools/run_resident.py > "$out/${tag}_resident_batches.txt" 2>/dev/null
@@ -24,11 +24,11 @@ stats 512_perstep bench.py $Q --resident 0 --steps 512 --warmup 64
 stats 1024 bench.py $Q --grid 1024 --steps 128 --warmup 32
 stats 512_clustered bench.py $Q --rule clustered --steps 256 --warmup 32
 stats 1024_clustered bench.py $Q --grid 1024 --rule clustered --steps 64 --warmup 16
-stats render bench.py --no-cpu-baseline --no-scaling-base --steps 64 --warmup 8
+stats render bench.py --full --no-cpu-baseline --no-scaling-base --steps 64 --warmup 8
 for g in 256 1024; do python bench.py $Q --grid $g --steps 1024 --warmup 128 >> "$out/${tag}_bench_matrix.jsonl"; done
 for g in 256 512 1024; do python bench.py $Q --grid $g --rule clustered --steps 256 --warmup 64 >> "$out/${tag}_bench_matrix.jsonl"; done
 for r in vn_b24_s135 life2d; do python bench.py $Q --grid 512 --rule $r --steps 1024 --warmup 128 >> "$out/${tag}_bench_matrix.jsonl"; done
-python bench.py --config 5 --steps 16 --warmup 4 --no-cpu-baseline > "$out/${tag}_bench_config5_1gpu.json"
+python bench.py --full --config 5 --steps 16 --warmup 4 --no-cpu-baseline > "$out/${tag}_bench_config5_1gpu.json"
 pmc() { rocprofv3 --output-format csv --pmc $2 --kernel-trace -d "$out/${tag}_pmc_$1" -o p -- python ${@:3} > /dev/null; }
 pmc fetch512res FETCH_SIZE $DRV $Q
 pmc write512res WRITE_SIZE $DRV $Q
@@ -38,7 +38,7 @@ pmc fetch512cl FETCH_SIZE bench.py $Q --rule clustered --steps 128 --warmup 16
 pmc write512cl WRITE_SIZE bench.py $Q --rule clustered --steps 128 --warmup 16
 pmc sq512cl "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY" bench.py $Q --rule clustered --steps 128 --warmup 16
 pmc sq512res "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY" $DRV $Q
-pmc sqrender "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY" bench.py --no-cpu-baseline --no-scaling-base --steps 64 --warmup 8
+pmc sqrender "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY" bench.py --full --no-cpu-baseline --no-scaling-base --steps 64 --warmup 8
 python tools/pmc_reduce.py "ca_resident_vn@512" ca_resident_vn "$out/${tag}_pmc_fetch512res" "$out/${tag}_pmc_write512res" "$out/${tag}_pmc_traffic.json"
 python tools/pmc_reduce.py "ca_packed_vn@512" ca_packed_vn "$out/${tag}_pmc_fetch512" "$out/${tag}_pmc_write512" "$out/${tag}_pmc_traffic.json"
 python tools/pmc_reduce.py "ca_resident_class@512" ca3d_jit_resident_class "$out/${tag}_pmc_fetch512cl" "$out/${tag}_pmc_write512cl" "$out/${tag}_pmc_traffic.json"

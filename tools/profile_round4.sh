@@ -25,8 +25,8 @@ if [ "$what" = stats ] || [ "$what" = all ]; then
   stats 512_clustered bench.py $Q --rule clustered --steps 256 --warmup 32
   stats 1024_clustered bench.py $Q --grid 1024 --rule clustered --steps 64 --warmup 16
   stats 992 bench.py $Q --grid 992 --steps 64 --warmup 16
-  stats render bench.py --no-cpu-baseline --no-scaling-base --no-per-step-leg --no-per-call-leg --no-grid-256 --min-seconds 0.2 --steps 64 --warmup 8 --verify-steps 0
-  python3 bench.py --config 5 --steps 16 --warmup 4 --no-cpu-baseline --min-seconds 0.3 > "$out/${tag}_bench_config5_1gpu.json"
+  stats render bench.py --full --no-cpu-baseline --no-scaling-base --no-per-step-leg --no-per-call-leg --no-grid-256 --min-seconds 0.2 --steps 64 --warmup 8 --verify-steps 0
+  python3 bench.py --full --config 5 --steps 16 --warmup 4 --no-cpu-baseline --min-seconds 0.3 > "$out/${tag}_bench_config5_1gpu.json"
 fi
 if [ "$what" = pmc ] || [ "$what" = all ]; then
   pmc sq512res "$SQ" $DRV $Q

@@ -14,7 +14,7 @@ out=$PWD/gpurun_out
 mkdir -p "$out"
 export TMPDIR=/tmp
 Q="--no-cpu-baseline --no-render --no-scaling-base --no-per-step-leg --no-per-call-leg --no-grid-256 --min-seconds 0.2 --verify-steps 0"
-DRV="bench.py --steps 20 --warmup 5"          # the driver's own command
+DRV="bench.py --steps 2060 --warmup 5"        # the driver's calls of 20 steps: every resident launch holds 2060 steps
 SQ="SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY"
 stats() { rocprofv3 --output-format csv --kernel-trace --stats -d "$out/${tag}_stats_$1" -o s -- python3 ${@:2} > "$out/${tag}_bench_$1_under_rocprof.json"; cp "$out/${tag}_stats_$1"/*/s_kernel_stats.csv "$out/${tag}_$1_kernel_stats.csv" 2>/dev/null || cp "$out/${tag}_stats_$1"/s_kernel_stats.csv "$out/${tag}_$1_kernel_stats.csv"; echo "stats $1 done"; }
 pmc() { rocprofv3 --output-format csv --pmc $2 --kernel-trace -d "$out/${tag}_pmc_$1" -o p -- python3 ${@:3} > "$out/${tag}_pmc_$1_bench.json"; echo "pmc $1 done"; }
@@ -79,8 +79,8 @@ if [ "$what" = stats ] || [ "$what" = all ]; then
   stats 512_clustered bench.py $Q --rule clustered --steps 256 --warmup 32
   stats 1024_clustered bench.py $Q --grid 1024 --rule clustered --steps 64 --warmup 16
   stats 992 bench.py $Q --grid 992 --steps 64 --warmup 16
-  stats render bench.py --no-cpu-baseline --no-scaling-base --no-per-step-leg --no-per-call-leg --no-grid-256 --min-seconds 0.2 --steps 64 --warmup 8 --verify-steps 0
-  python3 bench.py --config 5 --steps 16 --warmup 4 --no-cpu-baseline --min-seconds 0.3 > "$out/${tag}_bench_config5_1gpu.json"
+  stats render bench.py --full --no-cpu-baseline --no-scaling-base --no-per-step-leg --no-per-call-leg --no-grid-256 --min-seconds 0.2 --steps 64 --warmup 8 --verify-steps 0
+  python3 bench.py --full --config 5 --steps 16 --warmup 4 --no-cpu-baseline --min-seconds 0.3 > "$out/${tag}_bench_config5_1gpu.json"
 fi
 if [ "$what" = matrix ] || [ "$what" = all ]; then
   python3 tools/grid_matrix.py --grids 64,96,128,160,256,288,384,512,640,768,896,992,1024 --out "$out/${tag}_grid_matrix.jsonl" > /dev/null
