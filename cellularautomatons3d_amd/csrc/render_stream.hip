@@ -1,21 +1,25 @@
 // The converged frame of a dense packed volume as a RAY STREAM (gfx950): the same frame as render.hip's plain kernel, bit for
 // bit, drawn by four lean passes instead of one kernel that carries a sample from its view ray to its colour.
 //
-//   ca_stream_walk<primary>   persistent; lanes take sample jobs of the volume's screen rectangle from queues of 64-job chunks,
-//                             form the view ray (shade_sample up to its walk) and walk it; answer per job: hit distance | none
+//   ca_stream_walk2<primary>  persistent; waves draw sample jobs of the volume's screen rectangle from eight ticket counters, set
+//                             up 64 view rays at a time (shade_sample up to its walk), queue them in LDS and walk them; answer per
+//                             job: hit distance | none
 //   ca_stream_shadow_rays     one lane per job: shade_sample with the answer looked up, up to the shadow ray; lit jobs leave the
 //                             point the shadow ray starts from
-//   ca_stream_walk<shadow>    persistent, the same stepping loop over the shadow rays; answer per lit job: occluded or not
+//   ca_stream_walk2<shadow>   persistent, the same stepping loop over the shadow rays; answer per lit job: occluded or not
 //   ca_stream_resolve         one lane per pixel: shade_sample with both answers looked up, samples summed in order, three outputs
+//
+// The walks read the bricked copy of the volume (render_frame.hip) where there is one, the row-major state otherwise (grids above
+// 2048, render_frame_bricks = 0): the same kernel, the same cells visited, the same frame.
 //
 // Why: in one kernel (ca_render_packed_sched) the stepping loop was ~110 vector instructions per cell at 30 of 64 lanes, compiled
 // at the 128-register edge the shading code sets (4 waves per SIMD), and a third of it was the slab test of the one or two lanes
-// that stood on a live cell. Here the stepping loop stands alone: ~17 registers of state, 8 waves per SIMD, a lane that finishes is
-// refilled from the queue at once (no tile to wait for), and the live-cell test is a conservative interval filter on the walk's own
-// boundary times (14 instructions) that calls the reference's slab test only when the two disagree within rounding — so the cells
-// visited, the hits found and the distances reported are those of the plain walk (pathtraced_fragment_clustered.wgsl:212-225 for
-// the test, 682-741 / 635-680 for what the walks replace). Everything per-sample and expensive (view ray, shading gate,
-// Cook-Torrance) runs in the two one-lane-per-job passes at full lane occupancy.
+// that stood on a live cell. Here the stepping loop stands alone, a lane that finishes takes a prepared ray at once (no tile to
+// wait for), and the live-cell test is a conservative interval filter on the walk's own boundary times (14 instructions) that
+// calls the reference's slab test only when the two disagree within rounding — so the cells visited, the hits found and the
+// distances reported are those of the plain walk (pathtraced_fragment_clustered.wgsl:212-225 for the test, 682-741 / 635-680 for
+// what the walks replace). Everything per-sample and expensive (view ray, shading gate, Cook-Torrance) runs in the two
+// one-lane-per-job passes at full lane occupancy.
 //
 // Built with -ffp-contract=off like render.hip: every pass instantiates the same shade_sample_with, and the walks' boundary times are
 // accumulated by the same float operations as render_device.inc's walk().
@@ -37,15 +41,7 @@ constexpr u32 kNoHit = 0xFFFFFFFFu; // a hit distance is never NaN (the slab tes
 constexpr u32 kUnanswered = 0x5A5A5A5Au; // check build: what the answer arrays are filled with before the passes (a distance of 1.5e16)
 enum : unsigned char { kOcclNone = 0, kOcclHit = 1, kOcclPending = 2 };
 
-#ifndef CA3D_STREAM_WAVES
-#define CA3D_STREAM_WAVES 8
-#endif
-constexpr int kStreamWaves = CA3D_STREAM_WAVES; // waves per SIMD the walk kernel is compiled for
 constexpr int kStatSlots = 64;
-#ifndef CA3D_STREAM_INNER
-#define CA3D_STREAM_INNER 1
-#endif
-constexpr int kInner = CA3D_STREAM_INNER; // cells a lane may advance per read of the volume (stepping loop; 3 measured SLOWER: below)
 
 struct StreamParams
 {
@@ -55,24 +51,22 @@ struct StreamParams
 	float4 *rays;        // per lit job: the point the shadow ray starts from
 	u32 *ctl;            // [2] filter / slab-test contradictions (check build); [16 + 4 * slot + {0 shadow rays, 1 primary visits, 2 shadow
 	                     // visits}] statistics, kStatSlots slots; [kQueueWords + 32 * (8 * pass + q)] head of queue q of walk pass `pass`
-	u32 chunks, chunks_x; // chunks of 64 jobs = pixel blocks (4 x 4 pixels at 4 samples, 8 x 8 at one) of the rectangle, row-major;
-	                      // jobs of chunk c: [64 c, 64 c + 64), pixel-major, a pixel's samples next to each other
+	u32 chunks, chunks_x; // chunks of 256 jobs = pixel blocks (8 x 8 pixels at 4 samples, 16 x 16 at one) of the rectangle, row-major;
+	                      // jobs of chunk c: [256 c, 256 c + 256), pixel-major, a pixel's samples next to each other
 	const u32 *volume;   // what the walks read: R.cells, or the bricked copy of it
 	u32 lg, lc;          // log2 G, log2 cols (power-of-two grids)
 	u32 nb;              // bricks per edge, G / 8
 	u32 lnbp;            // packed cell positions (kBricksPacked): bits of a brick coordinate, log2 nb
-	u32 probe_mask;      // timing probes (kProbe*): 0
-	int tail_batch;      // ca_stream_walk2: 1 = the batched stepping loop once a wave cannot refill any more and in the drain launch
-	int refill2;         // ca_stream_walk2: idle lanes at which a wave leaves the stepping loop to pop prepared rays (tuning: CA3D_STREAM_POP)
-	int refill;          // lanes without a ray at which a wave leaves the stepping loop to take new jobs (tuning: CA3D_STREAM_REFILL)
+	int tail_batch;      // 1 = the batched stepping loop once a wave cannot refill any more (2, tuning: from the first cell on)
+	int pop_at;          // idle lanes at which a wave leaves the stepping loop to pop prepared rays (tuning: CA3D_STREAM_POP)
 	u32 lb;              // log2 of a chunk's pixel-block edge; jobs per chunk = spp << (2 lb)
 	u32 qmap;            // 0: queue q owns a contiguous eighth of the chunks (a band of the image); 1: every eighth chunk
 	u32 skip_ok;         // 1: sparse (scattered) volumes are drawn by the stream passes too — ca_stream_walk2<.., SKIP = true> (round 5, late)
 	u32 check;           // diagnostics build: answers were pre-set to kUnanswered and whoever looks one up counts those still unset in ctl[3]
 	unsigned long long *trace; // diagnostics (CA3D_STREAM_TRACE=<file>): 8 words per wave and walk pass — start, end (s_memrealtime, 100 MHz),
-	                           // refill rounds, stepping iterations, chunks taken, ticks spent refilling, jobs started, 0
+	                           // refill rounds, 0, 0, ticks spent refilling, jobs started, 0
 };
-constexpr u32 kQueueWords = 512, kNoChunk = 0xFFFFFFFFu;
+constexpr u32 kQueueWords = 512;
 
 // Which frames the stream passes draw: dense volumes; and, with skip_ok, sparse volumes whose live cells are scattered (the block-skipping
 // walk inside ca_stream_walk2<.., true>). A sparse volume with a small live box stays with render.hip's spread kernel.
@@ -177,10 +171,10 @@ struct Walker
 // 2.32, bricks 0.80 / 1.98, bricks + a read per cell 0.785 / 1.94; a whole 8 x 8 z-slice per lane in two registers 0.805 / 2.11.
 // kBricksReadAny: the same over the bricks of a grid that is not a power of two (96, 160, ..., 992): G / 8 bricks per edge, padded to a power
 // of two in the address (render_frame.hip, ca_brick_volume_any), so the brick index is shifts there too.
-// kProbe*: timing probes of the stepping loop (CA3D_STREAM_PROBE=1..4; the frame is garbage: no cell is ever taken for live, every walk runs to
-// the end of the volume, so the four differ ONLY in what the read costs): no read at all / every lane reads word 0 (one cache line per
-// wave-level read) / word key & 1023 (a 4 KiB footprint, as many lines per read as the real walk) / the real word.
-enum { kRowsP2 = 0, kRowsAny = 1, kBricks = 2, kBricksRead = 3, kBricksReadAny = 4, kProbeNone = 5, kProbeSame = 6, kProbeSmall = 7, kProbeFull = 8, kBricksPacked = 9 };
+// kRowsP2 / kRowsAny: the row-major state (grids above 2048, where there is no bricked copy; render_frame_bricks = 0); the walker keeps
+// the last word it read and reads again only when its cell leaves it.
+// (The values are those of the kernels' names in earlier profiles.)
+enum { kRowsP2 = 0, kRowsAny = 1, kBricksRead = 3, kBricksReadAny = 4, kBricksPacked = 9 };
 
 template <int LAYOUT>
 __device__ __forceinline__ int word_key(const StreamParams &S, int ix, int iy, int iz)
@@ -190,7 +184,7 @@ __device__ __forceinline__ int word_key(const StreamParams &S, int ix, int iy, i
 		const u32 b = (((((u32)iz >> 3) << S.lnbp) + ((u32)iy >> 3)) << S.lnbp) + ((u32)ix >> 3); // (bricks per edge padded to a power of two in the address)
 		return (int)((b << 4) + (((u32)iz & 7u) << 1) + (((u32)iy & 7u) >> 2));
 	}
-	if (LAYOUT == kBricks || LAYOUT == kBricksRead || LAYOUT >= kProbeNone)
+	if (LAYOUT == kBricksRead)
 	{
 		const u32 lnb = S.lg - 3u;
 		const u32 b = (((((u32)iz >> 3) << lnb) + ((u32)iy >> 3)) << lnb) + ((u32)ix >> 3);
@@ -202,11 +196,13 @@ __device__ __forceinline__ int word_key(const StreamParams &S, int ix, int iy, i
 template <int LAYOUT>
 __device__ __forceinline__ u32 word_bit(int ix, int iy)
 {
-	return (LAYOUT == kBricks || LAYOUT == kBricksRead || LAYOUT == kBricksReadAny || LAYOUT >= kProbeNone) ? (((u32)ix & 7u) | (((u32)iy & 3u) << 3)) : ((u32)ix & 31u);
+	return (LAYOUT == kBricksRead || LAYOUT == kBricksReadAny) ? (((u32)ix & 7u) | (((u32)iy & 3u) << 3)) : ((u32)ix & 31u);
 }
 
-// walk_begin of render.hip / the head of walk(): first cell, boundary times, increments
-__device__ __forceinline__ void walker_begin(const RenderParams &P, Walker &w, v3 start, v3 dir, float t0, float tmax, float *ctx, int stride)
+// walk_begin of render.hip / the head of walk(): first cell, boundary times, increments in `w`; what the slab test reads (ray origin and
+// 1 / direction) in c6 — it goes into LDS with the queued ray, not into registers: only a lane whose filter cannot decide and a lane that
+// reports a hit look at it
+__device__ __forceinline__ void walker_prepare(const RenderParams &P, Walker &w, bool &axis_parallel, float c6[6], v3 start, v3 dir, float t0, float tmax)
 {
 	const int G = (int)P.G;
 	const float cs = 1.0f / (float)P.G;
@@ -229,18 +225,18 @@ __device__ __forceinline__ void walker_begin(const RenderParams &P, Walker &w, v
 	w.sx = sx; w.sy = sy; w.sz = sz;
 	w.word = 0;
 	w.wkey = -1;
-	// Error bound of the interval filter (walk_cell below). The filter reads the hit cube's slab times off the walk's boundary times:
+	// Error bound of the interval filter (walk_cell_word below). The filter reads the hit cube's slab times off the walk's boundary times:
 	// along axis a the cell is left at ta (accumulated: a division, then k <= t / da + 1 additions of da, each rounded) and the cube of
 	// half-size h spans [ta - k1 da, ta - k0 da], k0 = 1/2 - h / cs. Against the real slab times that is off by at most
 	// 2^-24 (t^2 / da + 3 t + 2 da) per axis; the reference's slab test ((c -+ h) - o) * (1 / d) is itself off by 2^-24 (G da + 2 t).
 	// With sum 1 / da = G sum |d| <= 1.74 G:  eps(t) = 2^-21 G t^2 + 2^-18 t + 2^-20 (G + 8) (dx + dy + dz) covers the sum of both
 	// several times over, and a zero direction component (its slab times are +-inf in the reference's test) makes it infinite.
-	const bool axis_parallel = dir.x == 0.0f || dir.y == 0.0f || dir.z == 0.0f;
-	w.eps_b = axis_parallel ? __builtin_inff() : 9.5367431640625e-7f * ((float)P.G + 8.0f) * (w.dx + w.dy + w.dz);
-	// what the slab test reads: ray origin and 1 / direction — in LDS, not in registers: only a lane whose filter cannot decide
-	// and a lane that reports a hit look at them
-	ctx[0 * stride] = start.x; ctx[1 * stride] = start.y; ctx[2 * stride] = start.z;
-	ctx[3 * stride] = 1.0f / dir.x; ctx[4 * stride] = 1.0f / dir.y; ctx[5 * stride] = 1.0f / dir.z;
+	// The walker's constant term eps_b is set when a lane pops the ray: from axis_parallel (one bit of the queued record) and
+	// eps_c = 2^-20 (G + 8) in ca_stream_walk2.
+	axis_parallel = dir.x == 0.0f || dir.y == 0.0f || dir.z == 0.0f;
+	w.eps_b = 0.0f;
+	c6[0] = start.x; c6[1] = start.y; c6[2] = start.z;
+	c6[3] = 1.0f / dir.x; c6[4] = 1.0f / dir.y; c6[5] = 1.0f / dir.z;
 }
 
 // the reference's slab test of the cube in the walker's cell (ray_cube_inv: bit-identical to ray_cube)
@@ -253,43 +249,9 @@ __device__ __forceinline__ bool slab_test_at(const RenderParams &P, int ix, int 
 	ray_cube_inv(start, inv, cell_origin(1.0f / (float)P.G, ix, iy, iz), vhalf, tn, tf);
 	return SHADOW ? (tn <= tf && tn >= 0.0f) /* :668 */ : (tf >= 0.0f && tn <= tf) /* :722-729 */;
 }
-template <bool SHADOW>
-__device__ __forceinline__ bool slab_test(const RenderParams &P, const Walker &w, v3 vhalf, const float *ctx, int stride, float &tn)
-{
-	return slab_test_at<SHADOW>(P, w.ix, w.iy, w.iz, vhalf, ctx, stride, tn);
-}
 
-template <bool SHADOW, int LAYOUT, bool CHECK>
-__device__ __forceinline__ int walk_cell_word(const StreamParams &S, Walker &w, u32 cur, bool &exempt, v3 vhalf, float k0, float k1, float eps_a,
-                                              const float *ctx, int stride);
-
-// One cell of the walk. Returns 0 keep walking, 1 hit, 2 the ray left the volume or ran out of range.
-//   k0, k1: the cube's slab offsets in units of the cell's crossing time (walker_begin); eps_a = 2^-21 G
-//   LOAD: the lane may read the volume (the first pass of an iteration of the stepping loop); false: the caller has made sure the
-//   cell lies in what the lane holds (key == w.wkey)
-template <bool SHADOW, int LAYOUT, bool CHECK, bool LOAD>
-__device__ __forceinline__ int walk_cell(const StreamParams &S, Walker &w, int key, bool &exempt, v3 vhalf, float k0, float k1, float eps_a,
-                                         const float *ctx, int stride)
-{
-	const RenderParams &P = S.R;
-	// (a 32-bit byte offset from the scalar base: one shift instead of a sign extension and a 64-bit add per visit)
-	u32 cur;
-	if (LAYOUT >= kProbeNone)
-	{
-		const u32 k2 = LAYOUT == kProbeSame ? 0u : (LAYOUT == kProbeSmall ? ((u32)key & 1023u) : (u32)key);
-		cur = LAYOUT == kProbeNone ? (u32)key : *reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(S.volume) + (k2 << 2));
-		cur &= S.probe_mask; // 0 at run time: the compiler cannot drop the read, and no cell is live
-	}
-	else if (LAYOUT == kBricksRead || LAYOUT == kBricksReadAny) cur = *reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(S.volume) + ((u32)key << 2));
-	else
-	{
-		if (LOAD && key != w.wkey) { w.word = *reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(S.volume) + ((u32)key << 2)); w.wkey = key; }
-		cur = w.word;
-	}
-	return walk_cell_word<SHADOW, LAYOUT, CHECK>(S, w, cur, exempt, vhalf, k0, k1, eps_a, ctx, stride);
-}
-
-// walk_cell behind its read: `cur` is the word of the walker's cell
+// One cell of the walk, `cur` the word of the walker's cell. Returns 0 keep walking, 1 hit, 2 the ray left the volume or ran out of range.
+//   k0, k1: the cube's slab offsets in units of the cell's crossing time (walker_prepare); eps_a = 2^-21 G
 template <bool SHADOW, int LAYOUT, bool CHECK>
 __device__ __forceinline__ int walk_cell_word(const StreamParams &S, Walker &w, u32 cur, bool &exempt, v3 vhalf, float k0, float k1, float eps_a,
                                               const float *ctx, int stride)
@@ -305,7 +267,7 @@ __device__ __forceinline__ int walk_cell_word(const StreamParams &S, Walker &w, 
 		if (CHECK)
 		{
 			float e;
-			const bool truth = slab_test<SHADOW>(P, w, vhalf, ctx, stride, e);
+			const bool truth = slab_test_at<SHADOW>(P, w.ix, w.iy, w.iz, vhalf, ctx, stride, e);
 			if ((yes && !truth) || (no && truth)) atomicAdd(&S.ctl[2], 1u);
 			if (truth) return 1;
 		}
@@ -315,7 +277,7 @@ __device__ __forceinline__ int walk_cell_word(const StreamParams &S, Walker &w, 
 			if (!no)
 			{
 				float e;
-				if (slab_test<SHADOW>(P, w, vhalf, ctx, stride, e)) return 1;
+				if (slab_test_at<SHADOW>(P, w.ix, w.iy, w.iz, vhalf, ctx, stride, e)) return 1;
 			}
 		}
 	}
@@ -336,6 +298,22 @@ __device__ __forceinline__ int walk_cell_word(const StreamParams &S, Walker &w, 
 	return (outside || t >= w.tmax) ? 2 : 0;
 }
 
+// walk_cell_word with its read: bricks are read at every cell, rows only when the cell leaves the word the walker holds
+// (a 32-bit byte offset from the scalar base: one shift instead of a sign extension and a 64-bit add per visit)
+template <bool SHADOW, int LAYOUT, bool CHECK>
+__device__ __forceinline__ int walk_cell(const StreamParams &S, Walker &w, int key, bool &exempt, v3 vhalf, float k0, float k1, float eps_a,
+                                         const float *ctx, int stride)
+{
+	u32 cur;
+	if (LAYOUT == kBricksRead || LAYOUT == kBricksReadAny) cur = *reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(S.volume) + ((u32)key << 2));
+	else
+	{
+		if (key != w.wkey) { w.word = *reinterpret_cast<const u32 *>(reinterpret_cast<const char *>(S.volume) + ((u32)key << 2)); w.wkey = key; }
+		cur = w.word;
+	}
+	return walk_cell_word<SHADOW, LAYOUT, CHECK>(S, w, cur, exempt, vhalf, k0, k1, eps_a, ctx, stride);
+}
+
 // ---- the batched form of the stepping loop -----------------------------------------------------------------------------------
 // The walk's next cell depends on arithmetic only (the boundary times), never on what the volume holds: a lane can run kBatch cells
 // ahead, ask for all their words at once and test them in order when they arrive — ONE memory round trip per kBatch cells instead
@@ -347,9 +325,10 @@ __device__ __forceinline__ int walk_cell_word(const StreamParams &S, Walker &w, 
 //             live cell in turn for the interval filter / slab test — a hit ends the walk there, with the walker standing on the
 //             hit cell as the retire step expects; a lane without a hit ends where the forward pass ended.
 // Cells visited, hits and the state a hit leaves are those of the cell-by-cell loop (the same advance, the same filter).
-// Measured (CA3D_STREAM_BRICKS=3 selects it; bit-identical frames, the check mode passes): 1080p 4 spp 0.888 against 0.900 ms, one
-// sample 0.529 against 0.549, 4K 2.27 against 2.14 — a quarter of the memory round trips and no faster: like every other probe of
-// the stepping loop (see the cell-by-cell loop below) it says the walks are not waiting for the volume. Kept as an option.
+// Measured as the loop of a whole launch (round 4's walk kernel; bit-identical frames, the check mode passes): 1080p 4 spp 0.888
+// against 0.900 ms, one sample 0.529 against 0.549, 4K 2.27 against 2.14 — a quarter of the memory round trips and no faster: like
+// every other probe of the stepping loop (below) it says the walks are not waiting for the volume. Where it pays is the tail of a
+// launch (ca_stream_walk2).
 #ifndef CA3D_STREAM_BATCH
 #define CA3D_STREAM_BATCH 4
 #endif
@@ -384,13 +363,13 @@ __device__ __forceinline__ bool walk_hit_test(const StreamParams &S, const Walke
 	float e;
 	if (CHECK)
 	{
-		const bool truth = slab_test<SHADOW>(P, w, vhalf, ctx, stride, e);
+		const bool truth = slab_test_at<SHADOW>(P, w.ix, w.iy, w.iz, vhalf, ctx, stride, e);
 		if ((yes && !truth) || (no && truth)) atomicAdd(&S.ctl[2], 1u);
 		return truth;
 	}
 	if (yes) return true;
 	if (no) return false;
-	return slab_test<SHADOW>(P, w, vhalf, ctx, stride, e);
+	return slab_test_at<SHADOW>(P, w.ix, w.iy, w.iz, vhalf, ctx, stride, e);
 }
 
 // One batch for a lane with a ray. Returns the cells it visited; term: 0 keep walking, 1 hit (the walker stands on the cell), 2 over.
@@ -579,270 +558,12 @@ __device__ __forceinline__ u32 walk_batch_p(const StreamParams &S, const PackGeo
 	return visited;
 }
 
-// Job source of the walk passes. The rectangle's jobs come in chunks (a pixel block x its samples, a power of two of jobs). Chunks
-// are handed to WORKGROUPS — eight queues, one per XCD (workgroups go to the XCDs round-robin), a load before the atomic so that an
-// empty queue costs none, the first chunk of a workgroup its own (thousands of pullers asking at once queue for tens of
-// microseconds behind a word: ~88 dequeues per us) — and inside a workgroup the jobs are handed to LANES through a ticket counter in
-// LDS: a wave whose idle lanes reach the refill threshold draws that many tickets; ticket t is job t % per of the workgroup's
-// (t / per)-th chunk. The wave that draws the first ticket of chunk k fetches chunk k + 1's id from the global queue and posts it in a
-// ring of slots, so the id is there long before chunk k runs out; a lane whose ticket lands in a chunk not yet posted waits for it.
-// When the queues run dry the id posted is "none", and so is every id after it.
-// Per-wave chunk ownership (the first form of this kernel) left waves with one or with two heavy chunks of 256 jobs: the launch
-// lasted twice the average wave's life. Chunks of 64 jobs handed to waves through the global queues cost more in atomics than they
-// balanced (1.55 ms against 0.90).
-constexpr int kWalkThreads = 512, kWalkWaves = kWalkThreads / 64, kSlots = 8;
-
-template <bool SHADOW, int LAYOUT, bool CHECK, bool BATCHED>
-__global__ __launch_bounds__(kWalkThreads, kStreamWaves) void ca_stream_walk(StreamParams S)
-{
-	const RenderParams &P = S.R;
-	if (occ_skip_enabled(P)) return; // a sparse volume: the skipping kernels of render.hip draw the frame
-	__shared__ float ctx_lds[6][kWalkThreads];
-	__shared__ u32 q_ticket, q_id[kSlots], q_seq[kSlots], q_read[kSlots];
-	const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	float *ctx = &ctx_lds[0][tid];
-	constexpr int stride = kWalkThreads;
-	const float cs = 1.0f / (float)P.G;
-	const float vis = cs * P.u[U_CELLSIZE] * 0.5f;
-	const v3 vhalf = V(vis, vis, vis);
-	const float k0 = 0.5f - 0.5f * fabsf(P.u[U_CELLSIZE]), k1 = 1.0f - k0;
-	const float eps_a = 4.76837158203125e-7f * (float)P.G;
-	const u32 qown = blockIdx.x & 7u;
-	u32 qcur = qown, qtried = 0;
-	const u32 lper = 2u * S.lb + job_shift(P), per = 1u << lper; // jobs of a chunk
-	auto q_lo = [&](u32 q) { return S.qmap ? q : (u32)(((unsigned long long)S.chunks * q) >> 3); };
-	auto q_len = [&](u32 q) { return S.qmap ? (S.chunks + 7u - q) >> 3 : q_lo(q + 1u) - q_lo(q); };
-	auto q_chunk = [&](u32 q, u32 pos) { return S.qmap ? pos * 8u + q : q_lo(q) + pos; };
-	auto q_static = [&](u32 q) { return (gridDim.x + 7u - q) >> 3; }; // workgroups whose own chunk comes out of queue q
-	auto next_chunk = [&]() -> u32 { // wave-uniform
-		while (qtried < 8u)
-		{
-			u32 *head = S.ctl + kQueueWords + 32u * ((SHADOW ? 8u : 0u) + qcur);
-			const u32 len = q_len(qcur), st = q_static(qcur);
-			u32 pos = kNoChunk;
-			if (lane == 0)
-			{
-				if (st + __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < len) pos = st + atomicAdd(head, 1u);
-			}
-			pos = (u32)__builtin_amdgcn_readfirstlane((int)pos);
-			if (pos < len) return q_chunk(qcur, pos);
-			qcur = (qcur + 1u) & 7u;
-			qtried++;
-		}
-		return kNoChunk;
-	};
-	if (wave == 0)
-	{
-		const u32 idx = blockIdx.x >> 3;
-		const u32 c0 = idx < q_len(qown) ? q_chunk(qown, idx) : next_chunk();
-		if (lane == 0) { q_ticket = 0; q_id[0] = c0; q_seq[0] = 1u; }
-		if (lane > 0 && lane < kSlots) q_seq[lane] = 0u;
-		if (lane < kSlots) q_read[lane] = 0u;
-	}
-	__syncthreads();
-	bool more = true;
-	int job = -1, term = 0;
-	bool exempt = false;
-	Walker w;
-	u32 visits = 0; // wave-uniform
-	const unsigned long long tr_t0 = S.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
-	unsigned long long tr_refill = 0;
-	u32 tr_rounds = 0, tr_chunks = 0, tr_jobs = 0;
-	const u32 tr_iters = 0; // (not counted: a counter in the stepping loop costs every frame an instruction per cell visit)
-	for (;;)
-	{
-		// retire the lanes whose walk is over
-		if (job >= 0 && term != 0)
-		{
-			if (SHADOW) S.occl[job] = term == 1 ? kOcclHit : kOcclNone;
-			else
-			{
-				u32 out = kNoHit;
-				if (term == 1)
-				{
-					float tn;
-					slab_test<false>(P, w, vhalf, ctx, stride, tn); // the distance the plain walk reports: the slab test's own
-					out = __float_as_uint(tn);
-				}
-				S.hit[job] = out;
-			}
-			job = -1;
-			term = 0;
-		}
-		// refill
-		const unsigned long long tr_r0 = S.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
-		for (;;)
-		{
-			const unsigned long long idle = __ballot(job < 0);
-			const int nidle = __popcll(idle);
-			if (!more || nidle < S.refill) break;
-			tr_rounds++;
-			u32 base = 0;
-			if (lane == 0) base = atomicAdd(&q_ticket, (u32)nidle);
-			base = (u32)__builtin_amdgcn_readfirstlane((int)base);
-			// the first ticket of a chunk is among these: post the next chunk's id (at most one chunk starts in a draw: nidle <= 64 <= per)
-			const u32 kfirst = (base + per - 1u) >> lper;
-			if ((kfirst << lper) < base + (u32)nidle)
-			{
-				// ... unless chunk kfirst itself is "none": the queues ran dry, and everything after the first "none" must be "none" too —
-				// a wave that meets one stops drawing, so a real chunk posted behind it would never be drawn (two posters racing for the
-				// last chunks of the queues did exactly that: the one for chunk k got nothing, the one for k + 1 the last chunk). Chunk
-				// kfirst was asked for a whole chunk ago: it is there.
-				u32 prev = 0;
-				if (lane == 0)
-				{
-					while (__hip_atomic_load(&q_seq[kfirst % kSlots], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != kfirst + 1u) __builtin_amdgcn_s_sleep(1);
-					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-					prev = q_id[kfirst % kSlots];
-				}
-				prev = (u32)__builtin_amdgcn_readfirstlane((int)prev);
-				const u32 c = prev == kNoChunk ? kNoChunk : next_chunk();
-				tr_chunks++;
-				if (lane == 0)
-				{
-					// the slot's last tenant (chunk kfirst + 1 - kSlots) must have been read by every lane that drew one of its tickets:
-					// q_read counts the tickets read per slot, all of its tenants together (they were all drawn before this draw, and a
-					// drawer reads at once: the wait is over before it begins, but it is what makes the ring safe)
-					const u32 m = kfirst + 1u;
-					while (__hip_atomic_load(&q_read[m % kSlots], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != (m / kSlots) << lper) __builtin_amdgcn_s_sleep(1);
-					q_id[(kfirst + 1u) % kSlots] = c;
-					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-					__hip_atomic_store(&q_seq[(kfirst + 1u) % kSlots], kfirst + 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-				}
-			}
-			bool dry = false;
-			if (job < 0)
-			{
-				const u32 t = base + (u32)__popcll(idle & ((1ull << lane) - 1ull));
-				const u32 k = t >> lper, cand = t & (per - 1u);
-				while (__hip_atomic_load(&q_seq[k % kSlots], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != k + 1u) __builtin_amdgcn_s_sleep(2);
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-				const u32 chunk = q_id[k % kSlots];
-				if (chunk == kNoChunk) dry = true;
-				else
-				{
-					const u32 j = chunk * per + cand;
-					u32 px, py, ks;
-					job_pixel(S, chunk, cand, px, py, ks);
-					if (!SHADOW)
-					{
-						if (px < P.W && py < P.row1)
-						{
-							float vu, vv;
-							sample_uv(P, px, py, ks, vu, vv);
-							CapturePrimary tr;
-							shade_sample_with(P, vu, vv, tr);
-							if (tr.wanted)
-							{
-								if (0.0f >= tr.len) S.hit[j] = kNoHit; // walk(): `if (t >= tmax) return false` before the first cell
-								else
-								{
-									walker_begin(P, w, tr.enter, tr.dir, 0.0f, tr.len, ctx, stride);
-									job = (int)j;
-								}
-							}
-						}
-					}
-					else if (S.occl[j] == kOcclPending)
-					{
-						// shade_sample_with between the shading gate and the shadow walk
-						const float4 r = S.rays[j];
-						const v3 p = V(r.x, r.y, r.z);
-						const v3 light_pos = V(P.u[U_LIGHT], P.u[U_LIGHT + 1], P.u[U_LIGHT + 2]);
-						const v3 ldir = norm3(light_pos - p);
-						float vn, vf;
-						ray_cube(p, ldir, V(0.0f, 0.0f, 0.0f), V(kHalf, kHalf, kHalf), vn, vf);
-						const v3 vexit = p + ldir * vf;
-						const v3 sseg = vexit - p;
-						const float slen = len3(sseg);
-						if (0.0025f >= slen) S.occl[j] = kOcclNone;
-						else
-						{
-							walker_begin(P, w, p, norm3(sseg), 0.0025f, slen, ctx, stride);
-							const int cx = (int)floorf(to_cells(P, p.x)), cy = (int)floorf(to_cells(P, p.y)), cz = (int)floorf(to_cells(P, p.z));
-							exempt = w.ix == cx && w.iy == cy && w.iz == cz; // any(cell != startCell) :664
-							job = (int)j;
-						}
-					}
-				}
-			}
-			if (__ballot(dry) != 0ull) more = false; // the queues are empty (every later chunk is posted as "none" too)
-			if (lane == 0)
-			{
-				// tickets read, per chunk (a draw spans at most two)
-				const u32 klo = base >> lper, nlo = min((u32)nidle, ((klo + 1u) << lper) - base);
-				atomicAdd(&q_read[klo % kSlots], nlo);
-				if ((u32)nidle > nlo) atomicAdd(&q_read[(klo + 1u) % kSlots], (u32)nidle - nlo);
-			}
-		}
-		int walking = __popcll(__ballot(job >= 0));
-		if (S.trace) { tr_refill += __builtin_amdgcn_s_memrealtime() - tr_r0; tr_jobs += (u32)walking; }
-		if (walking == 0)
-		{
-			if (!more) break;
-			continue;
-		}
-		// (readfirstlane: the loop's bookkeeping — counts, threshold, exit — is wave-uniform and the compiler is told so: scalar
-		// registers and a scalar branch instead of an exec-masked loop with its per-iteration v_cndmask / v_cmp of uniform values)
-		const int leave_at = __builtin_amdgcn_readfirstlane(more ? 64 - S.refill : 0);
-		if (BATCHED)
-		{
-			do
-			{
-				u32 n = 0;
-				if (job >= 0 && term == 0) n = walk_batch<SHADOW, LAYOUT, CHECK>(S, w, exempt, term, vhalf, k0, k1, eps_a, ctx, stride);
-				// cells visited by the wave: n is 0 .. kBatch per lane
-#pragma unroll
-				for (int k = 0; k < kBatch; k++) visits += (u32)__builtin_amdgcn_readfirstlane(__popcll(__ballot(n > (u32)k)));
-				walking = __builtin_amdgcn_readfirstlane(__popcll(__ballot(job >= 0 && term == 0)));
-			} while (walking > leave_at);
-		}
-		else
-		// An iteration = one read of the volume per lane that needs one, then up to kInner cells (kInner > 1: the lanes whose next cell
-		// lies in what they hold go on without reading). What the loop is bound by was probed from every side (1080p, 4 samples, dense
-		// scene, kernel ms): 8 -> 4 waves per SIMD 0.87 -> 0.90; ten instructions fewer per cell (scalar bookkeeping, 32-bit offsets) no
-		// change; + 16 dependent VALU or + 16 SALU per cell + 8-9 %; bricks instead of rows (a quarter of the cache lines per read) - 1 %,
-		// a whole 8 x 8 z-slice per lane (40 % fewer reads) - 4 %; kInner = 3 (a third fewer wave-level reads, more passes at low lane
-		// occupancy) + 13 %. PMC: the waves sit in s_waitcnt for 64-72 % of their cycles and issue VALU in 10-13 %. A latency chain per
-		// wave — cell -> key -> read -> test -> advance — that more waves do not hide (they queue behind the same vector L1) and that
-		// fewer instructions do not shorten much: the per-cell cost is the chain. Two more forms were built on top, both bit-identical,
-		// neither faster: the batched loop below (four cells per memory round trip) and ray set-up moved out of the walkers into
-		// one-lane-per-job passes that leave 64-byte ray records (the walkers' refill was 40 % of their vector instructions: 926 static
-		// VALU and 25 divisions per round, against ~55 per cell) — 0.93 ms against 0.87 at 1080p, 2.43 against 2.14 at 4K: the record
-		// traffic cost more than the instructions it removed, the per-wave timeline (tools/stream_trace.py) stayed what it was — every
-		// wave alive for the first 45 % of a launch, mean life 225 of 369 us, 11 refill rounds of ~3 us of latency each.
-		do
-		{
-			int key = word_key<LAYOUT>(S, w.ix, w.iy, w.iz);
-			visits += (u32)walking;
-			if (job >= 0 && term == 0) term = walk_cell<SHADOW, LAYOUT, CHECK, true>(S, w, key, exempt, vhalf, k0, k1, eps_a, ctx, stride);
-#pragma unroll
-			for (int k = 1; k < kInner; k++)
-			{
-				key = word_key<LAYOUT>(S, w.ix, w.iy, w.iz);
-				const bool go = job >= 0 && term == 0 && key == w.wkey;
-				const int n = __builtin_amdgcn_readfirstlane(__popcll(__ballot(go)));
-				if (n == 0) break;
-				visits += (u32)n;
-				if (go) term = walk_cell<SHADOW, LAYOUT, CHECK, false>(S, w, key, exempt, vhalf, k0, k1, eps_a, ctx, stride);
-			}
-			walking = __builtin_amdgcn_readfirstlane(__popcll(__ballot(job >= 0 && term == 0)));
-		} while (walking > leave_at);
-	}
-	if (S.trace && lane == 0)
-	{
-		unsigned long long *t = S.trace + 8ull * ((SHADOW ? gridDim.x * (u32)kWalkWaves : 0u) + blockIdx.x * (u32)kWalkWaves + (u32)wave);
-		t[0] = tr_t0; t[1] = __builtin_amdgcn_s_memrealtime(); t[2] = tr_rounds; t[3] = tr_iters; t[4] = tr_chunks; t[5] = tr_refill; t[6] = tr_jobs; t[7] = 0;
-	}
-	if (lane == 0 && visits) atomicAdd(&S.ctl[16 + 4 * ((blockIdx.x * (u32)kWalkWaves + (u32)wave) % kStatSlots) + (SHADOW ? 2 : 1)], visits);
-}
-
-// ---- second form of the walk passes (round 5; the default) -----------------------------------------------------------------------
-// What ca_stream_walk's time is made of was measured this round by taking the volume out of its stepping loop (CA3D_STREAM_PROBE: no
-// read / every lane the same word / a 4 KiB footprint / the real words — 2.34 / 1.91 / 2.40 / 2.39 ms for the same 967 M cell visits
-// with no cell ever live): with its lanes full and eight waves on a SIMD the loop does not wait for memory at all — it is bound by
-// instruction issue (~65 instructions per wave and cell, 62 % of the VALU issue slots) at 0.42 visits per ns. The real frame's
-// 123 M visits would take 0.29 ms at that rate; they took 0.69. The rest is what surrounds the loop:
+// ---- the walk passes --------------------------------------------------------------------------------------------------------
+// Where a persistent walk kernel's time goes was measured by taking the volume out of its stepping loop (DESIGN.md §5, round 4's walk
+// kernel: the same 967 M cell visits with no read, one word for every lane, a 4 KiB footprint and the real words took 2.34 / 1.91 /
+// 2.40 / 2.39 ms): with its lanes full and eight waves on a SIMD the loop does not wait for memory at all — it is bound by instruction
+// issue (~65 instructions per wave and cell) at 0.42 visits per ns. The real frame's 123 M visits would take 0.29 ms at that rate;
+// they took 0.69. The rest is what surrounds the loop:
 //   (a) a refill round set ~24 new rays up with the other 40 lanes of the wave idle (~900 instructions, 25 divisions), and three
 //       of four tickets of the shadow pass were samples without a shadow ray;
 //   (b) the loop ran between refills with up to 24 lanes empty (lanes active 0.46 / 0.43);
@@ -850,7 +571,7 @@ __global__ __launch_bounds__(kWalkThreads, kStreamWaves) void ca_stream_walk(Str
 //       walk ends after 9. When the queues run dry every wave is left with a handful of them and steps on for a hundred and more
 //       iterations at 5 of 64 lanes, alone or nearly alone on its SIMD — where an iteration is a dependent chain of ~1 200 cycles that
 //       nothing overlaps (tools/stream_trace.py: every wave alive for the first 55 % of a launch, mean life 0.68 of it).
-// This form:
+// So ca_stream_walk2:
 //   * sets rays up 64 AT A TIME — every lane, walking or not, takes a job and forms its ray (the walkers in flight stay in their
 //     registers) — and the prepared walk states go into a 64-slot queue of the wave in LDS (16 words per ray); a lane whose walk ends
 //     POPS a prepared state (16 LDS reads instead of the set-up), so the loop is left when 16 lanes are idle instead of 24;
@@ -860,11 +581,11 @@ __global__ __launch_bounds__(kWalkThreads, kStreamWaves) void ca_stream_walk(Str
 //     pixel is arithmetic, and the balance between waves is 64 jobs fine instead of a 256-job chunk per workgroup;
 //   * once a wave cannot refill any more it switches to the BATCHED stepping loop (walk_batch: four cells per memory round trip and
 //     per pass through the loop's bookkeeping): in the tail the chain per cell is what costs, and this is the one place where the
-//     batched loop pays (as the loop of the whole launch it measured no faster, above).
-// Same arithmetic per ray and cell, same answers: the frame is ca_stream_walk's and the plain kernel's bit for bit
-// (tests/test_gpu_render.py). Measured, dense bench scene, ms per frame, round 4's form -> this one (same box, same run):
-// 1080p 4 spp 0.792 -> 0.729, 3840 x 2160 1.946 -> 1.847, 1080p 1 spp 0.480 -> 0.440; lanes active in the walks 0.46 / 0.43 ->
-// 0.56 / 0.52 (the batched tail replays cells), vector instructions of the two walks 277 M -> 247 M. Without the batched tail 0.800: the tail is where the gain is.
+//     batched loop pays.
+// Same arithmetic per ray and cell, same answers: the frame is the plain kernel's bit for bit (tests/test_gpu_render.py). Measured,
+// dense bench scene, ms per frame, round 4's walk kernel -> this one (same box, same run): 1080p 4 spp 0.792 -> 0.729, 3840 x 2160
+// 1.946 -> 1.847, 1080p 1 spp 0.480 -> 0.440; lanes active in the walks 0.46 / 0.43 -> 0.56 / 0.52 (the batched tail replays cells),
+// vector instructions of the two walks 277 M -> 247 M. Without the batched tail 0.800: the tail is where the gain is.
 // Five waves per SIMD (88 / 81 registers, no scratch; six waves spill 64 bytes and measure 0.757; four 0.741).
 // Built on top and REMOVED again, both bit-identical and slower: a branch-free cell step (every lane computes filter and advance,
 // selects keep what must not change: 3 branches per cell instead of 8, but 9 % more vector instructions — 0.914 against 0.824);
@@ -876,35 +597,6 @@ __global__ __launch_bounds__(kWalkThreads, kStreamWaves) void ca_stream_walk(Str
 #define CA3D_STREAM2_WAVES 5
 #endif
 constexpr int kW2Threads = 256, kW2Waves = kW2Threads / 64, kW2PerSimd = CA3D_STREAM2_WAVES, kIdCap = 192, kRecWords = 16;
-// walker_begin without the LDS writes: the walk state in `w`, what the slab test reads in c6
-__device__ __forceinline__ void walker_prepare(const RenderParams &P, Walker &w, bool &axis_parallel, float c6[6], v3 start, v3 dir, float t0, float tmax)
-{
-	const int G = (int)P.G;
-	const float cs = 1.0f / (float)P.G;
-	const v3 p = start + dir * t0;
-	int ix = (int)floorf(to_cells(P, p.x)), iy = (int)floorf(to_cells(P, p.y)), iz = (int)floorf(to_cells(P, p.z));
-	ix = min(max(ix, 0), G - 1);
-	iy = min(max(iy, 0), G - 1);
-	iz = min(max(iz, 0), G - 1);
-	const int sx = dir.x > 0.0f ? 1 : -1, sy = dir.y > 0.0f ? 1 : -1, sz = dir.z > 0.0f ? 1 : -1;
-	const float big = 3.0e38f;
-	w.tx = dir.x != 0.0f ? (((float)(ix + (sx > 0 ? 1 : 0)) * cs - kHalf) - start.x) / dir.x : big;
-	w.ty = dir.y != 0.0f ? (((float)(iy + (sy > 0 ? 1 : 0)) * cs - kHalf) - start.y) / dir.y : big;
-	w.tz = dir.z != 0.0f ? (((float)(iz + (sz > 0 ? 1 : 0)) * cs - kHalf) - start.z) / dir.z : big;
-	w.dx = dir.x != 0.0f ? cs / fabsf(dir.x) : big;
-	w.dy = dir.y != 0.0f ? cs / fabsf(dir.y) : big;
-	w.dz = dir.z != 0.0f ? cs / fabsf(dir.z) : big;
-	w.t = t0;
-	w.tmax = tmax;
-	w.ix = ix; w.iy = iy; w.iz = iz;
-	w.sx = sx; w.sy = sy; w.sz = sz;
-	w.word = 0;
-	w.wkey = -1;
-	axis_parallel = dir.x == 0.0f || dir.y == 0.0f || dir.z == 0.0f; // (walker_begin: the filter's bound is infinite then)
-	w.eps_b = 0.0f;
-	c6[0] = start.x; c6[1] = start.y; c6[2] = start.z;
-	c6[3] = 1.0f / dir.x; c6[4] = 1.0f / dir.y; c6[5] = 1.0f / dir.z;
-}
 
 // SKIP (round 5, late): the walk of a SPARSE volume — walk<.., true> of render_device.inc, cell for cell: clipped to the live box at set-up
 // (live_box_clip), and a walker that enters a block the occupancy bits call empty (coarse 128 x 32 x 32, then fine 32 x 8 x 8; the last
@@ -946,8 +638,8 @@ __global__ __launch_bounds__(kW2Threads, kW2PerSimd) void ca_stream_walk2(Stream
 	auto q_static = [&](u32 q) { return (gridDim.x + 7u - q) >> 3; };
 	// Job source: tickets straight off eight GLOBAL counters (one per XCD: workgroups go to the XCDs round-robin, queue q owns every
 	// eighth chunk), 64 per draw, one per lane; ticket t of queue q is job (t mod tickets-per-chunk) of the queue's (t / tickets-per-
-	// chunk)-th chunk — arithmetic, no ring of chunk ids. ca_stream_walk hands whole chunks to workgroups and tickets to lanes through
-	// LDS: one global atomic per 256 jobs, but a workgroup that draws its last chunk just before the queues run dry ends a chunk's
+	// chunk)-th chunk — arithmetic, no ring of chunk ids. Round 4's walk kernel handed whole chunks to workgroups and tickets to lanes
+	// through LDS: one global atomic per 256 jobs, but a workgroup that draws its last chunk just before the queues run dry ends a chunk's
 	// worth (12-25 us, a tenth of the launch) after one that did not, and chunks differ by a factor of three in cost: wave lives
 	// spread over the last 45 % of a launch. At one atomic per 64 tickets the eight counters take 16 draws per us each (they sustain
 	// ~88), and the granularity of the balance is a quarter of a chunk per WAVE. A wave's first draw is static (its index in its
@@ -989,13 +681,13 @@ __global__ __launch_bounds__(kW2Threads, kW2PerSimd) void ca_stream_walk2(Stream
 	u32 visits = 0;              // wave-uniform
 	u32 idcount = 0;             // wave-uniform: ids waiting in ids[]
 	u32 qhead = 0, qavail = 0;   // wave-uniform: prepared rays rec[.][qhead .. qhead + qavail)
-	const int pop_at = S.refill2; // idle lanes at which the stepping loop is left for a pop
+	const int pop_at = S.pop_at; // idle lanes at which the stepping loop is left for a pop
 	const unsigned long long tr_t0 = S.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
 	unsigned long long tr_refill = 0;
 	u32 tr_rounds = 0, tr_jobs = 0;
 	for (;;)
 	{
-		// retire the lanes whose walk is over (ca_stream_walk's)
+		// retire the lanes whose walk is over
 		if (job >= 0 && term != 0)
 		{
 			if (SHADOW) S.occl[job] = term == 1 ? kOcclHit : kOcclNone;
@@ -1369,7 +1061,7 @@ __global__ __launch_bounds__(kW2Threads, kW2PerSimd) void ca_stream_walk2(Stream
 			{
 				const int key = word_key<LAYOUT>(S, w.ix, w.iy, w.iz);
 				visits += (u32)walking;
-				if (job >= 0 && term == 0) term = walk_cell<SHADOW, LAYOUT, CHECK, true>(S, w, key, exempt, vhalf, k0, k1, eps_a, ctx, stride);
+				if (job >= 0 && term == 0) term = walk_cell<SHADOW, LAYOUT, CHECK>(S, w, key, exempt, vhalf, k0, k1, eps_a, ctx, stride);
 				walking = __builtin_amdgcn_readfirstlane(__popcll(__ballot(job >= 0 && term == 0)));
 			} while (walking > leave_at);
 		}
@@ -1475,23 +1167,15 @@ __global__ __launch_bounds__(256) void ca_stream_resolve(StreamParams S)
 }
 
 // (S.skip_ok: the walks of a scattered sparse volume too — each of the two kernels of a pass returns at once on the frames of the other)
-template <int P2, bool CHECK>
+template <int LAYOUT, bool CHECK>
 void launch_walks2(const StreamParams &S, u32 wgs2, u32 job_blocks, hipStream_t stream)
 {
 	constexpr int PS = kBricksReadAny; // the skipping walk reads bricks cell by cell (not the packed positions); the brick index by the padded bit count — every grid's
-	hipLaunchKernelGGL((ca_stream_walk2<false, P2, CHECK>), dim3(wgs2), dim3(kW2Threads), 0, stream, S);
+	hipLaunchKernelGGL((ca_stream_walk2<false, LAYOUT, CHECK>), dim3(wgs2), dim3(kW2Threads), 0, stream, S);
 	if (S.skip_ok) hipLaunchKernelGGL((ca_stream_walk2<false, PS, CHECK, true>), dim3(wgs2), dim3(kW2Threads), 0, stream, S);
 	hipLaunchKernelGGL(ca_stream_shadow_rays, dim3(job_blocks), dim3(256), 0, stream, S);
-	hipLaunchKernelGGL((ca_stream_walk2<true, P2, CHECK>), dim3(wgs2), dim3(kW2Threads), 0, stream, S);
+	hipLaunchKernelGGL((ca_stream_walk2<true, LAYOUT, CHECK>), dim3(wgs2), dim3(kW2Threads), 0, stream, S);
 	if (S.skip_ok) hipLaunchKernelGGL((ca_stream_walk2<true, PS, CHECK, true>), dim3(wgs2), dim3(kW2Threads), 0, stream, S);
-}
-
-template <int P2, bool CHECK, bool BATCHED = false>
-void launch_walks(const StreamParams &S, u32 wgs, u32 job_blocks, hipStream_t stream)
-{
-	hipLaunchKernelGGL((ca_stream_walk<false, P2, CHECK, BATCHED>), dim3(wgs), dim3(kWalkThreads), 0, stream, S);
-	hipLaunchKernelGGL(ca_stream_shadow_rays, dim3(job_blocks), dim3(256), 0, stream, S);
-	hipLaunchKernelGGL((ca_stream_walk<true, P2, CHECK, BATCHED>), dim3(wgs), dim3(kWalkThreads), 0, stream, S);
 }
 
 } // namespace
@@ -1513,8 +1197,6 @@ hipError_t launch_render_stream(const void *params, void *scratch, uint32_t W, u
 {
 	StreamParams S;
 	S.R = *static_cast<const RenderParams *>(params);
-	S.skip_ok = 0u;
-	if (sparse_too) *sparse_too = false;
 	const RenderParams &P = S.R;
 	size_t hit_off, occl_off, rays_off;
 	stream_scratch_bytes(W, H, P.spp, &hit_off, &occl_off, &rays_off);
@@ -1523,14 +1205,13 @@ hipError_t launch_render_stream(const void *params, void *scratch, uint32_t W, u
 	S.hit = reinterpret_cast<u32 *>(base + hit_off);
 	S.occl = reinterpret_cast<unsigned char *>(base + occl_off);
 	S.rays = reinterpret_cast<float4 *>(base + rays_off);
-	static const int lb_env = getenv("CA3D_STREAM_LB") ? atoi(getenv("CA3D_STREAM_LB")) : 0;
 	static const int qmap_env = getenv("CA3D_STREAM_QMAP") ? atoi(getenv("CA3D_STREAM_QMAP")) : 0;
-	S.lb = lb_env >= 1 && lb_env <= 4 ? (u32)lb_env : (P.spp == 4u ? 3u : 4u); // pixel block of a chunk (the rectangle is aligned to 32 x 16)
+	S.lb = P.spp == 4u ? 3u : 4u; // pixel block of a chunk (the rectangle is aligned to 32 x 16)
 	S.qmap = qmap_env == 1 || !getenv("CA3D_STREAM_QMAP") ? 1u : 0u;
 	const u32 edge = 1u << S.lb;
 	S.chunks_x = (P.rx1 - P.rx0) / edge;
 	S.chunks = S.chunks_x * ((P.ry1 - P.ry0) / edge);
-	const u32 per = P.spp << (2u * S.lb);
+	const u32 per = P.spp << (2u * S.lb); // 256 jobs at one sample and at four (spp is 1 or 4): a chunk holds 64 tickets of two jobs and more
 	const bool p2 = (P.G & (P.G - 1u)) == 0u;
 	S.lg = S.lc = 0;
 	S.nb = P.G >> 3;
@@ -1541,8 +1222,6 @@ hipError_t launch_render_stream(const void *params, void *scratch, uint32_t W, u
 		while ((1u << S.lg) < P.G) S.lg++;
 		S.lc = S.lg - 5u;
 	}
-	static const int refill_env = getenv("CA3D_STREAM_REFILL") ? atoi(getenv("CA3D_STREAM_REFILL")) : 0;
-	S.refill = refill_env >= 1 && refill_env <= 64 ? refill_env : 24;
 	static const char *trace_path = getenv("CA3D_STREAM_TRACE");
 	static unsigned long long *trace_buf = nullptr;
 	const size_t trace_words = 8u * 2u * 4u * 256u * 8u * 2u; // two walk passes, up to 16 384 waves each
@@ -1560,59 +1239,42 @@ hipError_t launch_render_stream(const void *params, void *scratch, uint32_t W, u
 	if (e != hipSuccess) return e;
 	int dev = 0, cus = 256;
 	if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	const u32 wgs = min(S.chunks, (u32)cus * (u32)kStreamWaves * 4u / (u32)kWalkWaves); // persistent: what the chip holds at kStreamWaves per SIMD
 	const u32 job_blocks = (S.chunks * per + 255u) / 256u;
-	static const int bricks_env = getenv("CA3D_STREAM_BRICKS") ? atoi(getenv("CA3D_STREAM_BRICKS")) : 1; // tuning: 0 rows, 1 default, 2 bricks with a cached word, 3 batched loop
-	unsigned long long trace_waves = (unsigned long long)wgs * (unsigned)kWalkWaves;
-	const bool bricked = bricks && bricks_env && frame_bricks_applies(P.G);
+	const bool bricked = bricks && frame_bricks_applies(P.G);
 	S.volume = bricked ? bricks : P.cells;
-	if (bricked)
+	if (bricked && !bricks_valid) // (the engine says the bricks are those of this very state: a frame of the same state was drawn before)
 	{
-		if (!bricks_valid) // (the engine says the bricks are those of this very state: a frame of the same state was drawn before)
-		{
-			hipError_t eb = launch_brick_volume(P.cells, bricks, P.G, stream); // one pass over the state (~10 us at 512^3, 0.66 ms at 2048^3)
-			if (eb != hipSuccess) return eb;
-			if (bricks_built) *bricks_built = true;
-		}
-		// which form of the walk passes: 2 (default) sets rays up 64 at a time and queues them in LDS (ca_stream_walk2); 1: round 4's form
-		static const int form_env = getenv("CA3D_STREAM_FORM") ? atoi(getenv("CA3D_STREAM_FORM")) : 2;
-		static const int pop_env = getenv("CA3D_STREAM_POP") ? atoi(getenv("CA3D_STREAM_POP")) : 0;
-		S.refill2 = pop_env >= 1 && pop_env <= 64 ? pop_env : 16;
-		static const int tb_env = getenv("CA3D_STREAM_TAIL_BATCH") ? atoi(getenv("CA3D_STREAM_TAIL_BATCH")) : 1;
-		S.tail_batch = tb_env == 2 ? 2 : (tb_env ? 1 : 0); // (2, tuning: the batched loop from the first cell on)
-		// A persistent walk launch asks for the wave slots of the whole chip — unless other frames are in flight beside this one (ca3d_api.cpp,
-		// FrameLane): then for its share of them, so that the frames' walks run side by side from their first workgroup on instead of one
-		// launch filling the chip and the next one seeping into its tail (tools/sweep_stream_wgs.sh; CA3D_STREAM_WGS_PCT overrides: tuning).
-		static const int wgs_env = getenv("CA3D_STREAM_WGS_PCT") ? atoi(getenv("CA3D_STREAM_WGS_PCT")) : 0;
-		const u32 pct = (u32)(wgs_env >= 10 && wgs_env <= 100 ? wgs_env : (walk_share_pct >= 10 && walk_share_pct <= 100 ? walk_share_pct : 100));
-		const u32 wgs2 = max(8u, min(S.chunks, (u32)cus * (u32)kW2PerSimd * 4u / (u32)kW2Waves * pct / 100u));
-		const bool form2 = form_env == 2 && per >= 128u && bricks_env == 1; // (a chunk holds at least 64 tickets of two jobs)
-		// scattered sparse volumes through the stream passes as well (ca_stream_walk2<.., SKIP>; CA3D_STREAM_SKIP=0: render.hip's scheduled kernel, tuning / A-B)
-		static const int skip_env = getenv("CA3D_STREAM_SKIP") ? atoi(getenv("CA3D_STREAM_SKIP")) : 1;
-		S.skip_ok = form2 && skip_env && P.occ && !getenv("CA3D_STREAM_PROBE") ? 1u : 0u;
-		if (sparse_too) *sparse_too = S.skip_ok != 0u;
-		if (form2) trace_waves = (unsigned long long)wgs2 * (unsigned)kW2Waves;
-		static const int probe_env = getenv("CA3D_STREAM_PROBE") ? atoi(getenv("CA3D_STREAM_PROBE")) : 0;
-		static const int packed_env = getenv("CA3D_STREAM_PACKED") ? atoi(getenv("CA3D_STREAM_PACKED")) : 1; // tuning: 0 = cell coordinates as three integers (kBricksRead)
-		S.probe_mask = 0u;
-		if (probe_env >= 1 && probe_env <= 4 && p2)
-		{
-			if (probe_env == 1) launch_walks<kProbeNone, false>(S, wgs, job_blocks, stream);
-			else if (probe_env == 2) launch_walks<kProbeSame, false>(S, wgs, job_blocks, stream);
-			else if (probe_env == 3) launch_walks<kProbeSmall, false>(S, wgs, job_blocks, stream);
-			else launch_walks<kProbeFull, false>(S, wgs, job_blocks, stream);
-		}
-		else if (form2 && packed_env && P.G <= 1024u && (unsigned long long)S.chunks * per < (1ull << 28)) { if (check) launch_walks2<kBricksPacked, true>(S, wgs2, job_blocks, stream); else launch_walks2<kBricksPacked, false>(S, wgs2, job_blocks, stream); }
-		else if (form2 && !p2) { if (check) launch_walks2<kBricksReadAny, true>(S, wgs2, job_blocks, stream); else launch_walks2<kBricksReadAny, false>(S, wgs2, job_blocks, stream); }
-		else if (form2) { if (check) launch_walks2<kBricksRead, true>(S, wgs2, job_blocks, stream); else launch_walks2<kBricksRead, false>(S, wgs2, job_blocks, stream); }
-		else if (!p2) { if (check) launch_walks<kBricksReadAny, true>(S, wgs, job_blocks, stream); else launch_walks<kBricksReadAny, false>(S, wgs, job_blocks, stream); }
-		else if (bricks_env == 3) { if (check) launch_walks<kBricks, true, true>(S, wgs, job_blocks, stream); else launch_walks<kBricks, false, true>(S, wgs, job_blocks, stream); }
-		else if (bricks_env == 2) { if (check) launch_walks<kBricks, true>(S, wgs, job_blocks, stream); else launch_walks<kBricks, false>(S, wgs, job_blocks, stream); }
-		else if (check) launch_walks<kBricksRead, true>(S, wgs, job_blocks, stream);
-		else launch_walks<kBricksRead, false>(S, wgs, job_blocks, stream);
+		hipError_t eb = launch_brick_volume(P.cells, bricks, P.G, stream); // one pass over the state (~10 us at 512^3, 0.66 ms at 2048^3)
+		if (eb != hipSuccess) return eb;
+		if (bricks_built) *bricks_built = true;
 	}
-	else if (p2) { if (check) launch_walks<kRowsP2, true>(S, wgs, job_blocks, stream); else launch_walks<kRowsP2, false>(S, wgs, job_blocks, stream); }
-	else { if (check) launch_walks<kRowsAny, true>(S, wgs, job_blocks, stream); else launch_walks<kRowsAny, false>(S, wgs, job_blocks, stream); }
+	static const int pop_env = getenv("CA3D_STREAM_POP") ? atoi(getenv("CA3D_STREAM_POP")) : 0;
+	S.pop_at = pop_env >= 1 && pop_env <= 64 ? pop_env : 16;
+	static const int tb_env = getenv("CA3D_STREAM_TAIL_BATCH") ? atoi(getenv("CA3D_STREAM_TAIL_BATCH")) : 1;
+	S.tail_batch = tb_env == 2 ? 2 : (tb_env ? 1 : 0); // (2, tuning: the batched loop from the first cell on)
+	// A persistent walk launch asks for the wave slots of the whole chip — unless other frames are in flight beside this one (ca3d_api.cpp,
+	// FrameLane): then for its share of them, so that the frames' walks run side by side from their first workgroup on instead of one
+	// launch filling the chip and the next one seeping into its tail (tools/sweep_stream_wgs.sh; CA3D_STREAM_WGS_PCT overrides: tuning).
+	static const int wgs_env = getenv("CA3D_STREAM_WGS_PCT") ? atoi(getenv("CA3D_STREAM_WGS_PCT")) : 0;
+	const u32 pct = (u32)(wgs_env >= 10 && wgs_env <= 100 ? wgs_env : (walk_share_pct >= 10 && walk_share_pct <= 100 ? walk_share_pct : 100));
+	const u32 wgs2 = max(8u, min(S.chunks, (u32)cus * (u32)kW2PerSimd * 4u / (u32)kW2Waves * pct / 100u));
+	// scattered sparse volumes through the stream passes as well (ca_stream_walk2<.., SKIP>, which reads the bricks; CA3D_STREAM_SKIP=0:
+	// render.hip's scheduled kernel, tuning / A-B). Without bricks they stay with render.hip's kernels.
+	static const int skip_env = getenv("CA3D_STREAM_SKIP") ? atoi(getenv("CA3D_STREAM_SKIP")) : 1;
+	S.skip_ok = bricked && skip_env && P.occ ? 1u : 0u;
+	if (sparse_too) *sparse_too = S.skip_ok != 0u;
+	// where the walks read the volume: packed cell positions in the bricks (G <= 1024, job ids below 2^28; CA3D_STREAM_PACKED=0, tuning:
+	// cell coordinates as three integers), the bricks, or the row-major state
+	static const int packed_env = getenv("CA3D_STREAM_PACKED") ? atoi(getenv("CA3D_STREAM_PACKED")) : 1;
+	const bool packed = bricked && packed_env && P.G <= 1024u && (unsigned long long)S.chunks * per < (1ull << 28);
+	void (*walks)(const StreamParams &, u32, u32, hipStream_t);
+	if (packed) walks = check ? launch_walks2<kBricksPacked, true> : launch_walks2<kBricksPacked, false>;
+	else if (bricked && p2) walks = check ? launch_walks2<kBricksRead, true> : launch_walks2<kBricksRead, false>;
+	else if (bricked) walks = check ? launch_walks2<kBricksReadAny, true> : launch_walks2<kBricksReadAny, false>;
+	else if (p2) walks = check ? launch_walks2<kRowsP2, true> : launch_walks2<kRowsP2, false>;
+	else walks = check ? launch_walks2<kRowsAny, true> : launch_walks2<kRowsAny, false>;
+	walks(S, wgs2, job_blocks, stream);
+	const unsigned long long trace_waves = (unsigned long long)wgs2 * (unsigned)kW2Waves;
 	if (before_resolve) // (two frames in flight: the frame before this one must have written the shared presentation surface first)
 	{
 		hipError_t ew = hipStreamWaitEvent(stream, before_resolve, 0);

@@ -401,7 +401,8 @@ int ca3d_get_render_pipeline(ca3d_t *h, int32_t *frames_in_flight);
  * literal frame is never pipelined; ca3d_get_render_pipeline reports the depth in use; the first pipelined frame of an engine probes
  * the runtime's streams for separate hardware queues (a few milliseconds per pair, once);
  * "render_frame_bricks" 0/1 the literal frame as a batched march over the bricked volume (on by default; 0: the statement-by-
- * statement form, the same frame bit for bit); "rows" 0/1 the run-time compiled rows kernel on grids that are not a power of two (on by
+ * statement form, the same frame bit for bit); it also decides whether the converged frame's ray-stream walks read the bricked
+ * copy or the row-major state (grids up to 2048; above, always the state) — the same pixels either way; "rows" 0/1 the run-time compiled rows kernel on grids that are not a power of two (on by
  * default; 0: the kernels that served them before — tests, tuning). */
 int ca3d_set_option(ca3d_t *h, const char *name, int64_t value);
 

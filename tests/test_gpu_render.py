@@ -87,7 +87,38 @@ def test_grids_that_are_not_a_power_of_two(eng, G, W, H, spp):
     assert eng.info().grid_size == G
 
 
-@pytest.mark.parametrize("G,steps", [(96, 12), (160, 30), (288, 40)])
+@pytest.mark.parametrize("rounds", [4, 12])
+@pytest.mark.parametrize("G,W,H,spp", [(64, 320, 180, 4), (96, 320, 180, 1), (160, 320, 180, 4)])
+def test_stream_passes_over_the_row_major_volume(eng, G, W, H, spp, rounds):
+    """render_frame_bricks 0: the stream passes walk the row-major state instead of the bricked copy (the only volume they have on grids
+    above 2048) — on power-of-two grids and others, dense and scattered sparse, with and without the filter checked against the slab
+    test: bit for bit the plain kernel's frame, cell-visit counts included."""
+    cells = host.random_fill(host.words_per_buffer(G), seed=29 + G, and_rounds=rounds)
+    u = host.uniform_block(W, H, host.orbit_camera())
+    eng.configure(G)
+    set_rules(eng, rules("default"))
+    eng.upload_state(cells)
+    eng.set_option("render_sched", 0)
+    pres0, light0, depth0 = eng.render(u, W, H, spp)
+    st0 = eng.render_stats()
+    try:
+        eng.set_option("render_sched", 1)
+        eng.set_option("render_stream", 1)
+        eng.set_option("render_frame_bricks", 0)
+        for check in (1, 0):
+            eng.set_option("render_stream_check", check)
+            pres, light, depth = eng.render(u, W, H, spp)
+            st1 = eng.render_stats()
+            np.testing.assert_array_equal(pres, pres0)
+            np.testing.assert_array_equal(light.view(np.uint16), light0.view(np.uint16))
+            np.testing.assert_array_equal(depth.view(np.uint16), depth0.view(np.uint16))
+            assert (st0.shadow_rays, st0.primary_cell_visits, st0.shadow_cell_visits) == (st1.shadow_rays, st1.primary_cell_visits, st1.shadow_cell_visits)
+    finally:
+        eng.set_option("render_frame_bricks", 1)
+        eng.set_option("render_stream_check", 0)
+
+
+@pytest.mark.parametrize("G,steps",[(96, 12), (160, 30), (288, 40)])
 def test_sparse_scenes_on_grids_that_are_not_a_power_of_two(eng, G, steps):
     """The UI's start-up seed a few steps on, on grids that are not a power of two: the sparse-volume kernels (occupancy bits over 32 x 8 x 8
     blocks, the box of the live blocks, block jumps, the spread kernel; no second occupancy level off multiples of 128) against the
