@@ -47,6 +47,17 @@ class RenderStats(C.Structure):
     ]
 
 
+class SummaryStruct(C.Structure):
+    """ca3d_summary (include/ca3d.h)."""
+    _fields_ = [
+        ("step", C.c_uint64), ("population", C.c_uint64), ("births", C.c_uint64), ("deaths", C.c_uint64), ("digest", C.c_uint64),
+        ("has_previous", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3),
+    ]
+
+
+STOP_EXTINCT, STOP_STILL = 1, 2
+
+
 class CommInfo(C.Structure):
     _fields_ = [("device", C.c_int32), ("comm_ranks", C.c_int32), ("comm_rank", C.c_int32), ("comm_device", C.c_int32),
                 ("pci_bus_id", C.c_char * 32)]
@@ -108,6 +119,10 @@ SYMBOLS = [
     ("ca3d_group_synchronize", C.c_int, [_H]),
     ("ca3d_group_set_option", C.c_int, [_H, C.c_char_p, C.c_int64]),
     ("ca3d_group_render", C.c_int, [_H, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ca3d_group_summarize", C.c_int, [_H, C.POINTER(SummaryStruct), _u32p]),
+    ("ca3d_summarize", C.c_int, [_H, C.POINTER(SummaryStruct), _u32p]),
+    ("ca3d_get_summary_time", C.c_int, [_H, C.POINTER(C.c_double)]),
+    ("ca3d_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct), _u32p, _u32p]),
     ("ca3d_render_target", C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     ("ca3d_synchronize", C.c_int, [_H]),
     ("ca3d_recovered_launches", C.c_int, [_H, C.POINTER(C.c_uint32)]),

@@ -197,6 +197,15 @@ struct ca3d_engine
 	ca3d_stats stats{};
 	const char *kernel_name = "";
 
+	// ca3d_summarize: result block on the device (ca_summary.hip), its pinned host copy, the event pair around clear + kernel
+	uint32_t *sum_dev = nullptr, *sum_host = nullptr;
+	size_t sum_words = 0;
+	hipEvent_t sum_ev0 = nullptr, sum_ev1 = nullptr;
+	bool sum_ev_valid = false;
+	// the owned planes of buffer [(step + 1) % 2] hold the state one step earlier: set by the step paths that guarantee it, cleared by
+	// everything that writes a buffer any other way (upload, buffers handed out, gathers, the resident slab launch)
+	bool prev_ok = false;
+
 	// renderer targets: presentation + two history pairs (light RGBA16F, depth RG16F), swapped per frame
 	uint32_t rw = 0, rh = 0;
 	uint32_t *r_present = nullptr;
@@ -321,6 +330,12 @@ void free_buffers(ca3d_engine *h)
 	h->cur = 0;
 	h->pending_edges = 0; // an edge phase belongs to the state that has just gone
 	h->ghosts_valid = false;
+	h->prev_ok = false;
+	if (h->sum_dev) hipFree(h->sum_dev);
+	if (h->sum_host) hipHostFree(h->sum_host);
+	h->sum_dev = h->sum_host = nullptr;
+	h->sum_words = 0;
+	h->sum_ev_valid = false;
 }
 
 // the engine's stream waits for the frames in flight on the lanes (nothing is waited for on the host)
@@ -1050,6 +1065,8 @@ int ca3d_destroy(ca3d_t *h) CA3D_API_TRY
 	if (h->rev_stop) hipEventDestroy(h->rev_stop);
 	if (h->ev_start) hipEventDestroy(h->ev_start);
 	if (h->ev_stop) hipEventDestroy(h->ev_stop);
+	if (h->sum_ev0) hipEventDestroy(h->sum_ev0);
+	if (h->sum_ev1) hipEventDestroy(h->sum_ev1);
 	if (h->own_stream) hipStreamDestroy(h->own_stream);
 	delete h;
 	return CA3D_OK;
@@ -1154,6 +1171,7 @@ int ca3d_upload_state(ca3d_t *h, const uint32_t *words, size_t n_words) CA3D_API
 	HIP_TRY(hipStreamSynchronize(h->stream));
 	h->step = 0;
 	h->cur = 0;
+	h->prev_ok = false;
 	h->state_serial++;
 	h->buffers_exposed = false;
 	h->pending_edges = 0; // a restart between the two phases of a batch abandons the batch
@@ -1250,6 +1268,7 @@ static int submit_steps(ca3d_engine *h, uint32_t n_steps)
 		h->cur = (h->cur + n) & 1u;
 		left -= n;
 	}
+	h->prev_ok = true; // every full-grid path leaves the state one step earlier in the other buffer (include/ca3d.h, ca3d_step)
 	if (h->want_stats) HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
 	h->ev_valid = h->want_stats != 0;
 	h->stats.steps = n_steps;
@@ -1381,6 +1400,10 @@ int slab_batch(ca3d_engine *h, uint32_t n_steps, int phase)
 	h->pending_edges = 0;
 	h->step += n;
 	h->cur = (h->cur + n) & 1u;
+	// Sub-step n - 1 of the per-step kernels wrote planes [n - 1, L - n + 1) of the other buffer (n == 1: it is the batch's input), which
+	// cover the owned planes [K, K + nz) because n <= K: they hold the state one step earlier. The resident slab launch writes its final
+	// state only (for an even n into the buffer it read from): nothing is known about the other buffer then.
+	h->prev_ok = !resident;
 	h->ghosts_valid = false; // the caller (or ca3d_slab_run) refreshes them
 	if (h->want_stats) HIP_TRY(hipEventRecord(h->ev_stop, h->stream));
 	h->ev_valid = h->want_stats != 0;
@@ -1595,6 +1618,7 @@ int ca3d_slab_gather(ca3d_t *h, ca3d_t *full) CA3D_API_TRY
 	}
 	full->has_state = true;
 	full->state_serial++;
+	full->prev_ok = false; // only the current buffer was written
 	return CA3D_OK;
 }
 CA3D_API_CATCH
@@ -1657,6 +1681,135 @@ int ca3d_measure_copy(ca3d_t *h, size_t n_bytes, uint32_t reps, double *gb_per_s
 }
 CA3D_API_CATCH
 
+} // extern "C"
+
+// The summary of the current state onto the engine's stream and back: clear of the result block, ONE kernel (ca_summary.hip), one
+// small copy into pinned memory, one wait. The entry guard is ca3d_read_state's.
+static int summarize_state(ca3d_engine *h, ca3d_summary *out, uint32_t *plane_population)
+{
+	if (!h) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL engine handle");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	if (!h->configured || !h->has_state) return fail(CA3D_ERR_NOT_CONFIGURED, "no state to summarise: configure and upload first");
+	// the edge phase of a slab batch ping-pongs its zones through BOTH buffers: until the interior phase commits the batch neither holds a state
+	if (h->pending_edges) return fail(CA3D_ERR_INVALID_ARGUMENT, "an edge phase is pending: finish it with the interior phase");
+	FLUSH_QUEUED(h);
+	int rc = bind_device(h);
+	if (rc) return rc;
+	rc = settle_resident(h); // a resident launch that gave up is recovered from before the state is looked at
+	if (rc) return rc;
+	const size_t words = kSummaryHeaderWords + (size_t)h->nz;
+	if (h->sum_words < words)
+	{
+		HIP_TRY(hipStreamSynchronize(h->stream));
+		if (h->sum_dev) hipFree(h->sum_dev);
+		if (h->sum_host) hipHostFree(h->sum_host);
+		h->sum_dev = h->sum_host = nullptr;
+		h->sum_words = 0;
+		HIP_TRY(hipMalloc((void **)&h->sum_dev, words * sizeof(uint32_t)));
+		HIP_TRY(hipHostMalloc((void **)&h->sum_host, words * sizeof(uint32_t), hipHostMallocDefault));
+		h->sum_words = words;
+	}
+	if (h->want_stats && !h->sum_ev0)
+	{
+		HIP_TRY(hipEventCreate(&h->sum_ev0));
+		HIP_TRY(hipEventCreate(&h->sum_ev1));
+	}
+	const bool has_prev = h->step >= 1 && h->prev_ok;
+	const size_t off = h->slab ? (size_t)h->ghost * h->plane_words : 0;
+	SummaryLaunch l;
+	l.cur = h->buf[h->cur] + off;
+	l.prev = has_prev ? h->buf[h->cur ^ 1u] + off : nullptr;
+	l.result = h->sum_dev;
+	l.G = h->G;
+	l.layout = h->layout;
+	l.z0 = h->z0;
+	l.nz = h->nz;
+	h->sum_ev_valid = false;
+	if (h->want_stats) HIP_TRY(hipEventRecord(h->sum_ev0, h->stream));
+	HIP_TRY(hipMemsetAsync(h->sum_dev, 0, words * sizeof(uint32_t), h->stream));
+	hipError_t e = launch_summary(l, h->stream);
+	if (e != hipSuccess) return fail(CA3D_ERR_DEVICE, "summary kernel launch failed: %s", hipGetErrorString(e));
+	if (h->want_stats) HIP_TRY(hipEventRecord(h->sum_ev1, h->stream));
+	HIP_TRY(hipMemcpyAsync(h->sum_host, h->sum_dev, (plane_population ? words : (size_t)kSummaryHeaderWords) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(hipStreamSynchronize(h->stream));
+	h->sum_ev_valid = h->want_stats != 0;
+	const uint32_t *r = h->sum_host;
+	uint64_t r64[4];
+	memcpy(r64, r, sizeof r64);
+	memset(out, 0, sizeof *out);
+	out->step = h->step;
+	out->population = r64[0];
+	out->births = has_prev ? r64[1] : 0;
+	out->deaths = has_prev ? r64[2] : 0;
+	out->digest = r64[3];
+	out->has_previous = has_prev ? 1u : 0u;
+	for (int i = 0; i < 3; i++)
+	{
+		out->box_min[i] = r64[0] ? ~r[8 + i] : h->G;
+		out->box_max[i] = r64[0] ? r[11 + i] : 0u;
+	}
+	if (plane_population) memcpy(plane_population, r + kSummaryHeaderWords, (size_t)h->nz * sizeof(uint32_t));
+	return CA3D_OK;
+}
+
+extern "C"
+{
+
+int ca3d_summarize(ca3d_t *h, ca3d_summary *out, uint32_t *plane_population) CA3D_API_TRY
+{
+	return summarize_state(h, out, plane_population);
+}
+CA3D_API_CATCH
+
+int ca3d_get_summary_time(ca3d_t *h, double *gpu_ms) CA3D_API_TRY
+{
+	if (!h || !gpu_ms) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	*gpu_ms = 0.0;
+	if (!h->sum_ev_valid) return CA3D_OK;
+	int rc = bind_device(h);
+	if (rc) return rc;
+	float ms = 0.f;
+	HIP_TRY(hipEventElapsedTime(&ms, h->sum_ev0, h->sum_ev1));
+	*gpu_ms = ms;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, ca3d_summary *out, uint32_t *steps_done,
+                    uint32_t *reason) CA3D_API_TRY
+{
+	if (steps_done) *steps_done = 0;
+	if (reason) *reason = 0;
+	if (!h) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL engine handle");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	if (check_every == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "check_every must be at least 1");
+	if (stop_mask & ~(uint32_t)(CA3D_STOP_EXTINCT | CA3D_STOP_STILL)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in stop_mask %#x", stop_mask);
+	if (h->configured && h->slab) return fail(CA3D_ERR_UNSUPPORTED, "ca3d_step_until takes a full-grid engine: a slab's neighbours must step with it");
+	int rc = check_ready(h);
+	if (rc) return rc;
+	uint32_t done = 0;
+	for (;;)
+	{
+		rc = summarize_state(h, out, nullptr);
+		if (rc) return rc;
+		uint32_t fired = 0;
+		if (out->population == 0) fired |= CA3D_STOP_EXTINCT;
+		if (out->has_previous && out->births + out->deaths == 0) fired |= CA3D_STOP_STILL;
+		fired &= stop_mask;
+		if (fired || done == max_steps)
+		{
+			if (steps_done) *steps_done = done;
+			if (reason) *reason = fired;
+			return CA3D_OK;
+		}
+		const uint32_t n = max_steps - done < check_every ? max_steps - done : check_every;
+		rc = ca3d_step(h, n); // the very path of a caller's ca3d_step(n): queue, resident kernels, captured graphs
+		if (rc) return rc;
+		done += n;
+	}
+}
+CA3D_API_CATCH
+
 int ca3d_recovered_launches(ca3d_t *h, uint32_t *out_count) CA3D_API_TRY
 {
 	if (!h || !out_count) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1712,6 +1865,7 @@ int ca3d_device_buffer(ca3d_t *h, int which, void **device_ptr, size_t *n_bytes)
 	if (int rcs = settle_resident(h)) return rcs;
 	*device_ptr = h->buf[which];
 	*n_bytes = h->buffer_words() * sizeof(uint32_t);
+	h->prev_ok = false; // (... nor does ca3d_summarize compare buffers the caller may have written: has_previous stays 0 until the next step)
 	h->state_serial++; // the caller may write through the pointer: what the renderer derived from the state is stale from here on,
 	h->buffers_exposed = true; // and again before every frame while the pointer is valid (ca3d_render)
 	return CA3D_OK;
@@ -2379,6 +2533,7 @@ int engine_mark_state(ca3d_engine *h)
 	HIP_TRY(hipMemsetAsync(h->buf[1], 0, h->buffer_words() * sizeof(uint32_t), h->stream));
 	h->step = 0;
 	h->cur = 0;
+	h->prev_ok = false;
 	h->has_state = true;
 	h->binary_state = true;
 	h->state_serial++;

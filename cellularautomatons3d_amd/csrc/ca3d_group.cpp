@@ -348,6 +348,42 @@ int ca3d_group_set_option(ca3d_group_t *g, const char *name, int64_t value) CA3D
 }
 CA3D_API_CATCH
 
+// ca3d_summarize of the whole grid: every rank summarises its owned planes on its own device; sums, box union and the concatenation of
+// the plane counts happen here (the digest is keyed by the word's index in the full grid, so the slabs' digests simply add up).
+int ca3d_group_summarize(ca3d_group_t *g, ca3d_summary *out, uint32_t *plane_population) CA3D_API_TRY
+{
+	G_TRY(check_group(g, false));
+	if (!g->has_state) return set_error(CA3D_ERR_NOT_CONFIGURED, "no state to summarise: upload first");
+	if (!out) return set_error(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	G_TRY(ca3d_group_synchronize(g));
+	const uint32_t n = (uint32_t)P(g), nz = g->G / n;
+	ca3d_summary t;
+	memset(&t, 0, sizeof t);
+	t.step = g->step;
+	t.has_previous = 1;
+	for (int i = 0; i < 3; i++) { t.box_min[i] = g->G; t.box_max[i] = 0; }
+	for (uint32_t k = 0; k < n; k++)
+	{
+		ca3d_summary s;
+		G_TRY(ca3d_summarize(g->eng[k], &s, plane_population ? plane_population + (size_t)k * nz : nullptr));
+		t.population += s.population;
+		t.births += s.births;
+		t.deaths += s.deaths;
+		t.digest += s.digest;
+		t.has_previous &= s.has_previous;
+		if (s.population)
+			for (int i = 0; i < 3; i++)
+			{
+				if (s.box_min[i] < t.box_min[i]) t.box_min[i] = s.box_min[i];
+				if (s.box_max[i] > t.box_max[i]) t.box_max[i] = s.box_max[i];
+			}
+	}
+	if (!t.has_previous) t.births = t.deaths = 0;
+	*out = t;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
 // The frame of the whole grid, shared between the GPUs: shadow rays cross slabs, so every rank gets the full
 // packed volume (peer copies of every slab's owned planes into a full-grid engine per rank), renders its band of image rows
 // ("replicas over pixels") and the bands land in the caller's buffers. A band is bit-identical to the same rows of a

@@ -181,6 +181,20 @@ struct RenderLaunch
 	bool stream_check = false; // diagnostics: every live-cell decision of the interval filter is checked against the slab test and contradictions counted
 };
 
+// ca_summary.hip: one pass over the owned planes of the current buffer (and of `prev`, the same planes of the buffer that holds the
+// state one step earlier, or null) into a zeroed result block of kSummaryHeaderWords + nz words:
+//   u64 [0] population, [1] births, [2] deaths, [3] digest; u32 [8..10] ~box_min x y z (complemented: zero means "none yet"),
+//   [11..13] box_max, [14..15] unused, [16 + k] live cells of owned plane k
+constexpr uint32_t kSummaryHeaderWords = 16;
+struct SummaryLaunch
+{
+	const uint32_t *cur, *prev; // first OWNED plane of each buffer
+	uint32_t *result;
+	uint32_t G;
+	int layout;
+	uint32_t z0, nz; // owned planes [z0, z0 + nz) of the grid
+};
+hipError_t launch_summary(const SummaryLaunch &l, hipStream_t stream);
 // ca_diag.hip: float4 device-to-device copy (measurement only)
 hipError_t launch_copy_f4(const void *in, void *out, size_t bytes, hipStream_t stream);
 // ca_diag.hip: do two (idle) streams run side by side, i.e. sit on different hardware queues? (probe: ~2 ms)

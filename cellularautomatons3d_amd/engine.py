@@ -6,7 +6,8 @@ Method names follow the reference's host methods: `restart_sim` (_restartSim, 62
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -23,6 +24,28 @@ def _as_u32(a) -> np.ndarray:
 
 def _as_i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+@dataclass
+class Summary:
+    """`ca3d_summary` (include/ca3d.h): what the device says about the current state."""
+    step: int
+    population: int
+    births: int
+    deaths: int
+    digest: int
+    has_previous: bool
+    box_min: Tuple[int, int, int]
+    box_max: Tuple[int, int, int]
+    plane_population: Optional[np.ndarray] = None  # u32 per owned z plane, when asked for
+
+
+def _summary(s: "_capi.SummaryStruct", planes: Optional[np.ndarray]) -> Summary:
+    return Summary(int(s.step), int(s.population), int(s.births), int(s.deaths), int(s.digest), bool(s.has_previous),
+                   tuple(int(v) for v in s.box_min), tuple(int(v) for v in s.box_max), planes)
+
+
+STOP_EXTINCT, STOP_STILL = _capi.STOP_EXTINCT, _capi.STOP_STILL
 
 
 class Engine:
@@ -122,6 +145,29 @@ class Engine:
         `set_option("queue", n)` and a caller that records its own events on the stream — every other call on the engine
         submits first by itself."""
         _capi.check(self._lib.ca3d_flush(self._h))
+
+    def summary(self, planes: bool = False) -> Summary:
+        """`ca3d_summarize`: population, births / deaths against the state one step earlier, bounding box and digest of the current
+        state, computed on the device (one pass, a few dozen bytes come back); `planes`: the live cells per owned z plane too."""
+        st = _capi.SummaryStruct()
+        pp = np.empty(self.info().nz, dtype=np.uint32) if planes else None
+        _capi.check(self._lib.ca3d_summarize(self._h, C.byref(st), pp.ctypes.data_as(_u32p) if planes else None))
+        return _summary(st, pp)
+
+    def summary_gpu_ms(self) -> float:
+        """hipEvent time of the last `summary()`'s clear + kernel (measurement; 0.0 with option "stats" off)."""
+        v = C.c_double()
+        _capi.check(self._lib.ca3d_get_summary_time(self._h, C.byref(v)))
+        return float(v.value)
+
+    def step_until(self, max_steps: int, check_every: int = 8, extinct: bool = True, still: bool = True):
+        """`ca3d_step_until`: step in batches of `check_every` until the grid is empty (`extinct`) or a fixed point (`still`), at
+        most `max_steps` steps. -> (steps_done, reason, Summary); reason: STOP_EXTINCT | STOP_STILL bits, 0 = max_steps reached."""
+        st = _capi.SummaryStruct()
+        done, reason = C.c_uint32(), C.c_uint32()
+        mask = (STOP_EXTINCT if extinct else 0) | (STOP_STILL if still else 0)
+        _capi.check(self._lib.ca3d_step_until(self._h, max_steps, check_every, mask, C.byref(st), C.byref(done), C.byref(reason)))
+        return int(done.value), int(reason.value), _summary(st, None)
 
     def slab_step(self, n_steps: int) -> None:
         _capi.check(self._lib.ca3d_slab_step(self._h, n_steps))
@@ -333,6 +379,13 @@ class EngineGroup:
 
     def synchronize(self) -> None:
         _capi.check(self._lib.ca3d_group_synchronize(self._h))
+
+    def summary(self, planes: bool = False) -> Summary:
+        """`ca3d_group_summarize`: every rank summarises its slab on its own device, combined on the host."""
+        st = _capi.SummaryStruct()
+        pp = np.empty(self.grid_size, dtype=np.uint32) if planes else None
+        _capi.check(self._lib.ca3d_group_summarize(self._h, C.byref(st), pp.ctypes.data_as(_u32p) if planes else None))
+        return _summary(st, pp)
 
     def set_option(self, name: str, value: int) -> None:
         _capi.check(self._lib.ca3d_group_set_option(self._h, name.encode(), int(value)))

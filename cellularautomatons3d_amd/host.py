@@ -214,6 +214,104 @@ def get_cell(grid_size: int, words: np.ndarray, x: int, y: int, z: int) -> int:
     return int((int(words[get_cluster_idx_from_grid_coordinates(grid_size, x, y, z)]) >> (x % 32)) & 1)
 
 
+# ------------------------------------------------------------------------------------------- state summary
+# The definition of ca3d_summarize (include/ca3d.h) in executable form: what the device kernel (csrc/ca_summary.hip) must return,
+# usable on checkpoint files and read-back states. No reference counterpart.
+
+_M64 = (1 << 64) - 1
+
+
+def digest_mix(index: int, word: int) -> int:
+    """splitmix64 finaliser of key = (index << 32 | word) modulo 2^64: one term of the state digest (plain Python integers)."""
+    z = ((((index << 32) & _M64) | word) + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _popcount32(w: np.ndarray) -> np.ndarray:
+    """Set bits per u32 word."""
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(w).astype(np.uint32)
+    w = w - ((w >> np.uint32(1)) & np.uint32(0x55555555))
+    w = (w & np.uint32(0x33333333)) + ((w >> np.uint32(2)) & np.uint32(0x33333333))
+    w = (w + (w >> np.uint32(4))) & np.uint32(0x0F0F0F0F)
+    return (w * np.uint32(0x01010101)) >> np.uint32(24)
+
+
+def _digest(words: np.ndarray, base_index: int) -> int:
+    total = 0
+    chunk = 1 << 22
+    with np.errstate(over="ignore"):
+        for lo in range(0, words.size, chunk):
+            w = words[lo:lo + chunk]
+            nz = np.flatnonzero(w)
+            if nz.size == 0:
+                continue
+            z = ((nz.astype(np.uint64) + np.uint64(base_index + lo)) << np.uint64(32)) | w[nz].astype(np.uint64)
+            z = z + np.uint64(0x9E3779B97F4A7C15)
+            z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+            z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+            z = z ^ (z >> np.uint64(31))
+            total = (total + int(np.add.reduce(z, dtype=np.uint64))) & _M64
+    return total
+
+
+def state_summary(grid_size: int, words, prev_words=None, layout: int = 0, z0: int = 0) -> dict:
+    """The numbers of `ca3d_summarize` for the state `words` (layout 0: PACKED32, 1: UNPACKED) — the whole grid, or the planes
+    [z0, z0 + nz) of it when fewer words are given (a slab's owned planes). `prev_words`: the same planes one step earlier (None:
+    has_previous False, births = deaths = 0). Box coordinates are global; the digest is keyed by the word's index in the FULL grid,
+    so the digests of the slabs of a grid add up (modulo 2^64) to the digest of the grid.
+
+    -> dict(population, births, deaths, digest, has_previous, box_min (x, y, z), box_max, plane_population u32[nz])."""
+    G = int(grid_size)
+    w = np.ascontiguousarray(words, dtype=np.uint32).ravel()
+    cols = G // 32 if layout == 0 else G
+    if layout == 0:
+        _check_grid(G)
+    plane_words = cols * G
+    if w.size == 0 or w.size % plane_words:
+        raise ValueError("the state must hold whole z planes")
+    nz = w.size // plane_words
+    if z0 < 0 or z0 + nz > G:
+        raise ValueError("planes outside the grid")
+    alive = _popcount32(w) if layout == 0 else (w == 1).astype(np.uint32)  # unpacked: alive iff the word == 1 (the legacy kernel's `st == 1u`)
+    out = {"has_previous": prev_words is not None, "births": 0, "deaths": 0}
+    if prev_words is not None:
+        q = np.ascontiguousarray(prev_words, dtype=np.uint32).ravel()
+        if q.size != w.size:
+            raise ValueError("prev_words must hold the same planes")
+        if layout == 0:
+            out["births"] = int(_popcount32(w & ~q).sum(dtype=np.uint64))
+            out["deaths"] = int(_popcount32(q & ~w).sum(dtype=np.uint64))
+        else:
+            was = q == 1
+            out["births"] = int(np.count_nonzero((w == 1) & ~was))
+            out["deaths"] = int(np.count_nonzero(was & (w != 1)))
+    a3 = alive.reshape(nz, G, cols)
+    planes = a3.sum(axis=(1, 2), dtype=np.uint64)
+    out["plane_population"] = planes.astype(np.uint32)
+    out["population"] = int(planes.sum(dtype=np.uint64))
+    out["digest"] = _digest(w, z0 * plane_words)
+    if out["population"] == 0:
+        out["box_min"], out["box_max"] = (G, G, G), (0, 0, 0)
+        return out
+    zs = np.flatnonzero(planes)
+    ys = np.flatnonzero(a3.any(axis=(0, 2)))
+    xcols = np.flatnonzero(a3.any(axis=(0, 1)))
+    if layout == 0:
+        w3 = w.reshape(nz, G, cols)
+        lo = int(np.bitwise_or.reduce(w3[:, :, xcols[0]], axis=None))
+        hi = int(np.bitwise_or.reduce(w3[:, :, xcols[-1]], axis=None))
+        x0 = int(xcols[0]) * 32 + ((lo & -lo).bit_length() - 1)
+        x1 = int(xcols[-1]) * 32 + hi.bit_length() - 1
+    else:
+        x0, x1 = int(xcols[0]), int(xcols[-1])
+    out["box_min"] = (x0, int(ys[0]), z0 + int(zs[0]))
+    out["box_max"] = (x1, int(ys[-1]), z0 + int(zs[-1]))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

@@ -468,6 +468,58 @@ static napi_value js_slab_gather(napi_env env, napi_callback_info info)
 	return rc ? throw_ca3d(env, rc) : undefined(env);
 }
 
+/* ca3d_summary as a JS object. uint64 fields: `digest` uses all 64 bits and crosses as a BigInt; step, population, births and
+ * deaths stay below 2^53 on every grid the engine accepts (8192^3 = 2^39 cells) and cross as Numbers. */
+static napi_value summary_object(napi_env env, const ca3d_summary *s, napi_value planes)
+{
+	napi_value o, v, lo, hi;
+	napi_create_object(env, &o);
+	set_num(env, o, "step", (double)s->step);
+	set_num(env, o, "population", (double)s->population);
+	set_num(env, o, "births", (double)s->births);
+	set_num(env, o, "deaths", (double)s->deaths);
+	napi_create_bigint_uint64(env, s->digest, &v);
+	napi_set_named_property(env, o, "digest", v);
+	napi_get_boolean(env, s->has_previous != 0, &v);
+	napi_set_named_property(env, o, "hasPrevious", v);
+	napi_create_array_with_length(env, 3, &lo);
+	napi_create_array_with_length(env, 3, &hi);
+	for (uint32_t i = 0; i < 3; i++)
+	{
+		napi_create_uint32(env, s->box_min[i], &v);
+		napi_set_element(env, lo, i, v);
+		napi_create_uint32(env, s->box_max[i], &v);
+		napi_set_element(env, hi, i, v);
+	}
+	napi_set_named_property(env, o, "boxMin", lo);
+	napi_set_named_property(env, o, "boxMax", hi);
+	if (planes) napi_set_named_property(env, o, "planePopulation", planes);
+	return o;
+}
+
+/* summary(handle, Uint32Array(nz) | null) */
+static napi_value js_summary(napi_env env, napi_callback_info info)
+{
+	napi_value argv[2];
+	if (!get_args(env, info, 2, argv)) return NULL;
+	ca3d_t *h = get_handle(env, argv[0]);
+	void *pp;
+	size_t n;
+	if (!h || !get_typed(env, argv[1], napi_uint32_array, 1, &pp, &n)) return NULL;
+	ca3d_info i;
+	int rc = ca3d_get_info(h, &i);
+	if (rc) return throw_ca3d(env, rc);
+	if (pp && n != i.nz)
+	{
+		napi_throw_range_error(env, NULL, "planePopulation must hold one entry per owned plane (info().nz)");
+		return NULL;
+	}
+	ca3d_summary s;
+	rc = ca3d_summarize(h, &s, (uint32_t *)pp);
+	if (rc) return throw_ca3d(env, rc);
+	return summary_object(env, &s, pp ? argv[1] : NULL);
+}
+
 /*
  * Asynchronous forms of the calls that wait for the GPU ("optional napi_async_work wrappers"): the wait
  * runs on a libuv worker thread and the call returns a Promise, so a UI thread never blocks in a read-back. The engine
@@ -478,7 +530,9 @@ typedef struct
 	napi_async_work work;
 	napi_deferred deferred;
 	ca3d_t *h;
-	int kind; /* 0 readState, 1 render, 2 synchronize */
+	int kind; /* 0 readState, 1 render, 2 synchronize, 3 stepUntil */
+	uint32_t max_steps, check_every, stop_mask, steps_done, reason;
+	ca3d_summary summary;
 	int rc;
 	char err[512];
 	uint32_t *words;
@@ -498,6 +552,7 @@ static void job_execute(napi_env env, void *data)
 	AsyncJob *j = (AsyncJob *)data;
 	if (j->kind == 0) j->rc = ca3d_read_state(j->h, j->words, j->n_words);
 	else if (j->kind == 1) j->rc = ca3d_render(j->h, j->uniforms, j->w, j->hh, j->spp, j->pres, j->light, j->depth);
+	else if (j->kind == 3) j->rc = ca3d_step_until(j->h, j->max_steps, j->check_every, j->stop_mask, &j->summary, &j->steps_done, &j->reason);
 	else j->rc = ca3d_synchronize(j->h);
 	if (j->rc) snprintf(j->err, sizeof j->err, "ca3d error %d: %s", j->rc, ca3d_last_error()); /* ca3d_last_error is per thread */
 }
@@ -508,7 +563,14 @@ static void job_complete(napi_env env, napi_status status, void *data)
 	napi_value v;
 	if (status == napi_ok && j->rc == 0)
 	{
-		napi_get_undefined(env, &v);
+		if (j->kind == 3)
+		{
+			napi_create_object(env, &v);
+			set_num(env, v, "stepsDone", j->steps_done);
+			set_num(env, v, "reason", j->reason);
+			napi_set_named_property(env, v, "summary", summary_object(env, &j->summary, NULL));
+		}
+		else napi_get_undefined(env, &v);
 		napi_resolve_deferred(env, j->deferred, v);
 	}
 	else
@@ -611,6 +673,21 @@ static napi_value js_synchronize_async(napi_env env, napi_callback_info info)
 	j->h = h; j->kind = 2;
 	job_hold_engine(env, j, argv[0]);
 	return job_start(env, j, "ca3d.synchronize");
+}
+
+/* stepUntilAsync(handle, maxSteps, checkEvery, stopMask) -> Promise<{stepsDone, reason, summary}>: many batches and a wait each */
+static napi_value js_step_until_async(napi_env env, napi_callback_info info)
+{
+	napi_value argv[4];
+	if (!get_args(env, info, 4, argv)) return NULL;
+	ca3d_t *h = get_handle(env, argv[0]);
+	uint32_t max_steps, every, mask;
+	if (!h || !get_u32(env, argv[1], &max_steps) || !get_u32(env, argv[2], &every) || !get_u32(env, argv[3], &mask)) return NULL;
+	AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
+	if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+	j->h = h; j->kind = 3; j->max_steps = max_steps; j->check_every = every; j->stop_mask = mask;
+	job_hold_engine(env, j, argv[0]);
+	return job_start(env, j, "ca3d.stepUntil");
 }
 
 /* ---- ca3d_group_*: one JS thread drives the Z-slab split over several GPUs (include/ca3d.h) ---------------------------- */
@@ -805,6 +882,31 @@ static napi_value js_group_info(napi_env env, napi_callback_info info)
 	return o;
 }
 
+/* groupSummary(group, Uint32Array(G) | null) */
+static napi_value js_group_summary(napi_env env, napi_callback_info info)
+{
+	napi_value argv[2];
+	if (!get_args(env, info, 2, argv)) return NULL;
+	ca3d_group_t *g = get_group(env, argv[0]);
+	void *pp;
+	size_t n;
+	if (!g || !get_typed(env, argv[1], napi_uint32_array, 1, &pp, &n)) return NULL;
+	ca3d_t *e = NULL;
+	ca3d_info i;
+	int rc = ca3d_group_engine(g, 0, &e);
+	if (rc == 0) rc = ca3d_get_info(e, &i);
+	if (rc) return throw_ca3d(env, rc);
+	if (pp && n != i.grid_size)
+	{
+		napi_throw_range_error(env, NULL, "planePopulation must hold one entry per plane of the grid");
+		return NULL;
+	}
+	ca3d_summary s;
+	rc = ca3d_group_summarize(g, &s, (uint32_t *)pp);
+	if (rc) return throw_ca3d(env, rc);
+	return summary_object(env, &s, pp ? argv[1] : NULL);
+}
+
 static napi_value js_group_render(napi_env env, napi_callback_info info)
 {
 	napi_value argv[8];
@@ -884,7 +986,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"groupCreate", js_group_create}, {"groupDestroy", js_group_destroy}, {"groupConfigure", js_group_configure}, {"groupSetRules", js_group_set_rules},
 	    {"groupUploadState", js_group_upload_state}, {"groupReadState", js_group_read_state}, {"groupStep", js_group_step},
 	    {"groupSynchronize", js_group_synchronize}, {"groupSetOption", js_group_set_option}, {"groupInfo", js_group_info}, {"groupRender", js_group_render},
-	    {"readStateAsync", js_read_state_async}, {"renderAsync", js_render_async}, {"synchronizeAsync", js_synchronize_async}};
+	    {"readStateAsync", js_read_state_async}, {"renderAsync", js_render_async}, {"synchronizeAsync", js_synchronize_async},
+	    {"summary", js_summary}, {"groupSummary", js_group_summary}, {"stepUntilAsync", js_step_until_async}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

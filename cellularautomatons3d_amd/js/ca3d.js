@@ -169,6 +169,8 @@ function loadAddon()
 	return addon;
 }
 
+const STOP_EXTINCT = 1, STOP_STILL = 2; // ca3d_step_until: bits of `reason`
+
 class Engine
 {
 	constructor(device)
@@ -270,6 +272,25 @@ class Engine
 	}
 	synchronizeAsync() { return this._queue(() => this._a.synchronizeAsync(this._h)); }
 
+	// ca3d_summarize (no reference counterpart): population, births / deaths against the state one step earlier, bounding box and
+	// digest of the current state, computed on the device. -> {step, population, births, deaths, digest (BigInt), hasPrevious,
+	// boxMin [x, y, z], boxMax, planePopulation? (Uint32Array, one entry per owned z plane, with {planes: true})}
+	summary(opts)
+	{
+		this._idle("summary");
+		const planes = opts && opts.planes ? new Uint32Array(this._a.info(this._h).nz) : null;
+		return this._a.summary(this._h, planes);
+	}
+	// ca3d_step_until: steps in batches of checkEvery (default 8) until the grid is empty (extinct, default true) or a fixed point
+	// (still, default true), at most maxSteps steps; the batches and their waits run on a worker thread.
+	// -> Promise<{stepsDone, reason (STOP_EXTINCT | STOP_STILL bits; 0: maxSteps reached), summary}>
+	stepUntil(maxSteps, opts)
+	{
+		const o = Object.assign({ checkEvery: 8, extinct: true, still: true }, opts || {});
+		const mask = (o.extinct ? STOP_EXTINCT : 0) | (o.still ? STOP_STILL : 0);
+		return this._queue(() => this._a.stepUntilAsync(this._h, maxSteps, o.checkEvery, mask));
+	}
+
 	info() { this._idle("info"); return this._a.info(this._h); }
 	stats() { this._idle("stats"); return this._a.stats(this._h); }
 	renderStats() { this._idle("renderStats"); return this._a.renderStats(this._h); }
@@ -308,6 +329,8 @@ class EngineGroup
 	/** "transport": 0 peer copies (default), 1 RCCL; any other option goes to every slab engine */
 	setOption(name, value) { this._a.groupSetOption(this._g, name, value); }
 	info(rank) { return this._a.groupInfo(this._g, rank || 0); }
+	/** ca3d_group_summarize: Engine.summary() of the whole grid (every rank summarises its slab on its own device) */
+	summary(opts) { return this._a.groupSummary(this._g, opts && opts.planes ? new Uint32Array(this.gridSize) : null); }
 	render(uniforms, width, height, spp, targets)
 	{
 		const t = targets || {};
@@ -316,7 +339,7 @@ class EngineGroup
 }
 
 module.exports = {
-	Engine, EngineGroup, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
+	Engine, EngineGroup, STOP_EXTINCT, STOP_STILL, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
 	initialState, dispatchShape, randomFill, loadAddon, saveCheckpoint, loadCheckpoint
 };

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline */
+#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time */
 #define CA3D_LUT_LEN 81 /* 3 rule-sets x 27 slots (main_pathtraced.js:10, 155-159) */
 
 typedef struct ca3d_engine ca3d_t;
@@ -221,6 +221,10 @@ int ca3d_group_synchronize(ca3d_group_t *g);
 int ca3d_group_set_option(ca3d_group_t *g, const char *name, int64_t value);
 int ca3d_group_render(ca3d_group_t *g, const float uniforms[128], uint32_t width, uint32_t height, uint32_t spp,
                       uint8_t *presentation_rgba8, uint16_t *light_rgba16f, uint16_t *depth_rg16f);
+/* ca3d_summarize (below) for the whole grid: synchronises the group, summarises every rank on its own device and combines on the host —
+ * sums, the union of the boxes, the plane counts concatenated in z order (G entries, nullable), has_previous the AND of the ranks'. */
+struct ca3d_summary;
+int ca3d_group_summarize(ca3d_group_t *g, struct ca3d_summary *out, uint32_t *plane_population);
 
 /* Device pointer + byte size of the targets of the last ca3d_render call: 0 presentation RGBA8, 1 light RGBA16F,
  * 2 depth RG16F (row-major, top row first) — e.g. to gather the bands of a frame shared between GPUs without a
@@ -228,6 +232,80 @@ int ca3d_group_render(ca3d_group_t *g, const float uniforms[128], uint32_t width
 int ca3d_render_target(ca3d_t *h, int which, void **device_ptr, size_t *n_bytes);
 
 int ca3d_synchronize(ca3d_t *h);
+
+/*
+ * State summary on the device (no reference counterpart: its UI shows no statistics): how many cells are alive, where, and whether
+ * anything still changes — one pass of one kernel over the state, a few dozen bytes back over the bus instead of the state.
+ *
+ * What is summarised: the CURRENT state, buffer [step % 2], after everything already asked of the engine — queued steps are
+ * submitted first (option "queue"), and a pending resident launch is verified and, if it gave up, recovered from (the entry guard of
+ * ca3d_read_state: a summary never describes the output of a launch that would have been rolled back). Runs on the engine's stream
+ * (or the one given by ca3d_set_stream), only READS the state, touches neither the step counter nor the render history; like
+ * ca3d_read_state it joins frames in flight and changes no pixel of a later frame. Returns when the numbers are on the host (one
+ * small copy into pinned memory; nothing state-sized moves). Not configured / nothing uploaded: CA3D_ERR_NOT_CONFIGURED.
+ *
+ * Layouts: PACKED32 — a cell is a bit. UNPACKED — a cell is alive exactly when its word == 1, which is what the legacy step kernel
+ * (csrc/ca_unpacked.hip, ca_unpacked_literal: `st == 1u` survives, `st == 0u` may be born, anything else dies) and the legacy
+ * renderer (csrc/render_device.inc: `cells[...] == 1u`) take for alive. The digest is over the words as stored, in both layouts.
+ *
+ * births / deaths compare the current buffer with the other ping-pong buffer, which holds the state one step earlier after every
+ * full-grid step path, resident launches included (ca3d_device_buffer). has_previous is 0 — and both counts are 0 — right after
+ * ca3d_upload_state / ca3d_configure (a checkpoint load is both), after ca3d_device_buffer handed the buffers out (the caller may
+ * have written them) and on the target of ca3d_slab_gather, until the next step. Slab engines: after ca3d_slab_step,
+ * ca3d_slab_step_phase(EDGES) + (INTERIOR) and ca3d_slab_run (with and without overlap) through the per-step kernels the owned
+ * planes of the other buffer DO hold step - 1 (sub-step n - 1 of a batch of n <= ghost sub-steps still covers every owned plane) and
+ * has_previous is 1; it is 0 after a batch that ran as ONE launch of the resident slab kernel (kernel name ca_resident_slab_vn:
+ * that launch writes the final state only). population, box, digest and plane counts are exact on slabs in every case and cover
+ * the OWNED planes only (ghosts are never counted). Between the EDGES and the INTERIOR phase of a batch the edge zones have been
+ * ping-ponged through both buffers and neither holds a state: the call fails with CA3D_ERR_INVALID_ARGUMENT there.
+ *
+ * digest: the sum modulo 2^64, over all words w != 0, of mix(i, w), where i is the word's index in the FULL grid's state array (the
+ * digests of the slabs of a grid add up to the digest of the grid) and mix is the splitmix64 finaliser of
+ * key = ((uint64_t)i << 32) | w (i as a 64-bit integer, the shift modulo 2^64):
+ *   z = key + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^= z >> 31.
+ * A sum, so the result does not depend on the order workgroups finish in: two runs give the same 64 bits. Equal states have equal
+ * digests; it is a quick equality check (and the empty state's digest is 0), NOT a cryptographic one.
+ *
+ * plane_population (nullable): live cells per owned z plane, nz entries (ca3d_info.nz; entry 0 = plane z0), each <= G^2.
+ */
+typedef struct ca3d_summary
+{
+	uint64_t step;          /* ca3d_info.step of the state the numbers describe */
+	uint64_t population;    /* live cells (slab engine: owned planes only) */
+	uint64_t births;        /* alive now, dead one step earlier */
+	uint64_t deaths;        /* dead now, alive one step earlier */
+	uint64_t digest;        /* order-independent 64-bit digest, defined above */
+	uint32_t has_previous;  /* 1 iff births / deaths are meaningful (step >= 1 and see above); else both are 0 */
+	uint32_t box_min[3];    /* x, y, z of the live cells' bounding box, inclusive, GLOBAL cell coordinates */
+	uint32_t box_max[3];    /* population == 0: box_min = {G,G,G}, box_max = {0,0,0} */
+} ca3d_summary;
+int ca3d_summarize(ca3d_t *h, ca3d_summary *out, uint32_t *plane_population);
+/* Measurement: hipEvent time of the last ca3d_summarize's clear + kernel on the engine's stream, without the copy back and the host's
+ * wait (0 when option "stats" is off or nothing was summarised yet). */
+int ca3d_get_summary_time(ca3d_t *h, double *gpu_ms);
+
+/*
+ * Run until something happens, without a round trip per step: checks the stop conditions on entry, then repeats
+ * { ca3d_step(min(check_every, steps left)); summarise; check } until a condition in stop_mask holds or max_steps steps were taken.
+ *   CA3D_STOP_EXTINCT  population == 0
+ *   CA3D_STOP_STILL    has_previous && births + deaths == 0: the state is a fixed point of the rule
+ * *reason (nullable) receives the bits of stop_mask that fired (0: max_steps reached; both bits if both hold), *steps_done (nullable)
+ * the steps taken by this call, *out the last summary. The batches go through ca3d_step itself, so kernel selection (resident kernels
+ * for batches of "resident_min" steps and more, captured graphs, option "queue") is what it is for a caller's own ca3d_step(n), and
+ * the state afterwards is bit for bit the state after ca3d_step(steps_done). Conditions are only OBSERVED at the check points:
+ * steps_done is a multiple of check_every (or max_steps), not the first step at which a condition became true; a state that was still
+ * for a step in between and moved again is not noticed (it cannot happen: a fixed point stays one). CA3D_STOP_EXTINCT is not
+ * absorbing for rules whose born list contains 0: the empty grid then fills again at the next step.
+ * check_every == 0, out == NULL, unknown bits in stop_mask: CA3D_ERR_INVALID_ARGUMENT. Full-grid engines only: a slab engine gets
+ * CA3D_ERR_UNSUPPORTED (its neighbours must step with it).
+ */
+enum
+{
+	CA3D_STOP_EXTINCT = 1,
+	CA3D_STOP_STILL = 2
+};
+int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, ca3d_summary *out, uint32_t *steps_done,
+                    uint32_t *reason);
 
 /* Resident launches that gave up (a wait for neighbour tile faces timed out: not all workgroups were on the chip) and
  * whose steps the engine re-ran through the per-step kernels, since ca3d_create. The calls that noticed returned CA3D_OK
