@@ -12,7 +12,7 @@
 #include <new>
 #include <vector>
 
-#include "ca3d_internal.h"
+#include "ca3d_engine.h"
 
 using namespace ca3d;
 
@@ -38,12 +38,6 @@ struct ca3d_group
 namespace
 {
 
-#define G_HIP_TRY(expr)                                                                                                              \
-	do                                                                                                                               \
-	{                                                                                                                                \
-		hipError_t e_ = (expr);                                                                                                      \
-		if (e_ != hipSuccess) return set_error(e_ == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-	} while (0)
 #define G_TRY(expr)           \
 	do                        \
 	{                         \
@@ -56,8 +50,8 @@ int P(const ca3d_group *g) { return (int)g->eng.size(); }
 // device-to-device copy onto `stream` of the destination's device; a peer copy when the devices differ
 int copy_planes(void *dst, int dst_dev, const void *src, int src_dev, size_t bytes, hipStream_t stream)
 {
-	if (dst_dev == src_dev) G_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
-	else G_HIP_TRY(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, stream));
+	if (dst_dev == src_dev) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
+	else HIP_TRY(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, stream));
 	return CA3D_OK;
 }
 
@@ -70,41 +64,41 @@ int exchange_copy(ca3d_group *g)
 	const bool ring = g->layout == CA3D_LAYOUT_UNPACKED;
 	for (int k = 0; k < n; k++)
 	{
-		G_HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
-		G_HIP_TRY(hipEventRecord(g->ev_done[(size_t)k], engine_stream(g->eng[(size_t)k])));
+		HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
+		HIP_TRY(hipEventRecord(g->ev_done[(size_t)k], g->eng[(size_t)k]->stream));
 	}
 	for (int d = 0; d < n; d++)
 	{
 		const int above = (d + 1) % n, below = (d + n - 1) % n;
 		ca3d_t *e = g->eng[(size_t)d];
-		hipStream_t s = engine_stream(e);
-		G_HIP_TRY(hipSetDevice(g->devices[(size_t)d]));
+		hipStream_t s = e->stream;
+		HIP_TRY(hipSetDevice(g->devices[(size_t)d]));
 		void *dst, *src;
 		size_t bytes, sb;
 		// high ghost <- the first planes of the rank above (the top rank: rank 0's, plane G wraps to plane 0)
 		G_TRY(ca3d_slab_region(e, CA3D_SLAB_RECV_HIGH, &dst, &bytes));
 		G_TRY(ca3d_slab_region(g->eng[(size_t)above], CA3D_SLAB_SEND_LOW, &src, &sb));
-		if (above != d) G_HIP_TRY(hipStreamWaitEvent(s, g->ev_done[(size_t)above], 0));
+		if (above != d) HIP_TRY(hipStreamWaitEvent(s, g->ev_done[(size_t)above], 0));
 		G_TRY(copy_planes(dst, g->devices[(size_t)d], src, g->devices[(size_t)above], bytes, s));
 		// low ghost <- the last planes of the rank below; packed: rank 0 has none (z == -1 is dead)
 		if (ring || d != 0)
 		{
 			G_TRY(ca3d_slab_region(e, CA3D_SLAB_RECV_LOW, &dst, &bytes));
 			G_TRY(ca3d_slab_region(g->eng[(size_t)below], CA3D_SLAB_SEND_HIGH, &src, &sb));
-			if (below != d) G_HIP_TRY(hipStreamWaitEvent(s, g->ev_done[(size_t)below], 0));
+			if (below != d) HIP_TRY(hipStreamWaitEvent(s, g->ev_done[(size_t)below], 0));
 			G_TRY(copy_planes(dst, g->devices[(size_t)d], src, g->devices[(size_t)below], bytes, s));
 		}
-		G_HIP_TRY(hipEventRecord(g->ev_copied[(size_t)d], s));
+		HIP_TRY(hipEventRecord(g->ev_copied[(size_t)d], s));
 	}
 	for (int k = 0; k < n; k++)
 	{
 		// who read from rank k: the rank below (k's first planes -> its high ghost) and the rank above (k's last planes -> its low ghost)
 		const int above = (k + 1) % n, below = (k + n - 1) % n;
-		G_HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
-		hipStream_t s = engine_stream(g->eng[(size_t)k]);
-		if (below != k) G_HIP_TRY(hipStreamWaitEvent(s, g->ev_copied[(size_t)below], 0));
-		if (above != k && above != below && (ring || above != 0)) G_HIP_TRY(hipStreamWaitEvent(s, g->ev_copied[(size_t)above], 0));
-		engine_set_ghosts_valid(g->eng[(size_t)k], true);
+		HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
+		hipStream_t s = g->eng[(size_t)k]->stream;
+		if (below != k) HIP_TRY(hipStreamWaitEvent(s, g->ev_copied[(size_t)below], 0));
+		if (above != k && above != below && (ring || above != 0)) HIP_TRY(hipStreamWaitEvent(s, g->ev_copied[(size_t)above], 0));
+		g->eng[(size_t)k]->ghosts_valid = true;
 	}
 	return CA3D_OK;
 }
@@ -127,10 +121,10 @@ int exchange(ca3d_group *g)
 
 int check_group(const ca3d_group *g, bool need_state)
 {
-	if (!g) return set_error(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
-	if (!g->configured) return set_error(CA3D_ERR_NOT_CONFIGURED, "ca3d_group_configure has not been called");
-	if (need_state && !g->has_rules) return set_error(CA3D_ERR_NOT_CONFIGURED, "ca3d_group_set_rules has not been called");
-	if (need_state && !g->has_state) return set_error(CA3D_ERR_NOT_CONFIGURED, "ca3d_group_upload_state has not been called");
+	if (!g) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
+	if (!g->configured) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_group_configure has not been called");
+	if (need_state && !g->has_rules) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_group_set_rules has not been called");
+	if (need_state && !g->has_state) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_group_upload_state has not been called");
 	return CA3D_OK;
 }
 
@@ -157,18 +151,18 @@ extern "C"
 
 int ca3d_group_create(const int *device_ids, int n_devices, ca3d_group_t **out) CA3D_API_TRY
 {
-	if (!out) return set_error(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
 	*out = nullptr;
-	if (!device_ids || n_devices < 1 || n_devices > 64) return set_error(CA3D_ERR_INVALID_ARGUMENT, "a group takes 1 to 64 devices");
+	if (!device_ids || n_devices < 1 || n_devices > 64) return fail(CA3D_ERR_INVALID_ARGUMENT, "a group takes 1 to 64 devices");
 	ca3d_group *g = new (std::nothrow) ca3d_group();
-	if (!g) return set_error(CA3D_ERR_OUT_OF_MEMORY, "out of host memory");
+	if (!g) return fail(CA3D_ERR_OUT_OF_MEMORY, "out of host memory");
 	for (int k = 0; k < n_devices; k++)
 	{
 		ca3d_t *e = nullptr;
 		int rc = ca3d_create(device_ids[k], &e);
 		hipEvent_t a = nullptr, b = nullptr;
 		if (rc == CA3D_OK && (hipEventCreateWithFlags(&a, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess))
-			rc = set_error(CA3D_ERR_DEVICE, "hipEventCreate failed on device %d", device_ids[k]);
+			rc = fail(CA3D_ERR_DEVICE, "hipEventCreate failed on device %d", device_ids[k]);
 		if (rc)
 		{
 			if (e) ca3d_destroy(e);
@@ -213,7 +207,7 @@ CA3D_API_CATCH
 
 int ca3d_group_size(ca3d_group_t *g, int *out_n) CA3D_API_TRY
 {
-	if (!g || !out_n) return set_error(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	if (!g || !out_n) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
 	*out_n = P(g);
 	return CA3D_OK;
 }
@@ -221,8 +215,8 @@ CA3D_API_CATCH
 
 int ca3d_group_engine(ca3d_group_t *g, int rank, ca3d_t **out) CA3D_API_TRY
 {
-	if (!g || !out) return set_error(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
-	if (rank < 0 || rank >= P(g)) return set_error(CA3D_ERR_INVALID_ARGUMENT, "rank %d of %d", rank, P(g));
+	if (!g || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	if (rank < 0 || rank >= P(g)) return fail(CA3D_ERR_INVALID_ARGUMENT, "rank %d of %d", rank, P(g));
 	*out = g->eng[(size_t)rank];
 	return CA3D_OK;
 }
@@ -230,11 +224,11 @@ CA3D_API_CATCH
 
 int ca3d_group_configure(ca3d_group_t *g, uint32_t grid_size, int layout, uint32_t ghost) CA3D_API_TRY
 {
-	if (!g) return set_error(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
+	if (!g) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
 	const uint32_t n = (uint32_t)P(g);
-	if (grid_size == 0 || grid_size % n) return set_error(CA3D_ERR_INVALID_ARGUMENT, "a grid of %u planes does not split evenly over %u slabs", grid_size, n);
+	if (grid_size == 0 || grid_size % n) return fail(CA3D_ERR_INVALID_ARGUMENT, "a grid of %u planes does not split evenly over %u slabs", grid_size, n);
 	const uint32_t nz = grid_size / n;
-	if (ghost == 0 || ghost > nz) return set_error(CA3D_ERR_INVALID_ARGUMENT, "ghost depth must be in [1, %u] (planes per slab)", nz);
+	if (ghost == 0 || ghost > nz) return fail(CA3D_ERR_INVALID_ARGUMENT, "ghost depth must be in [1, %u] (planes per slab)", nz);
 	destroy_full(g);
 	g->configured = g->has_state = false;
 	for (uint32_t k = 0; k < n; k++) G_TRY(ca3d_configure_slab(g->eng[k], grid_size, layout, k * nz, nz, ghost));
@@ -255,7 +249,7 @@ CA3D_API_CATCH
 int ca3d_group_set_rules(ca3d_group_t *g, const int32_t *main_offsets, uint32_t n_main, const int32_t *edges_offsets, uint32_t n_edges,
                          const int32_t *corners_offsets, uint32_t n_corners, const uint32_t survive[CA3D_LUT_LEN], const uint32_t born[CA3D_LUT_LEN]) CA3D_API_TRY
 {
-	if (!g) return set_error(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
+	if (!g) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
 	for (ca3d_t *e : g->eng) G_TRY(ca3d_set_rules(e, main_offsets, n_main, edges_offsets, n_edges, corners_offsets, n_corners, survive, born));
 	for (ca3d_t *f : g->full) G_TRY(ca3d_set_rules(f, main_offsets, n_main, edges_offsets, n_edges, corners_offsets, n_corners, survive, born));
 	g->r_main.assign(main_offsets, main_offsets + n_main);
@@ -271,12 +265,12 @@ CA3D_API_CATCH
 int ca3d_group_upload_state(ca3d_group_t *g, const uint32_t *words, size_t n_words) CA3D_API_TRY
 {
 	G_TRY(check_group(g, false));
-	if (!words) return set_error(CA3D_ERR_INVALID_ARGUMENT, "words is NULL");
+	if (!words) return fail(CA3D_ERR_INVALID_ARGUMENT, "words is NULL");
 	const size_t n = (size_t)P(g);
 	ca3d_info info;
 	G_TRY(ca3d_get_info(g->eng[0], &info));
 	const size_t per = (size_t)info.state_words;
-	if (n_words != per * n) return set_error(CA3D_ERR_INVALID_ARGUMENT, "state has %zu words, expected %zu", n_words, per * n);
+	if (n_words != per * n) return fail(CA3D_ERR_INVALID_ARGUMENT, "state has %zu words, expected %zu", n_words, per * n);
 	for (size_t k = 0; k < n; k++) G_TRY(ca3d_upload_state(g->eng[k], words + k * per, per)); // z is the slowest index: a slab is contiguous
 	g->has_state = true;
 	g->ghosts_valid = false;
@@ -288,13 +282,13 @@ CA3D_API_CATCH
 int ca3d_group_read_state(ca3d_group_t *g, uint32_t *words, size_t n_words) CA3D_API_TRY
 {
 	G_TRY(check_group(g, false));
-	if (!g->has_state) return set_error(CA3D_ERR_NOT_CONFIGURED, "no state to read: upload first");
-	if (!words) return set_error(CA3D_ERR_INVALID_ARGUMENT, "words is NULL");
+	if (!g->has_state) return fail(CA3D_ERR_NOT_CONFIGURED, "no state to read: upload first");
+	if (!words) return fail(CA3D_ERR_INVALID_ARGUMENT, "words is NULL");
 	const size_t n = (size_t)P(g);
 	ca3d_info info;
 	G_TRY(ca3d_get_info(g->eng[0], &info));
 	const size_t per = (size_t)info.state_words;
-	if (n_words != per * n) return set_error(CA3D_ERR_INVALID_ARGUMENT, "state has %zu words, expected %zu", n_words, per * n);
+	if (n_words != per * n) return fail(CA3D_ERR_INVALID_ARGUMENT, "state has %zu words, expected %zu", n_words, per * n);
 	for (size_t k = 0; k < n; k++) G_TRY(ca3d_read_state(g->eng[k], words + k * per, per));
 	return CA3D_OK;
 }
@@ -320,7 +314,7 @@ CA3D_API_CATCH
 
 int ca3d_group_synchronize(ca3d_group_t *g) CA3D_API_TRY
 {
-	if (!g) return set_error(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
+	if (!g) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
 	for (ca3d_t *e : g->eng) G_TRY(ca3d_synchronize(e));
 	for (ca3d_t *f : g->full) G_TRY(ca3d_synchronize(f));
 	return CA3D_OK;
@@ -329,14 +323,14 @@ CA3D_API_CATCH
 
 int ca3d_group_set_option(ca3d_group_t *g, const char *name, int64_t value) CA3D_API_TRY
 {
-	if (!g || !name) return set_error(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	if (!g || !name) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
 	if (!strcmp(name, "transport"))
 	{
-		if (value != 0 && value != 1) return set_error(CA3D_ERR_INVALID_ARGUMENT, "transport must be 0 (peer copies) or 1 (RCCL send / receive)");
+		if (value != 0 && value != 1) return fail(CA3D_ERR_INVALID_ARGUMENT, "transport must be 0 (peer copies) or 1 (RCCL send / receive)");
 		if (value == 1)
 			for (size_t i = 0; i < g->devices.size(); i++)
 				for (size_t j = i + 1; j < g->devices.size(); j++)
-					if (g->devices[i] == g->devices[j]) return set_error(CA3D_ERR_UNSUPPORTED, "the RCCL transport needs one device per slab (device %d appears twice)", g->devices[i]);
+					if (g->devices[i] == g->devices[j]) return fail(CA3D_ERR_UNSUPPORTED, "the RCCL transport needs one device per slab (device %d appears twice)", g->devices[i]);
 		g->transport = (int)value;
 		g->ghosts_valid = false;
 		return CA3D_OK;
@@ -353,8 +347,8 @@ CA3D_API_CATCH
 int ca3d_group_summarize(ca3d_group_t *g, ca3d_summary *out, uint32_t *plane_population) CA3D_API_TRY
 {
 	G_TRY(check_group(g, false));
-	if (!g->has_state) return set_error(CA3D_ERR_NOT_CONFIGURED, "no state to summarise: upload first");
-	if (!out) return set_error(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	if (!g->has_state) return fail(CA3D_ERR_NOT_CONFIGURED, "no state to summarise: upload first");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
 	G_TRY(ca3d_group_synchronize(g));
 	const uint32_t n = (uint32_t)P(g), nz = g->G / n;
 	ca3d_summary t;
@@ -392,8 +386,8 @@ int ca3d_group_render(ca3d_group_t *g, const float uniforms[128], uint32_t width
                       uint16_t *light_rgba16f, uint16_t *depth_rg16f) CA3D_API_TRY
 {
 	G_TRY(check_group(g, true));
-	if (g->layout != CA3D_LAYOUT_PACKED32) return set_error(CA3D_ERR_UNSUPPORTED, "the shared frame takes the packed layout");
-	if (!uniforms) return set_error(CA3D_ERR_INVALID_ARGUMENT, "uniforms is NULL");
+	if (g->layout != CA3D_LAYOUT_PACKED32) return fail(CA3D_ERR_UNSUPPORTED, "the shared frame takes the packed layout");
+	if (!uniforms) return fail(CA3D_ERR_INVALID_ARGUMENT, "uniforms is NULL");
 	const int n = P(g);
 	if (g->full.empty())
 	{
@@ -408,7 +402,7 @@ int ca3d_group_render(ca3d_group_t *g, const float uniforms[128], uint32_t width
 			if (rc == CA3D_OK) rc = ca3d_configure(f, g->G, g->G, g->G, g->layout);
 			if (rc == CA3D_OK) rc = ca3d_set_rules(f, g->r_main.data(), (uint32_t)g->r_main.size(), g->r_edges.data(), (uint32_t)g->r_edges.size(), g->r_corners.data(),
 			                                        (uint32_t)g->r_corners.size(), g->r_survive, g->r_born);
-			if (rc == CA3D_OK) rc = ca3d_set_stream(f, engine_stream(g->eng[(size_t)k])); // one stream per device: the gather, the band and the next batch stay ordered
+			if (rc == CA3D_OK) rc = ca3d_set_stream(f, g->eng[(size_t)k]->stream); // one stream per device: the gather, the band and the next batch stay ordered
 			if (rc) { if (f) ca3d_destroy(f); destroy_full(g); return rc; }
 			g->full.push_back(f);
 		}
@@ -419,8 +413,8 @@ int ca3d_group_render(ca3d_group_t *g, const float uniforms[128], uint32_t width
 	// every slab's owned planes -> every rank's full volume (the ranks' own batches are done: ev_done)
 	for (int k = 0; k < n; k++)
 	{
-		G_HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
-		G_HIP_TRY(hipEventRecord(g->ev_done[(size_t)k], engine_stream(g->eng[(size_t)k])));
+		HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
+		HIP_TRY(hipEventRecord(g->ev_done[(size_t)k], g->eng[(size_t)k]->stream));
 	}
 	for (int d = 0; d < n; d++)
 	{
@@ -429,23 +423,23 @@ int ca3d_group_render(ca3d_group_t *g, const float uniforms[128], uint32_t width
 		void *vol;
 		size_t vol_bytes;
 		G_TRY(engine_state_buffer(g->full[(size_t)d], fi.current_buffer, &vol, &vol_bytes));
-		G_HIP_TRY(hipSetDevice(g->devices[(size_t)d]));
-		hipStream_t s = engine_stream(g->eng[(size_t)d]);
+		HIP_TRY(hipSetDevice(g->devices[(size_t)d]));
+		hipStream_t s = g->eng[(size_t)d]->stream;
 		for (int k = 0; k < n; k++)
 		{
 			void *owned;
 			size_t bytes;
 			G_TRY(ca3d_slab_region(g->eng[(size_t)k], CA3D_SLAB_OWNED, &owned, &bytes));
-			if (k != d) G_HIP_TRY(hipStreamWaitEvent(s, g->ev_done[(size_t)k], 0));
+			if (k != d) HIP_TRY(hipStreamWaitEvent(s, g->ev_done[(size_t)k], 0));
 			G_TRY(copy_planes((char *)vol + (size_t)k * bytes, g->devices[(size_t)d], owned, g->devices[(size_t)k], bytes, s));
 		}
-		G_HIP_TRY(hipEventRecord(g->ev_copied[(size_t)d], s));
+		HIP_TRY(hipEventRecord(g->ev_copied[(size_t)d], s));
 	}
 	for (int k = 0; k < n; k++) // a slab is not stepped on while somebody still copies out of it
 	{
-		G_HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
+		HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
 		for (int d = 0; d < n; d++)
-			if (d != k) G_HIP_TRY(hipStreamWaitEvent(engine_stream(g->eng[(size_t)k]), g->ev_copied[(size_t)d], 0));
+			if (d != k) HIP_TRY(hipStreamWaitEvent(g->eng[(size_t)k]->stream, g->ev_copied[(size_t)d], 0));
 	}
 	// bands
 	const size_t px_row = (size_t)width;
@@ -465,31 +459,31 @@ int ca3d_group_render(ca3d_group_t *g, const float uniforms[128], uint32_t width
 		band_rows(height, n, k, &y0, &y1);
 		if (y1 <= y0) continue;
 		ca3d_t *f = g->full[(size_t)k];
-		G_HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
-		hipStream_t s = engine_stream(g->eng[(size_t)k]);
+		HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
+		hipStream_t s = g->eng[(size_t)k]->stream;
 		void *t;
 		size_t tb;
 		if (presentation_rgba8)
 		{
 			G_TRY(ca3d_render_target(f, 0, &t, &tb));
-			G_HIP_TRY(hipMemcpyAsync(presentation_rgba8 + (size_t)y0 * px_row * 4u, (char *)t + (size_t)y0 * px_row * 4u, (size_t)(y1 - y0) * px_row * 4u, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync(presentation_rgba8 + (size_t)y0 * px_row * 4u, (char *)t + (size_t)y0 * px_row * 4u, (size_t)(y1 - y0) * px_row * 4u, hipMemcpyDeviceToHost, s));
 		}
 		if (light_rgba16f)
 		{
 			G_TRY(ca3d_render_target(f, 1, &t, &tb));
-			G_HIP_TRY(hipMemcpyAsync((char *)light_rgba16f + (size_t)y0 * px_row * 8u, (char *)t + (size_t)y0 * px_row * 8u, (size_t)(y1 - y0) * px_row * 8u, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync((char *)light_rgba16f + (size_t)y0 * px_row * 8u, (char *)t + (size_t)y0 * px_row * 8u, (size_t)(y1 - y0) * px_row * 8u, hipMemcpyDeviceToHost, s));
 		}
 		if (depth_rg16f)
 		{
 			G_TRY(ca3d_render_target(f, 2, &t, &tb));
-			G_HIP_TRY(hipMemcpyAsync((char *)depth_rg16f + (size_t)y0 * px_row * 4u, (char *)t + (size_t)y0 * px_row * 4u, (size_t)(y1 - y0) * px_row * 4u, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync((char *)depth_rg16f + (size_t)y0 * px_row * 4u, (char *)t + (size_t)y0 * px_row * 4u, (size_t)(y1 - y0) * px_row * 4u, hipMemcpyDeviceToHost, s));
 		}
 	}
 	if (presentation_rgba8 || light_rgba16f || depth_rg16f)
 		for (int k = 0; k < n; k++)
 		{
-			G_HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
-			G_HIP_TRY(hipStreamSynchronize(engine_stream(g->eng[(size_t)k])));
+			HIP_TRY(hipSetDevice(g->devices[(size_t)k]));
+			HIP_TRY(hipStreamSynchronize(g->eng[(size_t)k]->stream));
 		}
 	g->rw = width;
 	g->rh = height;

@@ -174,7 +174,7 @@ struct RenderLaunch
 	// next frame of the same state with stale ones — a converged frame right after literal ones came out black that way)
 	bool *occ_built = nullptr, *bricks_built = nullptr;
 	void *stream_scratch = nullptr;
-	// two frames in flight (ca3d_api.cpp, FrameLane): the frame before this one runs on another stream; everything of THIS frame that
+	// two frames in flight (ca3d_engine.h, FrameLane): the frame before this one runs on another stream; everything of THIS frame that
 	// writes a target both share (the presentation surface) waits for this event first. Null: nothing to wait for.
 	hipEvent_t after = nullptr;
 	int walk_share_pct = 100; // frames in flight: the share of the chip's wave slots each persistent walk launch of this frame asks for (100: the frame has the chip to itself)
@@ -213,7 +213,7 @@ hipError_t launch_render_stream(const void *params, void *scratch, uint32_t W, u
                                 bool *sparse_too = nullptr); // *sparse_too: the passes launched draw scattered sparse volumes as well (render.hip then leaves its scheduled kernel out)
 
 // ca_packed.hip / ca_unpacked.hip
-hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream, const char **kernel_name);
+hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream);
 const char *packed_kernel_name(const CanonRules &r, uint32_t G, int variant);
 // ca_packed_vn.hip: the specialised von Neumann kernel (truth-table rules, power-of-two grids)
 bool vn_rule_applies(const CanonRules &r, int variant); // main list von Neumann, edges / corners rule-sets without effect
@@ -278,12 +278,10 @@ void resident_stream_retired(hipStream_t stream); // call after waiting for a st
 int jit_resident_slab_kernel(int device, uint32_t lut_s, uint32_t lut_b, int pz, void **fn, std::string *log);
 // Steps one fused launch advances for these rules / grid (0 = no fused kernel applies).
 int packed_fused_steps(const CanonRules &r, uint32_t G, int variant);
-hipError_t launch_packed_fused(const PackedLaunch &l, hipStream_t stream, const char **kernel_name);
+hipError_t launch_packed_fused(const PackedLaunch &l, hipStream_t stream);
 hipError_t launch_unpacked_step(const UnpackedLaunch &l, hipStream_t stream, const char **kernel_name);
 
 
-// ca3d_api.cpp internals used by ca3d_group.cpp
-int set_error(int code, const char *fmt, ...);
 // No C++ exception leaves an extern "C" entry point: each one is `int ca3d_x(...) CA3D_API_TRY { ... } CA3D_API_CATCH` — a
 // function-try-block whose handler maps what was thrown to a status code and a ca3d_last_error() message (ca3d_api.cpp;
 // tests/test_capi_cpu.py checks that every function include/ca3d.h declares is defined this way, and runs the handler on the CPU
@@ -296,15 +294,5 @@ void jit_stats(ca3d_jit_stats *out); // ca_jit.cpp
 	{                                           \
 		return ca3d::exception_to_status();     \
 	}
-int engine_device(const ca3d_engine *h);
-hipStream_t engine_stream(const ca3d_engine *h);
-int engine_mark_state(ca3d_engine *h); // both buffers zeroed on the engine's stream, "has a state" — for engines whose state arrives by device copies
-// ca3d_device_buffer for a writer inside the library (the group's peer copies): the state counts as rewritten by THIS call only — the
-// public call must assume writes at any later time and makes every frame rebuild its derived buffers while the pointer is valid
-int engine_state_buffer(ca3d_engine *h, int which, void **device_ptr, size_t *n_bytes);
-void engine_set_ghosts_valid(ca3d_engine *h, bool valid);
-bool engine_ghosts_valid(const ca3d_engine *h);
-int engines_rccl_init_all(ca3d_engine **engines, int n);
-int engines_rccl_exchange_all(ca3d_engine **engines, int n);
 
 } // namespace ca3d

@@ -37,7 +37,7 @@ __global__ void noop_kernel() {}
 
 // Are two streams served by DIFFERENT hardware queues — does work on `b` run while a kernel on `a` is still running? HIP maps its
 // streams onto a few hardware queues (four by default) by a policy of its own, and two streams on one queue execute in order: the
-// engine's two frame lanes (ca3d_api.cpp) overlap nothing then. Probed once per pair: a 2 ms one-wave spin on `a`, an empty kernel
+// engine's two frame lanes (ca3d_render.cpp) overlap nothing then. Probed once per pair: a 2 ms one-wave spin on `a`, an empty kernel
 // on `b`; `b` finishing first means separate queues. Both streams must be idle; they are when the call returns.
 hipError_t streams_concurrent(hipStream_t a, hipStream_t b, bool *out)
 {

@@ -583,9 +583,8 @@ int packed_fused_steps(const CanonRules &r, uint32_t G, int variant)
 	return fused_geometry(G, &g, &W) ? 2 : 0;
 }
 
-hipError_t launch_packed_fused(const PackedLaunch &l, hipStream_t stream, const char **kernel_name)
+hipError_t launch_packed_fused(const PackedLaunch &l, hipStream_t stream)
 {
-	if (kernel_name) *kernel_name = "ca_packed_fused<T=2>";
 	if (l.pr.hi <= l.pr.lo) return hipSuccess;
 	switch (l.rules->main)
 	{
@@ -595,16 +594,15 @@ hipError_t launch_packed_fused(const PackedLaunch &l, hipStream_t stream, const 
 	}
 }
 
-hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream, const char **kernel_name)
+hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream)
 {
 	const CanonRules &r = *l.rules;
-	if (kernel_name) *kernel_name = packed_kernel_name(r, l.pr.G, l.variant);
 	if (l.pr.hi <= l.pr.lo)
 	{
 		if (l.pr.hi2 <= l.pr.lo2) return hipSuccess;
 		PackedLaunch only = l; // only the second range has planes
 		only.pr.lo = l.pr.lo2; only.pr.hi = l.pr.hi2; only.pr.lo2 = only.pr.hi2 = 0;
-		return launch_packed_step(only, stream, nullptr);
+		return launch_packed_step(only, stream);
 	}
 	if (vn_kernel_applies(r, l.pr.G, l.variant)) return launch_packed_vn(l, stream);
 	if (const RollJit *rj = l.roll_jit; rj && rj->cv_np2 > 0 && (u32)rj->cv_np2 * 128u == l.pr.G && rj->main == (int)r.main && rj->e == r.need[1] && rj->c == r.need[2])
@@ -628,7 +626,6 @@ hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream, const c
 			const u32 *in = l.in;
 			u32 *out = l.out;
 			void *args[] = {(void *)&in, (void *)&out, (void *)&a};
-			if (kernel_name) *kernel_name = "ca_packed_roll_np2(jit)";
 			return hipModuleLaunchKernel((hipFunction_t)rj->np2[zi], bpp * nruns, 1, 1, 256, 1, 1, 0, stream, args, nullptr);
 		}
 	}
@@ -648,7 +645,6 @@ hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream, const c
 		PlaneRange pr = l.pr;
 		if (!two) pr.lo2 = pr.hi2 = 0;
 		void *args[] = {(void *)&in, (void *)&out, (void *)&pr, (void *)&a};
-		if (kernel_name) *kernel_name = "ca_packed_rows(jit)";
 		return hipModuleLaunchKernel((hipFunction_t)(Z > 1u ? rj->deep : rj->flat), bpp * nruns, 1, 1, 256, 1, 1, 0, stream, args, nullptr);
 	}
 	if (l.pr.hi2 > l.pr.lo2 && !use_class_kernel(r, l.pr.G, l.variant))
@@ -657,8 +653,8 @@ hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream, const c
 		PackedLaunch a = l, b = l;
 		a.pr.lo2 = a.pr.hi2 = 0;
 		b.pr.lo = l.pr.lo2; b.pr.hi = l.pr.hi2; b.pr.lo2 = b.pr.hi2 = 0;
-		hipError_t e = launch_packed_step(a, stream, nullptr);
-		return e != hipSuccess ? e : launch_packed_step(b, stream, nullptr);
+		hipError_t e = launch_packed_step(a, stream);
+		return e != hipSuccess ? e : launch_packed_step(b, stream);
 	}
 	if (use_class_kernel(r, l.pr.G, l.variant))
 	{

@@ -1252,7 +1252,7 @@ hipError_t launch_render_stream(const void *params, void *scratch, uint32_t W, u
 	S.pop_at = pop_env >= 1 && pop_env <= 64 ? pop_env : 16;
 	static const int tb_env = getenv("CA3D_STREAM_TAIL_BATCH") ? atoi(getenv("CA3D_STREAM_TAIL_BATCH")) : 1;
 	S.tail_batch = tb_env == 2 ? 2 : (tb_env ? 1 : 0); // (2, tuning: the batched loop from the first cell on)
-	// A persistent walk launch asks for the wave slots of the whole chip — unless other frames are in flight beside this one (ca3d_api.cpp,
+	// A persistent walk launch asks for the wave slots of the whole chip — unless other frames are in flight beside this one (ca3d_render.cpp,
 	// FrameLane): then for its share of them, so that the frames' walks run side by side from their first workgroup on instead of one
 	// launch filling the chip and the next one seeping into its tail (tools/sweep_stream_wgs.sh; CA3D_STREAM_WGS_PCT overrides: tuning).
 	static const int wgs_env = getenv("CA3D_STREAM_WGS_PCT") ? atoi(getenv("CA3D_STREAM_WGS_PCT")) : 0;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A host that steps between converged frames (ca3d_step(1); ca3d_render without target arrays; ...): every frame waits for the step before
 it, which waited for the frame before that — nothing is ever in flight beside a frame, so the frame pipeline must cost such a loop
-nothing (its frames take the whole chip: ca3d_api.cpp, `beside`). ms per iteration with the pipeline on and off, and the pure render loop."""
+nothing (its frames take the whole chip: ca3d_render.cpp, `beside`). ms per iteration with the pipeline on and off, and the pure render loop."""
 import os
 import sys
 import time
