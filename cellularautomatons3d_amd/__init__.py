@@ -12,4 +12,8 @@ def __getattr__(name):
         from . import engine
 
         return getattr(engine, name)
+    if name == "Ensemble":
+        from . import ensemble
+
+        return ensemble.Ensemble
     raise AttributeError(name)

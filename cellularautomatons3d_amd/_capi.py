@@ -56,6 +56,8 @@ class SummaryStruct(C.Structure):
 
 
 STOP_EXTINCT, STOP_STILL = 1, 2
+ENSEMBLE_ALL = 0xFFFFFFFF
+ENSEMBLE_WORDS = 8192  # words of one 64^3 universe
 
 
 class CommInfo(C.Structure):
@@ -123,6 +125,17 @@ SYMBOLS = [
     ("ca3d_summarize", C.c_int, [_H, C.POINTER(SummaryStruct), _u32p]),
     ("ca3d_get_summary_time", C.c_int, [_H, C.POINTER(C.c_double)]),
     ("ca3d_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct), _u32p, _u32p]),
+    ("ca3d_ensemble_create", C.c_int, [C.c_int, C.POINTER(_H)]),
+    ("ca3d_ensemble_destroy", C.c_int, [_H]),
+    ("ca3d_ensemble_configure", C.c_int, [_H, C.c_uint32, C.c_uint32]),
+    ("ca3d_ensemble_set_rules", C.c_int, [_H, C.c_uint32, _i32p, C.c_uint32, _i32p, C.c_uint32, _i32p, C.c_uint32, _u32p, _u32p]),
+    ("ca3d_ensemble_upload_state", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.c_size_t]),
+    ("ca3d_ensemble_read_state", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.c_size_t]),
+    ("ca3d_ensemble_step", C.c_int, [_H, C.c_uint32]),
+    ("ca3d_ensemble_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
+    ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),
+    ("ca3d_ensemble_synchronize", C.c_int, [_H]),
+    ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_render_target", C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     ("ca3d_synchronize", C.c_int, [_H]),
     ("ca3d_recovered_launches", C.c_int, [_H, C.POINTER(C.c_uint32)]),

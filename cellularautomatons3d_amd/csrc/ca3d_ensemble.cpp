@@ -1,0 +1,349 @@
+// ca3d_ensemble_*: many independent 64^3 universes side by side on one device (include/ca3d.h). One workgroup of ca_ensemble_vn64
+// (ca_ensemble.hip) steps one universe with its state in registers; a launch over B workgroups is B universes, each with its own von
+// Neumann rule table, its own step counter, its own summary record and — in ca3d_ensemble_step_until — its own moment to stop. The host
+// side is bookkeeping: the per-universe arrays, the rule canonicalisation (the engine's own, rules.cpp), and cutting long calls into
+// launches of at most kEnsembleMaxSteps steps.
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "ca3d_engine.h"
+
+using namespace ca3d;
+
+struct ca3d_ensemble
+{
+	int device = 0;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+	uint32_t n = 0; // universes; 0: not configured
+	uint32_t *state = nullptr, *prev = nullptr, *rules = nullptr, *steps_done = nullptr, *reason = nullptr;
+	ca3d_summary *records = nullptr;
+	std::vector<uint8_t> has_rules, has_state;
+	uint32_t missing_rules = 0, missing_state = 0; // universes without either
+	// the last step call, for ca3d_ensemble_get_stats
+	bool timed = false;
+	uint64_t last_steps = 0, last_launches = 0;
+	double last_cell_steps = 0;
+};
+
+namespace
+{
+
+void free_arrays(ca3d_ensemble *e)
+{
+	for (void *p : {(void *)e->state, (void *)e->prev, (void *)e->rules, (void *)e->steps_done, (void *)e->reason, (void *)e->records})
+		if (p) hipFree(p);
+	e->state = e->prev = e->rules = e->steps_done = e->reason = nullptr;
+	e->records = nullptr;
+	e->n = 0;
+	e->timed = false;
+}
+
+int check_range(const ca3d_ensemble *e, uint32_t first, uint32_t count)
+{
+	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called");
+	if (count == 0 || first >= e->n || count > e->n - first) return fail(CA3D_ERR_INVALID_ARGUMENT, "universes [%u, %u + %u) of %u", first, first, count, e->n);
+	return CA3D_OK;
+}
+
+// configure -> set_rules (every universe) -> upload (every universe) -> step
+int ensemble_ready(const ca3d_ensemble *e)
+{
+	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called");
+	if (e->missing_rules) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_set_rules has not been called for %u of %u universes", e->missing_rules, e->n);
+	if (e->missing_state) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for %u of %u universes", e->missing_state, e->n);
+	return CA3D_OK;
+}
+
+EnsembleLaunch launch_of(const ca3d_ensemble *e)
+{
+	EnsembleLaunch l{};
+	l.state = e->state; l.prev = e->prev;
+	l.rules = e->rules;
+	l.records = e->records;
+	l.steps_done = e->steps_done; l.reason = e->reason;
+	l.first = 0; l.count = e->n;
+	return l;
+}
+
+// `total` steps at most for every universe, as launches of at most kEnsembleMaxSteps steps whose ends fall on check points; with a
+// stop mask a universe leaves at the first check point at which one of its conditions holds
+int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_mask)
+{
+	HIP_TRY(hipEventRecord(e->ev_start, e->stream));
+	uint64_t launches = 0;
+	uint32_t base = 0;
+	do
+	{
+		uint32_t n = total - base;
+		if (n > kEnsembleMaxSteps)
+		{
+			n = kEnsembleMaxSteps;
+			if (stop_mask && check_every <= kEnsembleMaxSteps) n -= (base + n) % check_every; // end on a check point (base is one)
+		}
+		EnsembleLaunch l = launch_of(e);
+		l.steps = n;
+		l.base = base;
+		l.check_every = check_every;
+		l.stop_mask = stop_mask;
+		l.final = base + n == total;
+		HIP_TRY(launch_ensemble(l, e->stream));
+		launches++;
+		base += n;
+	} while (base < total);
+	HIP_TRY(hipEventRecord(e->ev_stop, e->stream));
+	e->timed = true;
+	e->last_launches = launches;
+	return CA3D_OK;
+}
+
+} // namespace
+
+extern "C"
+{
+
+int ca3d_ensemble_create(int device, ca3d_ensemble_t **out) CA3D_API_TRY
+{
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	*out = nullptr;
+	int n = 0;
+	hipError_t err = hipGetDeviceCount(&n);
+	if (err != hipSuccess || n <= 0)
+		return fail(CA3D_ERR_DEVICE, "no HIP device available (%s); an ensemble has no CPU fallback", err != hipSuccess ? hipGetErrorString(err) : "device count is 0");
+	if (device < 0 || device >= n) return fail(CA3D_ERR_INVALID_ARGUMENT, "device %d out of range [0,%d)", device, n);
+	HIP_TRY(hipSetDevice(device));
+	hipDeviceProp_t prop;
+	HIP_TRY(hipGetDeviceProperties(&prop, device));
+	if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+		return fail(CA3D_ERR_DEVICE, "device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
+	ca3d_ensemble *e = new (std::nothrow) ca3d_ensemble();
+	if (!e) return fail(CA3D_ERR_OUT_OF_MEMORY, "out of host memory");
+	e->device = device;
+	err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
+	if (err == hipSuccess) err = hipEventCreate(&e->ev_start);
+	if (err == hipSuccess) err = hipEventCreate(&e->ev_stop);
+	if (err != hipSuccess)
+	{
+		ca3d_ensemble_destroy(e);
+		return fail(CA3D_ERR_DEVICE, "ensemble set-up failed: %s", hipGetErrorString(err));
+	}
+	*out = e;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
+{
+	if (!e) return CA3D_OK;
+	hipSetDevice(e->device);
+	if (e->stream) hipStreamSynchronize(e->stream);
+	free_arrays(e);
+	if (e->ev_start) hipEventDestroy(e->ev_start);
+	if (e->ev_stop) hipEventDestroy(e->ev_stop);
+	if (e->stream) hipStreamDestroy(e->stream);
+	delete e;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_configure(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (grid_size != 64u) return fail(CA3D_ERR_UNSUPPORTED, "an ensemble steps 64^3 universes only (got %u): one workgroup holds one universe in its registers", grid_size);
+	if (n_universes == 0 || n_universes > (1u << 20)) return fail(CA3D_ERR_INVALID_ARGUMENT, "an ensemble holds 1 to %u universes (got %u)", 1u << 20, n_universes);
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	free_arrays(e);
+	const size_t state_bytes = (size_t)n_universes * kEnsembleWords * sizeof(uint32_t), word_bytes = (size_t)n_universes * sizeof(uint32_t);
+	hipError_t err = hipMalloc((void **)&e->state, state_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->prev, state_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->rules, word_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->steps_done, word_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->reason, word_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->records, (size_t)n_universes * sizeof(ca3d_summary));
+	if (err != hipSuccess)
+	{
+		free_arrays(e);
+		(void)hipGetLastError();
+		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating %u universes: %s", n_universes, hipGetErrorString(err));
+	}
+	e->n = n_universes;
+	e->has_rules.assign(n_universes, 0);
+	e->has_state.assign(n_universes, 0);
+	e->missing_rules = e->missing_state = n_universes;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe, const int32_t *main_offsets, uint32_t n_main, const int32_t *edges_offsets,
+                            uint32_t n_edges, const int32_t *corners_offsets, uint32_t n_corners, const uint32_t survive[CA3D_LUT_LEN],
+                            const uint32_t born[CA3D_LUT_LEN]) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	const bool all = universe == CA3D_ENSEMBLE_ALL;
+	int rc = check_range(e, all ? 0u : universe, all ? e->n : 1u);
+	if (rc) return rc;
+	const std::string who = all ? std::string("every universe") : "universe " + std::to_string(universe);
+	CanonRules r;
+	std::string err;
+	rc = canonicalize_rules(main_offsets, n_main, edges_offsets, n_edges, corners_offsets, n_corners, survive, born, &r, &err);
+	if (rc) return fail(rc, "%s: %s", who.c_str(), err.c_str());
+	if (!vn_rule_applies(r, -1))
+		return fail(CA3D_ERR_UNSUPPORTED, "%s: an ensemble takes rules that reduce to a von Neumann table pair (main list von Neumann, edges / corners tables that cannot fire)",
+		            who.c_str());
+	uint32_t lut_s, lut_b;
+	vn_tables(r, &lut_s, &lut_b);
+	const uint32_t word = (lut_s & 0x7Fu) | (lut_b & 0x7Fu) << 8;
+	const uint32_t first = all ? 0u : universe, count = all ? e->n : 1u;
+	const std::vector<uint32_t> words(count, word);
+	HIP_TRY(hipSetDevice(e->device));
+	// stream-ordered behind the steps already enqueued, which keep the rules they were enqueued under; the source is consumed on return
+	HIP_TRY(hipMemcpyAsync(e->rules + first, words.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_rules[u]) { e->has_rules[u] = 1; e->missing_rules--; }
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_upload_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *words, size_t n_words) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if (!words || n_words != (size_t)count * kEnsembleWords)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes take %zu words (got %zu)", count, (size_t)count * kEnsembleWords, n_words);
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t off = (size_t)first * kEnsembleWords, bytes = n_words * sizeof(uint32_t);
+	HIP_TRY(hipMemcpyAsync(e->state + off, words, bytes, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipMemcpyAsync(e->prev + off, e->state + off, bytes, hipMemcpyDeviceToDevice, e->stream)); // the same words in both buffers, as ca3d_upload_state
+	// the records of the new states: step 0, no previous state
+	EnsembleLaunch l = launch_of(e);
+	l.first = first; l.count = count;
+	l.reset = true;
+	l.final = true;
+	HIP_TRY(launch_ensemble(l, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream)); // the caller's buffer is consumed when the call returns
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_state[u]) { e->has_state[u] = 1; e->missing_state--; }
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_read_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t *words, size_t n_words) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if (!words || n_words != (size_t)count * kEnsembleWords)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes hold %zu words (got %zu)", count, (size_t)count * kEnsembleWords, n_words);
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(hipMemcpyAsync(words, e->state + (size_t)first * kEnsembleWords, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_step(ca3d_ensemble_t *e, uint32_t n_steps) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	int rc = ensemble_ready(e);
+	if (rc) return rc;
+	e->last_steps = n_steps;
+	e->last_cell_steps = (double)n_steps * e->n * (double)(64 * 64 * 64);
+	e->last_launches = 0;
+	e->timed = false;
+	if (n_steps == 0) return CA3D_OK;
+	HIP_TRY(hipSetDevice(e->device));
+	return run(e, n_steps, 1u, 0u);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_step_until(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                             uint32_t *reason) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (check_every == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "check_every must be at least 1");
+	if (stop_mask & ~(uint32_t)(CA3D_STOP_EXTINCT | CA3D_STOP_STILL)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in stop_mask %#x", stop_mask);
+	int rc = ensemble_ready(e);
+	if (rc) return rc;
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t word_bytes = (size_t)e->n * sizeof(uint32_t);
+	std::vector<uint32_t> done(e->n, stop_mask ? 0u : max_steps), fired(e->n, 0u);
+	e->last_launches = 0;
+	e->timed = false;
+	if (stop_mask)
+	{
+		// the kernel keeps both arrays: a universe whose reason word is set leaves the later launches of this call at once
+		HIP_TRY(hipMemsetAsync(e->steps_done, 0, word_bytes, e->stream));
+		HIP_TRY(hipMemsetAsync(e->reason, 0, word_bytes, e->stream));
+		rc = run(e, max_steps, check_every, stop_mask); // max_steps == 0: one launch that only checks
+		if (rc) return rc;
+		HIP_TRY(hipMemcpyAsync(done.data(), e->steps_done, word_bytes, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(fired.data(), e->reason, word_bytes, hipMemcpyDeviceToHost, e->stream));
+	}
+	else if (max_steps)
+	{
+		rc = run(e, max_steps, 1u, 0u); // nothing to watch: plain stepping
+		if (rc) return rc;
+	}
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	uint64_t sum = 0, most = 0;
+	for (uint32_t d : done) { sum += d; most = d > most ? d : most; }
+	e->last_steps = most;
+	e->last_cell_steps = (double)sum * (double)(64 * 64 * 64);
+	if (steps_done) memcpy(steps_done, done.data(), word_bytes);
+	if (reason) memcpy(reason, fired.data(), word_bytes);
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_summarize(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_summary *out) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(hipMemcpyAsync(out, e->records + first, (size_t)count * sizeof(ca3d_summary), hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_synchronize(ca3d_ensemble_t *e) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, ca3d_stats *out) CA3D_API_TRY
+{
+	if (!e || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	*out = ca3d_stats{};
+	out->steps = e->last_steps;
+	out->kernel_launches = e->last_launches;
+	out->cell_steps = e->last_cell_steps;
+	out->algorithmic_bytes = 0.25 * e->last_cell_steps;
+	if (e->timed)
+	{
+		HIP_TRY(hipSetDevice(e->device));
+		HIP_TRY(hipEventSynchronize(e->ev_stop));
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, e->ev_start, e->ev_stop));
+		out->gpu_ms = ms;
+	}
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+} // extern "C"

@@ -195,6 +195,26 @@ struct SummaryLaunch
 	uint32_t z0, nz; // owned planes [z0, z0 + nz) of the grid
 };
 hipError_t launch_summary(const SummaryLaunch &l, hipStream_t stream);
+// ca_ensemble.hip: one launch over universes [first, first + count) of an ensemble of independent 64^3 grids, one workgroup each;
+// every array is indexed by universe (ca3d_ensemble.cpp owns them)
+constexpr uint32_t kEnsembleWords = 8192;      // words of one 64^3 universe
+constexpr uint32_t kEnsembleMaxSteps = 65536;  // steps of one launch at most: a call that wants more is cut into launches
+struct EnsembleLaunch
+{
+	uint32_t *state, *prev;   // [B][8192] current state / the state one step earlier
+	const uint32_t *rules;    // [B] von Neumann tables: lut_s | lut_b << 8 (7 bits each, vn_tables)
+	ca3d_summary *records;    // [B] what the last launch left of each universe
+	uint32_t *steps_done;     // [B] steps taken in the current step-until call (written when stop_mask != 0)
+	uint32_t *reason;         // [B] stop bits that fired in the current call; a universe whose word is set leaves at once
+	uint32_t first, count;
+	uint32_t steps;           // <= kEnsembleMaxSteps
+	uint32_t base;            // steps the earlier launches of the same call took
+	uint32_t check_every, stop_mask; // stop_mask 0: plain stepping, nothing is checked
+	bool final;               // the call ends with this launch: the conditions are checked after its last step whatever the count
+	bool reset;               // after an upload: records are rebuilt with step 0 and no previous state (steps == 0)
+};
+hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream);
+int ensemble_workgroups_per_cu(); // what the runtime says of ca_ensemble_vn64 (0: it cannot tell)
 // ca_diag.hip: float4 device-to-device copy (measurement only)
 hipError_t launch_copy_f4(const void *in, void *out, size_t bytes, hipStream_t stream);
 // ca_diag.hip: do two (idle) streams run side by side, i.e. sit on different hardware queues? (probe: ~2 ms)

@@ -1,0 +1,327 @@
+// Ensemble kernel behind ca3d_ensemble_* (include/ca3d.h): B independent 64^3 universes, ONE workgroup each, in one launch.
+//
+// A universe is stepped exactly as resident64_run (ca_resident_kernel.inc) steps the lone 64^3 grid: 1024 threads hold its 32 KiB in
+// eight registers each — lane = row y, wave w = planes 4 w .. 4 w + 3, a row's two words in one thread; x neighbours by v_alignbit,
+// y neighbours by wave-wide DPP, z neighbours through a double-buffered LDS exchange with one barrier per step; - faces dead, + faces
+// wrap. A workgroup waits for nobody outside itself, so a grid of B of them is B universes whatever part of it is resident at once.
+// What differs from the lone-grid kernel:
+//   * the RULE IS DATA. A universe's von Neumann table pair (7 + 7 bits) is read once per workgroup with a wave-uniform load and
+//     expanded into 14 registers of all-zeros / all-ones (`leaf`); a word's update is then a multiplexer tree of v_bitop3 selects over
+//     (alive, count planes 0, 1, 2): 7 selects on the alive word pick born / survive per count, 3 on plane 0, 2 on plane 1, 1 on
+//     plane 2 (count 7 does not exist, so count 6's leaf needs no select on plane 0) — 13 instructions where the compiled rule needs 1
+//     to 3, after the same 8 of the carry-save count and the same 4 neighbour shifts: 25 per word instead of ~12. No per-cell
+//     extraction, no LDS table, and every select has ONE operand that is not a plain register.
+//   * the SUMMARY comes out of the registers: at the end of a launch every workgroup reduces population, births / deaths against the
+//     state one step earlier (held in registers across the last step), digest and bounding box — registers -> wave -> LDS -> thread 0,
+//     which writes the universe's ca3d_summary with plain stores.
+//   * STOPPING is decided per universe in the kernel: on entry from the stored record, then every check_every steps from a workgroup
+//     reduction of two bits — any cell alive, any cell changed in the last step — at the price of one extra barrier per check. A
+//     universe whose condition holds writes its state and record and leaves; the CU takes the next workgroup.
+// There are no waits on other workgroups, no spins, and nothing but vector stores.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ca3d_internal.h"
+
+namespace ca3d
+{
+namespace
+{
+#include "ca_bitops.inc"
+#include "ca_digest.h"
+
+typedef unsigned long long u64;
+
+constexpr u32 kThreads = 1024, kWaves = 16, kPT = 4; // threads, waves, planes per wave
+
+struct EnsembleArgs
+{
+	u32 *state, *prev;
+	const u32 *rules;
+	ca3d_summary *records;
+	u32 *steps_done, *reason;
+	u32 first, steps, base;
+	u32 check_every, first_check, stop_mask; // first_check: steps of this launch before the call's next check point (0: on entry)
+	u32 final, reset;
+};
+
+__device__ __forceinline__ u32 mux(u32 sel, u32 one, u32 zero) { return next_state(sel, one, zero); } // sel ? one : zero, bit by bit
+
+template <typename T>
+__device__ __forceinline__ T wave_add(T v)
+{
+	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+	return v;
+}
+__device__ __forceinline__ u32 wave_or(u32 v)
+{
+	for (int o = 32; o > 0; o >>= 1) v |= (u32)__shfl_xor(v, o);
+	return v;
+}
+
+// Four waves per SIMD = up to 128 registers = one workgroup per CU: cut for 64 registers (two per CU) the step loop spills
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a)
+{
+	__shared__ u32 xch[2u * kWaves * 2u * 2u * 64u]; // [step parity][wave][first / last plane][word][row]: 32 KiB
+	__shared__ __attribute__((aligned(16))) u32 chk[kWaves]; // per wave: bit 0 a cell is alive, bit 1 a cell changed in the last step
+	__shared__ u64 red64[kWaves][2];
+	__shared__ u32 red32[kWaves][6];
+	const u32 u = a.first + blockIdx.x;
+	const u32 tid = threadIdx.x, row = tid & 63u;
+	const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+	if (a.stop_mask && a.reason[u]) return; // stopped in an earlier launch of the same call
+	auto slot = [&](u32 buf, u32 w, u32 which, u32 h) { return (((buf * kWaves + w) * 2u + which) * 2u + h) * 64u + row; };
+
+	// the rule: leaf[c] = all-ones where a DEAD cell with c live neighbours is born, leaf[7 + c] where a LIVE one survives
+	u32 leaf[14];
+	{
+		const u32 lut = a.rules[u];
+#pragma unroll
+		for (int c = 0; c < 7; c++)
+		{
+			leaf[c] = 0u - ((lut >> (8 + c)) & 1u);
+			leaf[7 + c] = 0u - ((lut >> c) & 1u);
+			asm volatile("" : "+v"(leaf[c]));     // in vector registers for the whole launch: a select reads one other operand at most
+			asm volatile("" : "+v"(leaf[7 + c]));
+		}
+	}
+	auto rule = [&](u32 w, u32 l, u32 r, u32 ym, u32 yp, u32 below, u32 above) {
+		u32 p[3];
+		sum6(l, r, ym, yp, below, above, p);
+		u32 t[7];
+#pragma unroll
+		for (int c = 0; c < 7; c++) t[c] = mux(w, leaf[7 + c], leaf[c]);
+		const u32 q0 = mux(p[0], t[1], t[0]), q1 = mux(p[0], t[3], t[2]), q2 = mux(p[0], t[5], t[4]);
+		return mux(p[2], mux(p[1], t[6], q2), mux(p[1], q1, q0));
+	};
+
+	u32 *mine = a.state + (size_t)u * kEnsembleWords;
+	// Two register sets that change roles every step: the one a step reads still holds the state one step earlier afterwards,
+	// which is what a check and the summary compare with — no copies.
+	u32 ra[kPT][2], rb[kPT][2];
+#pragma unroll
+	for (u32 p = 0; p < kPT; p++)
+	{
+		const uint2 v = *reinterpret_cast<const uint2 *>(mine + ((size_t)((wave * kPT + p) * 64u + row)) * 2u);
+		ra[p][0] = v.x; ra[p][1] = v.y;
+		rb[p][0] = 0u; rb[p][1] = 0u;
+	}
+	const ca3d_summary *rec = a.records + u;
+	const u64 step0 = a.reset ? 0ull : rec->step;
+
+	u32 t = 0, fired = 0, until = a.first_check;
+	// One round of the loop: the check that is due on the state in `s` (previous state in `o`), then one step from `s` into `o`.
+	// Returns true when the launch is over for this universe, the state in `s` and the one before it in `o`.
+	auto round = [&](const u32 (&s)[kPT][2], u32 (&o)[kPT][2]) __attribute__((always_inline)) -> bool {
+		if (a.stop_mask && (until == 0u || (t == a.steps && a.final)))
+		{
+			bool alive, changed, has_prev;
+			if (t == 0u)
+			{
+				// nothing stepped in this launch yet: the record describes the state
+				alive = rec->population != 0ull;
+				has_prev = !a.reset && rec->has_previous != 0u;
+				changed = rec->births + rec->deaths != 0ull;
+			}
+			else
+			{
+				u32 al = 0, ch = 0;
+#pragma unroll
+				for (u32 p = 0; p < kPT; p++)
+#pragma unroll
+					for (u32 h = 0; h < 2u; h++)
+					{
+						al |= s[p][h];
+						ch |= s[p][h] ^ o[p][h];
+					}
+				const u32 f = (__ballot(al != 0u) ? 1u : 0u) | (__ballot(ch != 0u) ? 2u : 0u);
+				// (chk is rewritten at the next check at the earliest: a step — and its barrier — lies in between)
+				if (row == 0u) chk[wave] = f;
+				__syncthreads();
+				const uint4 *c4 = reinterpret_cast<const uint4 *>(chk);
+				uint4 m = c4[0];
+#pragma unroll
+				for (int i = 1; i < (int)kWaves / 4; i++) { const uint4 n = c4[i]; m.x |= n.x; m.y |= n.y; m.z |= n.z; m.w |= n.w; }
+				const u32 all = (u32)__builtin_amdgcn_readfirstlane((int)(m.x | m.y | m.z | m.w));
+				alive = (all & 1u) != 0u;
+				changed = (all & 2u) != 0u;
+				has_prev = true;
+			}
+			fired = ((alive ? 0u : (u32)CA3D_STOP_EXTINCT) | (has_prev && !changed ? (u32)CA3D_STOP_STILL : 0u)) & a.stop_mask;
+			if (fired) return true;
+			until = a.check_every;
+		}
+		if (t == a.steps) return true;
+
+		// ---- one step (resident64_run's, with the rule as data)
+		const u32 buf = t & 1u;
+		xch[slot(buf, wave, 0u, 0u)] = s[0][0];
+		xch[slot(buf, wave, 0u, 1u)] = s[0][1];
+		xch[slot(buf, wave, 1u, 0u)] = s[kPT - 1][0];
+		xch[slot(buf, wave, 1u, 1u)] = s[kPT - 1][1];
+		auto plane = [&](u32 p, const u32 (&bl)[2], const u32 (&ab)[2]) {
+#pragma unroll
+			for (u32 h = 0; h < 2u; h++)
+			{
+				const u32 w = s[p][h], other = s[p][h ^ 1u];
+				const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
+				const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
+				const u32 ym = dpp_mov<kDppWaveShr1>(w);    // row y - 1 (zero into row 0)
+				const u32 yp = dpp_mov<kDppWaveRol1>(w);    // row y + 1 (row 0 into row 63)
+				o[p][h] = rule(w, l, r, ym, yp, bl[h], ab[h]);
+			}
+		};
+		// the planes that need nothing from another wave first, under the exchange's LDS writes and the other waves' way to the barrier
+#pragma unroll
+		for (u32 p = 1; p + 1u < kPT; p++) plane(p, s[p - 1], s[p + 1]);
+		__syncthreads();
+		u32 below[2], above[2];
+#pragma unroll
+		for (u32 h = 0; h < 2u; h++)
+		{
+			below[h] = wave ? xch[slot(buf, wave - 1u, 1u, h)] : 0u;       // z == -1 is dead
+			above[h] = xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h)]; // z == 64 is plane 0
+		}
+		plane(0u, below, s[1]);
+		plane(kPT - 1u, s[kPT - 2], above);
+		t++;
+		until--;
+		return false;
+	};
+	u32 s[kPT][2], q[kPT][2]; // when the loop is over: the state; the state one step earlier
+	auto leave = [&](const u32 (&cur)[kPT][2], const u32 (&old)[kPT][2]) __attribute__((always_inline)) {
+#pragma unroll
+		for (u32 p = 0; p < kPT; p++)
+#pragma unroll
+			for (u32 h = 0; h < 2u; h++) { s[p][h] = cur[p][h]; q[p][h] = old[p][h]; }
+	};
+	for (;;)
+	{
+		if (round(ra, rb)) { leave(ra, rb); break; }
+		if (round(rb, ra)) { leave(rb, ra); break; }
+	}
+
+	if (a.stop_mask && tid == 0u)
+	{
+		a.steps_done[u] = a.base + t;
+		a.reason[u] = fired;
+	}
+	if (t == 0u && !a.reset) return; // nothing moved: state and record stand
+
+	// ---- the record, from the registers
+	const bool hp = t != 0u;
+	u32 pop = 0, births = 0, deaths = 0, o0 = 0, o1 = 0, zbits = 0;
+	u64 dig = 0;
+#pragma unroll
+	for (u32 p = 0; p < kPT; p++)
+	{
+#pragma unroll
+		for (u32 h = 0; h < 2u; h++)
+		{
+			const u32 w = s[p][h], was = q[p][h];
+			pop += (u32)__popc(w);
+			if (hp)
+			{
+				births += (u32)__popc(w & ~was);
+				deaths += (u32)__popc(was & ~w);
+			}
+			// digest index = the word's index in the universe's own 64^3 array
+			if (w) dig += digest_mix((u64)(((wave * kPT + p) * 64u + row) * 2u + h), w);
+		}
+		o0 |= s[p][0];
+		o1 |= s[p][1];
+		if (__ballot((s[p][0] | s[p][1]) != 0u)) zbits |= 1u << p;
+	}
+	const u64 ymask = __ballot((o0 | o1) != 0u); // bit y: row y of one of the wave's planes holds a live cell
+	pop = wave_add(pop); births = wave_add(births); deaths = wave_add(deaths); dig = wave_add(dig);
+	o0 = wave_or(o0); o1 = wave_or(o1);
+	__syncthreads(); // (a check may have read chk just now; the arrays below are separate, this orders the launch's last LDS traffic all the same)
+	if (row == 0u)
+	{
+		red64[wave][0] = dig; red64[wave][1] = ymask;
+		red32[wave][0] = pop; red32[wave][1] = births; red32[wave][2] = deaths;
+		red32[wave][3] = o0; red32[wave][4] = o1; red32[wave][5] = zbits;
+	}
+	__syncthreads();
+	if (tid == 0u)
+	{
+		u64 d = 0, ym = 0, zm = 0;
+		u32 r[5] = {0, 0, 0, 0, 0};
+#pragma nounroll
+		for (u32 w = 0; w < kWaves; w++)
+		{
+			d += red64[w][0];
+			ym |= red64[w][1];
+			zm |= (u64)red32[w][5] << (w * kPT);
+			for (int i = 0; i < 3; i++) r[i] += red32[w][i];
+			r[3] |= red32[w][3];
+			r[4] |= red32[w][4];
+		}
+		ca3d_summary o;
+		o.step = step0 + t;
+		o.population = r[0];
+		o.births = r[1];
+		o.deaths = r[2];
+		o.digest = d;
+		o.has_previous = hp ? 1u : 0u;
+		if (r[0])
+		{
+			o.box_min[0] = r[3] ? (u32)__builtin_ctz(r[3]) : 32u + (u32)__builtin_ctz(r[4]);
+			o.box_max[0] = r[4] ? 63u - (u32)__builtin_clz(r[4]) : 31u - (u32)__builtin_clz(r[3]);
+			o.box_min[1] = (u32)__builtin_ctzll(ym);
+			o.box_max[1] = 63u - (u32)__builtin_clzll(ym);
+			o.box_min[2] = (u32)__builtin_ctzll(zm);
+			o.box_max[2] = 63u - (u32)__builtin_clzll(zm);
+		}
+		else
+		{
+			for (int i = 0; i < 3; i++) { o.box_min[i] = 64u; o.box_max[i] = 0u; }
+		}
+		a.records[u] = o;
+	}
+	if (!hp) return; // a record rebuilt after an upload: the state is where the host put it
+
+	// every word of the universe was read into registers before the first barrier: writing in place is safe
+	u32 *old = a.prev + (size_t)u * kEnsembleWords;
+#pragma unroll
+	for (u32 p = 0; p < kPT; p++)
+	{
+		const size_t i = ((size_t)((wave * kPT + p) * 64u + row)) * 2u;
+		*reinterpret_cast<uint2 *>(mine + i) = make_uint2(s[p][0], s[p][1]);
+		*reinterpret_cast<uint2 *>(old + i) = make_uint2(q[p][0], q[p][1]);
+	}
+}
+
+} // namespace
+
+hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
+{
+	if (l.count == 0 || l.steps > kEnsembleMaxSteps || (l.stop_mask && l.check_every == 0)) return hipErrorInvalidValue;
+	EnsembleArgs a;
+	a.state = l.state; a.prev = l.prev;
+	a.rules = l.rules;
+	a.records = l.records;
+	a.steps_done = l.steps_done; a.reason = l.reason;
+	a.first = l.first; a.steps = l.steps; a.base = l.base;
+	a.check_every = l.check_every;
+	a.stop_mask = l.stop_mask;
+	const uint32_t into = l.stop_mask ? l.base % l.check_every : 0u; // steps since the call's last check point
+	a.first_check = into ? l.check_every - into : 0u;
+	a.final = l.final ? 1u : 0u;
+	a.reset = l.reset ? 1u : 0u;
+	hipLaunchKernelGGL(ca_ensemble_vn64, dim3(l.count), dim3(kThreads), 0, stream, a);
+	return hipGetLastError();
+}
+
+int ensemble_workgroups_per_cu()
+{
+	int per_cu = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)ca_ensemble_vn64, (int)kThreads, 0) != hipSuccess)
+	{
+		(void)hipGetLastError();
+		return 0;
+	}
+	return per_cu;
+}
+
+} // namespace ca3d

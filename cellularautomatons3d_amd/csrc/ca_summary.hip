@@ -40,14 +40,7 @@ struct SummaryArgs
 	u32 z0;
 };
 
-// splitmix64 finaliser of (word index << 32 | word): include/ca3d.h, "digest"
-__device__ __forceinline__ u64 digest_mix(u64 index, u32 w)
-{
-	u64 z = ((index << 32) | (u64)w) + 0x9E3779B97F4A7C15ull;
-	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-	z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-	return z ^ (z >> 31);
-}
+#include "ca_digest.h"
 
 __device__ __forceinline__ u32 wave_sum(u32 v)
 {

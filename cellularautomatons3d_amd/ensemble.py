@@ -1,0 +1,108 @@
+"""`Ensemble`: many independent 64^3 universes stepped side by side by one kernel launch (`ca3d_ensemble_*`, include/ca3d.h).
+
+Every universe has its own von Neumann rule, its own step counter, its own summary record and — in `step_until` — its own moment
+to stop. No reference counterpart: its UI runs one grid.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from . import _capi, host
+from ._capi import ENSEMBLE_ALL, ENSEMBLE_WORDS, Stats
+from .engine import STOP_EXTINCT, STOP_STILL, Summary, _as_i32, _as_u32, _summary
+
+_u32p = C.POINTER(C.c_uint32)
+_i32p = C.POINTER(C.c_int32)
+
+ALL = ENSEMBLE_ALL
+
+
+class Ensemble:
+    """One ensemble = one GPU, one HIP stream, `n` universes of 64^3 cells (8192 packed words each)."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _capi.load()
+        h = C.c_void_p()
+        _capi.check(self._lib.ca3d_ensemble_create(int(device), C.byref(h)))
+        self._h = h
+        self.n = 0
+        self.grid_size = 0
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.ca3d_ensemble_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def configure(self, n: int, grid_size: int = 64) -> None:
+        _capi.check(self._lib.ca3d_ensemble_configure(self._h, grid_size, n))
+        self.n, self.grid_size = n, grid_size
+
+    def set_rules(self, u: int, main_offsets, edges_offsets, corners_offsets, survive, born) -> None:
+        """The payload of `Engine.set_rules` for universe `u` (`ensemble.ALL`: every universe)."""
+        m, e, c = _as_i32(main_offsets), _as_i32(edges_offsets), _as_i32(corners_offsets)
+        s, b = _as_u32(survive), _as_u32(born)
+        if s.size != _capi.LUT_LEN or b.size != _capi.LUT_LEN:
+            raise ValueError("survive/born must hold 81 entries")
+        _capi.check(self._lib.ca3d_ensemble_set_rules(
+            self._h, u, m.ctypes.data_as(_i32p), m.size, e.ctypes.data_as(_i32p), e.size,
+            c.ctypes.data_as(_i32p), c.size, s.ctypes.data_as(_u32p), b.ctypes.data_as(_u32p)))
+
+    def set_rule_strings(self, u: int, born: str = host.DEFAULTS["bornRulesString"], survive: str = host.DEFAULTS["surviveRulesString"],
+                         neighbourhood: str = "von neumann", born_edges: str = "27", survive_edges: str = "27",
+                         born_corners: str = "27", survive_corners: str = "27") -> None:
+        b, s = host.recalculate_rules_values(born, survive, born_edges, survive_edges, born_corners, survive_corners)
+        self.set_rules(u, host.NEIGHBOURHOOD_MAP[neighbourhood], host.NEIGHBOURHOOD_MAP["edges"], host.NEIGHBOURHOOD_MAP["corners"], s, b)
+
+    def upload_state(self, first: int, words) -> None:
+        """`words`: [count, 8192] (or flat): the states of universes first .. first + count - 1."""
+        w = _as_u32(words).ravel()
+        if w.size == 0 or w.size % ENSEMBLE_WORDS:
+            raise ValueError("a universe holds 8192 words")
+        _capi.check(self._lib.ca3d_ensemble_upload_state(self._h, first, w.size // ENSEMBLE_WORDS, w.ctypes.data_as(_u32p), w.size))
+
+    def read_state(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        count = self.n - first if count is None else count
+        out = np.empty((count, ENSEMBLE_WORDS), dtype=np.uint32)
+        _capi.check(self._lib.ca3d_ensemble_read_state(self._h, first, count, out.ctypes.data_as(_u32p), out.size))
+        return out
+
+    def step(self, n_steps: int = 1) -> None:
+        """Every universe, unconditionally; asynchronous."""
+        _capi.check(self._lib.ca3d_ensemble_step(self._h, n_steps))
+
+    def step_until(self, max_steps: int, check_every: int = 8, stop_mask: int = STOP_EXTINCT | STOP_STILL) -> Tuple[np.ndarray, np.ndarray]:
+        """`Engine.step_until` per universe, decided inside the kernel -> (steps_done u32[n], reason u32[n])."""
+        done, reason = np.empty(self.n, dtype=np.uint32), np.empty(self.n, dtype=np.uint32)
+        _capi.check(self._lib.ca3d_ensemble_step_until(self._h, max_steps, check_every, stop_mask, done.ctypes.data_as(_u32p),
+                                                       reason.ctypes.data_as(_u32p)))
+        return done, reason
+
+    def summaries(self, first: int = 0, count: Optional[int] = None) -> List[Summary]:
+        """The universes' records (no per-plane counts): copied, not computed — every launch leaves them up to date."""
+        count = self.n - first if count is None else count
+        recs = (_capi.SummaryStruct * count)()
+        _capi.check(self._lib.ca3d_ensemble_summarize(self._h, first, count, recs))
+        return [_summary(r, None) for r in recs]
+
+    def synchronize(self) -> None:
+        _capi.check(self._lib.ca3d_ensemble_synchronize(self._h))
+
+    def stats(self) -> Stats:
+        s = Stats()
+        _capi.check(self._lib.ca3d_ensemble_get_stats(self._h, C.byref(s)))
+        return s

@@ -930,6 +930,209 @@ static napi_value js_group_render(napi_env env, napi_callback_info info)
 	return rc ? throw_ca3d(env, rc) : undefined(env);
 }
 
+/*
+ * ca3d_ensemble_*: many independent 64^3 universes in one launch (include/ca3d.h). Synchronous and 1:1, like the group calls.
+ */
+typedef struct
+{
+	ca3d_ensemble_t *e;
+	uint32_t n; /* universes, as last configured: what the arrays of ensembleStepUntil must hold */
+} EnsembleSlot;
+
+static void finalize_ensemble(napi_env env, void *data, void *hint)
+{
+	(void)env;
+	(void)hint;
+	EnsembleSlot *slot = (EnsembleSlot *)data;
+	if (slot->e) ca3d_ensemble_destroy(slot->e);
+	free(slot);
+}
+
+static ca3d_ensemble_t *get_ensemble(napi_env env, napi_value v)
+{
+	void *p = NULL;
+	if (napi_get_value_external(env, v, &p) != napi_ok || !p || !((EnsembleSlot *)p)->e)
+	{
+		napi_throw_type_error(env, NULL, "expected an ensemble handle");
+		return NULL;
+	}
+	return ((EnsembleSlot *)p)->e;
+}
+
+static napi_value js_ensemble_create(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	int32_t device = 0;
+	napi_get_value_int32(env, argv[0], &device);
+	ca3d_ensemble_t *e = NULL;
+	int rc = ca3d_ensemble_create(device, &e);
+	if (rc) return throw_ca3d(env, rc);
+	EnsembleSlot *slot = (EnsembleSlot *)calloc(1, sizeof *slot);
+	if (!slot) { ca3d_ensemble_destroy(e); napi_throw_error(env, NULL, "out of memory"); return NULL; }
+	slot->e = e;
+	napi_value ext;
+	NAPI_OK_OR_NULL(napi_create_external(env, slot, finalize_ensemble, NULL, &ext));
+	return ext;
+}
+
+static napi_value js_ensemble_destroy(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	void *p = NULL;
+	if (napi_get_value_external(env, argv[0], &p) == napi_ok && p)
+	{
+		EnsembleSlot *slot = (EnsembleSlot *)p;
+		if (slot->e) ca3d_ensemble_destroy(slot->e);
+		slot->e = NULL;
+	}
+	return undefined(env);
+}
+
+static napi_value js_ensemble_configure(napi_env env, napi_callback_info info)
+{
+	napi_value argv[3];
+	if (!get_args(env, info, 3, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t grid, n;
+	if (!e || !get_u32(env, argv[1], &grid) || !get_u32(env, argv[2], &n)) return NULL;
+	int rc = ca3d_ensemble_configure(e, grid, n);
+	if (rc) return throw_ca3d(env, rc);
+	void *p = NULL;
+	napi_get_value_external(env, argv[0], &p);
+	((EnsembleSlot *)p)->n = n;
+	return undefined(env);
+}
+
+/* ensembleSetRules(handle, universe | 0xFFFFFFFF, main, edges, corners, survive, born) */
+static napi_value js_ensemble_set_rules(napi_env env, napi_callback_info info)
+{
+	napi_value argv[7];
+	if (!get_args(env, info, 7, argv)) return NULL;
+	ca3d_ensemble_t *en = get_ensemble(env, argv[0]);
+	uint32_t u;
+	if (!en || !get_u32(env, argv[1], &u)) return NULL;
+	void *m, *e, *c, *s, *b;
+	size_t nm, ne, nc, ns, nb;
+	if (!get_typed(env, argv[2], napi_int32_array, 0, &m, &nm) || !get_typed(env, argv[3], napi_int32_array, 0, &e, &ne) ||
+	    !get_typed(env, argv[4], napi_int32_array, 0, &c, &nc) || !get_typed(env, argv[5], napi_uint32_array, 0, &s, &ns) ||
+	    !get_typed(env, argv[6], napi_uint32_array, 0, &b, &nb))
+		return NULL;
+	if (ns != CA3D_LUT_LEN || nb != CA3D_LUT_LEN)
+	{
+		napi_throw_range_error(env, NULL, "survive/born must be Uint32Array(81)");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_set_rules(en, u, (const int32_t *)m, (uint32_t)nm, (const int32_t *)e, (uint32_t)ne, (const int32_t *)c, (uint32_t)nc,
+	                                 (const uint32_t *)s, (const uint32_t *)b);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+/* ensembleUploadState / ensembleReadState(handle, first, Uint32Array(count * 8192)) */
+static napi_value ensemble_transfer(napi_env env, napi_callback_info info, int upload)
+{
+	napi_value argv[3];
+	if (!get_args(env, info, 3, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first;
+	void *w;
+	size_t n;
+	if (!e || !get_u32(env, argv[1], &first) || !get_typed(env, argv[2], napi_uint32_array, 0, &w, &n)) return NULL;
+	if (n == 0 || n % 8192u)
+	{
+		napi_throw_range_error(env, NULL, "a universe holds 8192 words");
+		return NULL;
+	}
+	int rc = upload ? ca3d_ensemble_upload_state(e, first, (uint32_t)(n / 8192u), (const uint32_t *)w, n)
+	                : ca3d_ensemble_read_state(e, first, (uint32_t)(n / 8192u), (uint32_t *)w, n);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+static napi_value js_ensemble_upload_state(napi_env env, napi_callback_info info) { return ensemble_transfer(env, info, 1); }
+static napi_value js_ensemble_read_state(napi_env env, napi_callback_info info) { return ensemble_transfer(env, info, 0); }
+
+static napi_value js_ensemble_step(napi_env env, napi_callback_info info)
+{
+	napi_value argv[2];
+	if (!get_args(env, info, 2, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t n;
+	if (!e || !get_u32(env, argv[1], &n)) return NULL;
+	int rc = ca3d_ensemble_step(e, n);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+/* ensembleStepUntil(handle, maxSteps, checkEvery, stopMask, Uint32Array(n) stepsDone, Uint32Array(n) reason) */
+static napi_value js_ensemble_step_until(napi_env env, napi_callback_info info)
+{
+	napi_value argv[6];
+	if (!get_args(env, info, 6, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t max_steps, every, mask;
+	void *done, *reason;
+	size_t nd, nr;
+	if (!e || !get_u32(env, argv[1], &max_steps) || !get_u32(env, argv[2], &every) || !get_u32(env, argv[3], &mask) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 0, &done, &nd) || !get_typed(env, argv[5], napi_uint32_array, 0, &reason, &nr))
+		return NULL;
+	void *p = NULL;
+	napi_get_value_external(env, argv[0], &p);
+	if (nd != ((EnsembleSlot *)p)->n || nr != nd)
+	{
+		napi_throw_range_error(env, NULL, "stepsDone and reason must hold one entry per universe");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_step_until(e, max_steps, every, mask, (uint32_t *)done, (uint32_t *)reason);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+/* ensembleSummaries(handle, first, count) -> [summary object, ...] */
+static napi_value js_ensemble_summaries(napi_env env, napi_callback_info info)
+{
+	napi_value argv[3];
+	if (!get_args(env, info, 3, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, count;
+	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count)) return NULL;
+	ca3d_summary *recs = (ca3d_summary *)calloc(count ? count : 1u, sizeof *recs);
+	if (!recs) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+	int rc = ca3d_ensemble_summarize(e, first, count, recs);
+	if (rc) { free(recs); return throw_ca3d(env, rc); }
+	napi_value out;
+	napi_create_array_with_length(env, count, &out);
+	for (uint32_t i = 0; i < count; i++) napi_set_element(env, out, i, summary_object(env, &recs[i], NULL));
+	free(recs);
+	return out;
+}
+
+static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	if (!e) return NULL;
+	int rc = ca3d_ensemble_synchronize(e);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+static napi_value js_ensemble_stats(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	if (!e) return NULL;
+	ca3d_stats st;
+	int rc = ca3d_ensemble_get_stats(e, &st);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value o;
+	napi_create_object(env, &o);
+	set_num(env, o, "steps", (double)st.steps);
+	set_num(env, o, "kernelLaunches", (double)st.kernel_launches);
+	set_num(env, o, "gpuMs", st.gpu_ms);
+	set_num(env, o, "cellSteps", st.cell_steps);
+	set_num(env, o, "algorithmicBytes", st.algorithmic_bytes);
+	return o;
+}
+
 static napi_value js_recovered_launches(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -987,7 +1190,11 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"groupUploadState", js_group_upload_state}, {"groupReadState", js_group_read_state}, {"groupStep", js_group_step},
 	    {"groupSynchronize", js_group_synchronize}, {"groupSetOption", js_group_set_option}, {"groupInfo", js_group_info}, {"groupRender", js_group_render},
 	    {"readStateAsync", js_read_state_async}, {"renderAsync", js_render_async}, {"synchronizeAsync", js_synchronize_async},
-	    {"summary", js_summary}, {"groupSummary", js_group_summary}, {"stepUntilAsync", js_step_until_async}};
+	    {"summary", js_summary}, {"groupSummary", js_group_summary}, {"stepUntilAsync", js_step_until_async},
+	    {"ensembleCreate", js_ensemble_create}, {"ensembleDestroy", js_ensemble_destroy}, {"ensembleConfigure", js_ensemble_configure},
+	    {"ensembleSetRules", js_ensemble_set_rules}, {"ensembleUploadState", js_ensemble_upload_state}, {"ensembleReadState", js_ensemble_read_state},
+	    {"ensembleStep", js_ensemble_step}, {"ensembleStepUntil", js_ensemble_step_until}, {"ensembleSummaries", js_ensemble_summaries},
+	    {"ensembleSynchronize", js_ensemble_synchronize}, {"ensembleStats", js_ensemble_stats}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

@@ -338,8 +338,53 @@ class EngineGroup
 	}
 }
 
+// ca3d_ensemble_*: `n` independent 64^3 universes (8192 packed words each) stepped side by side by one kernel launch, each with its
+// own von Neumann rule, step counter, summary record and — in stepUntil — its own moment to stop (include/ca3d.h). Synchronous.
+const ENSEMBLE_ALL = 0xFFFFFFFF, ENSEMBLE_WORDS = 8192;
+class Ensemble
+{
+	constructor(device)
+	{
+		this._a = loadAddon();
+		this._e = this._a.ensembleCreate(device || 0);
+		this.n = 0;
+	}
+	close() { if (this._e) { this._a.ensembleDestroy(this._e); this._e = null; } }
+	configure(n, gridSize) { this._a.ensembleConfigure(this._e, gridSize === undefined ? 64 : gridSize, n); this.n = n; }
+	/** universe: an index, or ENSEMBLE_ALL */
+	setRules(universe, mainOffsets, edgesOffsets, cornersOffsets, survive, born) { this._a.ensembleSetRules(this._e, universe, mainOffsets, edgesOffsets, cornersOffsets, survive, born); }
+	setRuleStrings(universe, rules)
+	{
+		const r = Object.assign({}, DEFAULT_RULES, rules || {});
+		const lut = recalculateRulesValues(r);
+		this.setRules(universe, NEIGHBOURHOOD_MAP[r.neighbourhood], NEIGHBOURHOOD_MAP["edges"], NEIGHBOURHOOD_MAP["corners"], lut.survive, lut.born);
+	}
+	/** words: Uint32Array(count * 8192), the states of universes first .. first + count - 1 */
+	uploadState(first, words) { this._a.ensembleUploadState(this._e, first, words); }
+	readState(first, count)
+	{
+		first = first || 0;
+		const out = new Uint32Array((count === undefined ? this.n - first : count) * ENSEMBLE_WORDS);
+		this._a.ensembleReadState(this._e, first, out);
+		return out;
+	}
+	step(n) { this._a.ensembleStep(this._e, n === undefined ? 1 : n); }
+	/** -> {stepsDone: Uint32Array(n), reason: Uint32Array(n)} (STOP_EXTINCT | STOP_STILL bits; 0: maxSteps reached) */
+	stepUntil(maxSteps, opts)
+	{
+		const o = Object.assign({ checkEvery: 8, stopMask: STOP_EXTINCT | STOP_STILL }, opts || {});
+		const stepsDone = new Uint32Array(this.n), reason = new Uint32Array(this.n);
+		this._a.ensembleStepUntil(this._e, maxSteps, o.checkEvery, o.stopMask, stepsDone, reason);
+		return { stepsDone, reason };
+	}
+	/** the universes' records, as Engine.summary() objects without planePopulation */
+	summaries(first, count) { first = first || 0; return this._a.ensembleSummaries(this._e, first, count === undefined ? this.n - first : count); }
+	synchronize() { this._a.ensembleSynchronize(this._e); }
+	stats() { return this._a.ensembleStats(this._e); }
+}
+
 module.exports = {
-	Engine, EngineGroup, STOP_EXTINCT, STOP_STILL, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
+	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
 	initialState, dispatchShape, randomFill, loadAddon, saveCheckpoint, loadCheckpoint
 };

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time */
+#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_* */
 #define CA3D_LUT_LEN 81 /* 3 rule-sets x 27 slots (main_pathtraced.js:10, 155-159) */
 
 typedef struct ca3d_engine ca3d_t;
@@ -306,6 +306,55 @@ enum
 };
 int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, ca3d_summary *out, uint32_t *steps_done,
                     uint32_t *reason);
+
+/*
+ * Ensemble: B independent 64^3 universes on one device, stepped side by side by ONE kernel launch (no reference counterpart: its UI
+ * runs one grid). For hosts that ask "what becomes of this rule / seed?" of thousands of pairs: one ca3d_t steps one universe on one
+ * CU of 256 and pays a launch, a rule set-up and a summary pass per universe; here one workgroup holds one universe in its registers
+ * (the layout of the engine's own 64^3 resident kernel), a launch is B such workgroups, and every universe has
+ *   - its own RULE, as data: the payload of ca3d_set_rules, canonicalised as there, which must reduce to a von Neumann table pair —
+ *     main list von Neumann, edges / corners tables that cannot fire; anything else is refused with CA3D_ERR_UNSUPPORTED and a message
+ *     that names the universe. Moore and clustered rules as data are out of scope here (a ca3d_t compiles them at run time);
+ *   - its own ca3d_summary RECORD, reduced from the registers at the end of every launch: ca3d_ensemble_summarize only copies records
+ *     (nothing state-sized moves). Field meanings as above with G = 64; `step` counts the universe's own steps since its last upload,
+ *     has_previous is 1 once it has taken one, and the digest's word index is the index in the universe's own array, so a record
+ *     equals ca3d_summarize's of a lone engine holding the same universe. No per-plane counts;
+ *   - its own END in ca3d_ensemble_step_until, decided inside the kernel: ca3d_step_until's semantics per universe — conditions
+ *     checked on entry and after every check_every steps (and after max_steps), steps_done[u] a multiple of check_every or max_steps,
+ *     reason[u] the bits of stop_mask that fired (0: max_steps reached), the state of universe u afterwards bit for bit the state
+ *     after steps_done[u] plain steps. A universe that stops stops costing anything; its workgroup's CU takes the next universe.
+ *     Returns when both arrays (B entries each, nullable) are on the host.
+ * grid_size: 64 only, anything else CA3D_ERR_UNSUPPORTED. Call order as for an engine: configure -> set_rules (every universe; universe
+ * == CA3D_ENSEMBLE_ALL sets all at once) -> upload_state (every universe) -> step; otherwise CA3D_ERR_NOT_CONFIGURED. Universes are
+ * 8192 words each in the engine's PACKED32 layout, `count` of them back to back from universe `first`. An upload resets the uploaded
+ * universes' step counters and has_previous. ca3d_ensemble_step steps every universe unconditionally and is asynchronous; calls of any
+ * length are cut into launches of at most 65 536 steps. ca3d_ensemble_get_stats describes the last step / step_until call: hipEvent
+ * time, launches, steps = the most any universe took, cell_steps = the sum over the universes of the steps each actually took x 64^3.
+ * A launch holds the CUs it runs on for up to its whole length: an engine of the same process whose resident multi-step launch needs the
+ * whole chip at once ("resident", 512^3 / 256^3) should not run beside one — it would wait, and past "resident_timeout_us" recover
+ * through its per-step kernels (ca3d_recovered_launches).
+ * One ensemble owns one HIP stream; calls on one handle are not thread-safe. Without a gfx950 device ca3d_ensemble_create fails with
+ * CA3D_ERR_DEVICE (there is no CPU fallback); a NULL handle gives CA3D_ERR_INVALID_ARGUMENT without touching a device.
+ */
+typedef struct ca3d_ensemble ca3d_ensemble_t;
+struct ca3d_stats;
+#define CA3D_ENSEMBLE_ALL 0xFFFFFFFFu
+int ca3d_ensemble_create(int device, ca3d_ensemble_t **out);
+int ca3d_ensemble_destroy(ca3d_ensemble_t *e);
+int ca3d_ensemble_configure(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes);
+int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe,
+                            const int32_t *main_offsets, uint32_t n_main,
+                            const int32_t *edges_offsets, uint32_t n_edges,
+                            const int32_t *corners_offsets, uint32_t n_corners,
+                            const uint32_t survive[CA3D_LUT_LEN], const uint32_t born[CA3D_LUT_LEN]);
+int ca3d_ensemble_upload_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *words, size_t n_words);
+int ca3d_ensemble_read_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t *words, size_t n_words);
+int ca3d_ensemble_step(ca3d_ensemble_t *e, uint32_t n_steps);
+int ca3d_ensemble_step_until(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                             uint32_t *reason);
+int ca3d_ensemble_summarize(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_summary *out);
+int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
+int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 
 /* Resident launches that gave up (a wait for neighbour tile faces timed out: not all workgroups were on the chip) and
  * whose steps the engine re-ran through the per-step kernels, since ca3d_create. The calls that noticed returned CA3D_OK

@@ -1,0 +1,141 @@
+"""Ensemble against the path that existed before it: B universes of 64^3 in ONE launch of ca_ensemble_vn64 (Ensemble.step) vs. the same
+universes stepped one after another through one Engine at 64^3 (Engine.step: the resident one-workgroup kernel compiled for the rule).
+
+For B = 1, 256, 1024, 4096 and 256 steps per launch (random fills, rule B2,4 / S1,3,5, which never settles): microseconds per launch,
+universe-steps per second, Tcells per second, for both paths and their ratio. Same machine, same process, the two paths alternating,
+after the final states of both have been compared. The baseline is timed at its best: B back-to-back step(256) calls on an engine that
+already holds a state, one synchronisation at the end — no upload, no summary and no read-back per universe, all of which a real sweep
+through one engine would pay on top.
+
+    python tools/bench_ensemble.py --out profiles/ensemble_64.json --commit <hash>
+
+Needs an MI355X; without one the engines cannot be created and the tool fails.
+"""
+import argparse
+import datetime
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from cellularautomatons3d_amd import Engine, Ensemble, _capi, host  # noqa: E402
+
+G, W, CELLS = 64, 8192, 64 ** 3
+BORN, SURVIVE = "2,4", "1,3,5"
+
+
+def fills(B):
+    return np.stack([host.random_fill(W, seed=1 + u) for u in range(B)])
+
+
+def verify(ens, eng, words, steps, sample):
+    """Final states of the ensemble against the engine's, universe by universe (the engine itself is checked against the CPU oracle
+    by the test suite)."""
+    ens.upload_state(0, words)
+    ens.step(steps)
+    got = ens.read_state()
+    for u in sample:
+        eng.upload_state(words[u])
+        eng.step(steps)
+        if not np.array_equal(got[u], eng.read_state()):
+            raise SystemExit(f"universe {u}: the ensemble and the engine disagree after {steps} steps")
+
+
+def timed(fn, sync, min_seconds):
+    """Seconds per call of fn: enough calls for min_seconds of work, one synchronisation at the end."""
+    fn(); sync()
+    t0 = time.perf_counter(); fn(); sync()
+    once = time.perf_counter() - t0
+    reps = max(1, int(min_seconds / max(once, 1e-6)))
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    sync()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--universes", type=int, nargs="+", default=[1, 256, 1024, 4096])
+    ap.add_argument("--steps", type=int, default=256, help="steps per launch")
+    ap.add_argument("--repeats", type=int, default=5, help="alternating measurements per path; the median is reported")
+    ap.add_argument("--min-seconds", type=float, default=0.25, help="work per measurement")
+    ap.add_argument("--out", default=None, help="JSON file to write")
+    ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
+    args = ap.parse_args()
+    commit = args.commit
+    if commit is None:
+        try:
+            commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
+        except Exception:
+            commit = "unknown"
+
+    eng, ens = Engine(0), Ensemble(0)
+    eng.configure(G)
+    eng.set_rule_strings(born=BORN, survive=SURVIVE)
+    eng.set_option("stats", 0)  # no event pair per call: the baseline at its best
+    rows = []
+    for B in args.universes:
+        words = fills(B)
+        ens.configure(B)
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, born=BORN, survive=SURVIVE)
+        sample = range(B) if B <= 256 else sorted(set(range(0, B, max(1, B // 64))) | {255, 256, B - 1})
+        verify(ens, eng, words, args.steps, sample)
+        eng.upload_state(words[0])
+
+        def ensemble_launch():
+            ens.step(args.steps)
+
+        def engine_sweep():
+            for _ in range(B):
+                eng.step(args.steps)
+
+        te, tb = [], []
+        for _ in range(args.repeats):
+            te.append(timed(ensemble_launch, ens.synchronize, args.min_seconds))
+            tb.append(timed(engine_sweep, eng.synchronize, args.min_seconds))
+        ens.step(args.steps)
+        event_ms = ens.stats().gpu_ms
+        e, b = statistics.median(te), statistics.median(tb)
+        row = {
+            "universes": B, "steps_per_launch": args.steps,
+            "ensemble": {"us_per_launch": e * 1e6, "us_per_launch_min_max": [min(te) * 1e6, max(te) * 1e6], "event_us_last_launch": event_ms * 1e3,
+                         "us_per_step": e * 1e6 / args.steps,
+                         "universe_steps_per_s": B * args.steps / e, "tcells_per_s": B * args.steps * CELLS / e / 1e12},
+            "baseline_engine_sweep": {"us_per_sweep": b * 1e6, "us_per_sweep_min_max": [min(tb) * 1e6, max(tb) * 1e6],
+                                      "us_per_step_per_universe": b * 1e6 / (B * args.steps),
+                                      "universe_steps_per_s": B * args.steps / b, "tcells_per_s": B * args.steps * CELLS / b / 1e12},
+            "baseline_over_ensemble": b / e,
+            "states_verified": len(list(sample)),
+        }
+        rows.append(row)
+        print(json.dumps(row))
+    kernel = eng.info().kernel_name.decode()
+    eng.close(); ens.close()
+    result = {
+        "what": "B universes of 64^3, rule B2,4/S1,3,5, random fills (density 1/2): one Ensemble.step(steps) launch vs. B Engine.step(steps) calls",
+        "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+        "ensemble_kernel": "ca_ensemble_vn64 (rule as data)", "baseline_kernel": kernel,
+        "timing": f"host clock around >= {args.min_seconds} s of calls ending in a synchronise; median of {args.repeats} alternating measurements",
+        "rows": rows,
+    }
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+    print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+    slower = [r["universes"] for r in rows if r["universes"] >= 256 and r["baseline_over_ensemble"] <= 1.0]
+    if slower:
+        raise SystemExit(f"the ensemble is no faster than the engine sweep at B = {slower}: it has no reason to exist")
+
+
+if __name__ == "__main__":
+    main()
