@@ -55,6 +55,11 @@ class SummaryStruct(C.Structure):
     ]
 
 
+class SeedStruct(C.Structure):
+    """ca3d_seed (include/ca3d.h)."""
+    _fields_ = [("seed", C.c_uint32), ("and_rounds", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
+
+
 STOP_EXTINCT, STOP_STILL = 1, 2
 ENSEMBLE_ALL = 0xFFFFFFFF
 ENSEMBLE_WORDS = 8192  # words of one 64^3 universe
@@ -131,6 +136,10 @@ SYMBOLS = [
     ("ca3d_ensemble_set_rules", C.c_int, [_H, C.c_uint32, _i32p, C.c_uint32, _i32p, C.c_uint32, _i32p, C.c_uint32, _u32p, _u32p]),
     ("ca3d_ensemble_upload_state", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.c_size_t]),
     ("ca3d_ensemble_read_state", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.c_size_t]),
+    ("ca3d_seed_state", C.c_int, [_H, C.POINTER(SeedStruct)]),
+    ("ca3d_group_seed_state", C.c_int, [_H, C.POINTER(SeedStruct)]),
+    ("ca3d_ensemble_seed_state", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SeedStruct), C.c_uint32]),
+    ("ca3d_ensemble_set_rule_tables", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint32]),
     ("ca3d_ensemble_step", C.c_int, [_H, C.c_uint32]),
     ("ca3d_ensemble_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),

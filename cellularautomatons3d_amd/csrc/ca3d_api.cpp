@@ -152,6 +152,45 @@ int check_ready(ca3d_engine *h)
 	return CA3D_OK;
 }
 
+// The "state replaced" tail of ca3d_upload_state and ca3d_seed_state: what holds of an engine whose two ping-pong buffers have just been
+// given the same new words (on the engine's stream; the caller has bound the device, joined the frames in flight and dropped the queued
+// steps). A resident launch whose completion has not been looked at must have left the stream before this is called.
+static int state_replaced(ca3d_engine *h)
+{
+	h->step = 0;
+	h->cur = 0;
+	h->prev_ok = false;
+	h->state_serial++;
+	h->buffers_exposed = false;
+	h->pending_edges = 0; // a restart between the two phases of a batch abandons the batch
+	h->ghosts_valid = false;
+	h->res_pending.clear(); // their results have just been overwritten
+	if (h->res_status_host && *h->res_status_host)
+	{
+		// a resident launch gave up earlier: clean mailboxes and status for whoever turns the path on again
+		HIP_TRY(hipMemsetAsync(h->res_mail, 0, h->res_mail_bytes, h->stream));
+		HIP_TRY(hipMemsetAsync(h->res_status, 0, kResStatusBytes, h->stream));
+		h->res_status_host[0] = h->res_status_host[1] = 0;
+		h->res_epoch = 0;
+		h->res_check = false;
+		h->res_failed = true;
+	}
+	h->has_state = true;
+	return CA3D_OK;
+}
+
+// ca3d_seed's refusals, decided once for engines, groups and ensembles
+const char *seed_spec_error(const ca3d_seed &s, uint32_t G)
+{
+	if (s.and_rounds > 31u) return "and_rounds must be in [0, 31]";
+	for (int i = 0; i < 3; i++)
+	{
+		if (s.box_min[i] > s.box_max[i]) return "box_min exceeds box_max";
+		if (s.box_max[i] >= G) return "box_max lies outside the grid";
+	}
+	return nullptr;
+}
+
 // ca3d_set_stream / ca3d_use_own_stream: everything of the old stream is waited for and verified, what was built for it is dropped
 static int switch_stream(ca3d_engine *h, hipStream_t s)
 {
@@ -378,25 +417,8 @@ int ca3d_upload_state(ca3d_t *h, const uint32_t *words, size_t n_words) CA3D_API
 	HIP_TRY(hipMemcpyAsync(h->buf[0] + off, words, bytes, hipMemcpyHostToDevice, h->stream));
 	HIP_TRY(hipMemcpyAsync(h->buf[1] + off, h->buf[0] + off, bytes, hipMemcpyDeviceToDevice, h->stream));
 	HIP_TRY(hipStreamSynchronize(h->stream));
-	h->step = 0;
-	h->cur = 0;
-	h->prev_ok = false;
-	h->state_serial++;
-	h->buffers_exposed = false;
-	h->pending_edges = 0; // a restart between the two phases of a batch abandons the batch
-	h->ghosts_valid = false;
-	h->res_pending.clear(); // their results have just been overwritten
-	if (h->res_status_host && *h->res_status_host)
-	{
-		// a resident launch gave up earlier: clean mailboxes and status for whoever turns the path on again
-		HIP_TRY(hipMemsetAsync(h->res_mail, 0, h->res_mail_bytes, h->stream));
-		HIP_TRY(hipMemsetAsync(h->res_status, 0, kResStatusBytes, h->stream));
-		h->res_status_host[0] = h->res_status_host[1] = 0;
-		h->res_epoch = 0;
-		h->res_check = false;
-		h->res_failed = true;
-	}
-	h->has_state = true;
+	rc = state_replaced(h);
+	if (rc) return rc;
 	h->binary_state = false;
 	if (h->layout == CA3D_LAYOUT_UNPACKED)
 	{
@@ -404,6 +426,34 @@ int ca3d_upload_state(ca3d_t *h, const uint32_t *words, size_t n_words) CA3D_API
 		for (size_t i = 0; i < n_words && bin; i++) bin = words[i] <= 1u;
 		h->binary_state = bin;
 	}
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_seed_state(ca3d_t *h, const ca3d_seed *spec) CA3D_API_TRY
+{
+	if (!h) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL engine handle");
+	if (!spec) return fail(CA3D_ERR_INVALID_ARGUMENT, "spec is NULL");
+	if (!h->configured) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_configure has not been called");
+	if (const char *why = seed_spec_error(*spec, h->G))
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "seed spec for a grid of %u: %s (box (%u, %u, %u) .. (%u, %u, %u), and_rounds %u)", h->G, why, spec->box_min[0],
+		            spec->box_min[1], spec->box_min[2], spec->box_max[0], spec->box_max[1], spec->box_max[2], spec->and_rounds);
+	h->queued = 0; // the state they would have produced is overwritten
+	int rc = bind_device(h);
+	if (rc) return rc;
+	// a resident launch nobody has looked at yet: its verdict must not arrive after the state it belonged to has gone (the upload's wait)
+	if (!h->res_pending.empty() || h->res_check) HIP_TRY(hipStreamSynchronize(h->stream));
+	SeedLaunch l;
+	l.buf0 = h->buf[0]; l.buf1 = h->buf[1];
+	l.G = h->G;
+	l.layout = h->layout;
+	l.z0 = h->z0; l.nz = h->nz; l.ghost = h->slab ? h->ghost : 0u;
+	l.spec = *spec;
+	hipError_t e = launch_seed(l, h->stream); // both buffers, ghost planes zeroed, in one pass
+	if (e != hipSuccess) return fail(CA3D_ERR_DEVICE, "seed kernel launch failed: %s", hipGetErrorString(e));
+	rc = state_replaced(h);
+	if (rc) return rc;
+	h->binary_state = true; // unpacked: every cell is 0 or 1
 	return CA3D_OK;
 }
 CA3D_API_CATCH

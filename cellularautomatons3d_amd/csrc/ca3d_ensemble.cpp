@@ -20,6 +20,10 @@ struct ca3d_ensemble
 	uint32_t n = 0; // universes; 0: not configured
 	uint32_t *state = nullptr, *prev = nullptr, *rules = nullptr, *steps_done = nullptr, *reason = nullptr;
 	ca3d_summary *records = nullptr;
+	// ca3d_ensemble_seed_state with one spec per universe: the specs on the device, their pinned staging copy (n entries each, allocated
+	// at the first such call) and the event behind the copy out of it
+	ca3d_seed *seed_dev = nullptr, *seed_host = nullptr;
+	hipEvent_t ev_seed = nullptr;
 	std::vector<uint8_t> has_rules, has_state;
 	uint32_t missing_rules = 0, missing_state = 0; // universes without either
 	// the last step call, for ca3d_ensemble_get_stats
@@ -37,6 +41,9 @@ void free_arrays(ca3d_ensemble *e)
 		if (p) hipFree(p);
 	e->state = e->prev = e->rules = e->steps_done = e->reason = nullptr;
 	e->records = nullptr;
+	if (e->seed_dev) hipFree(e->seed_dev);
+	if (e->seed_host) hipHostFree(e->seed_host);
+	e->seed_dev = e->seed_host = nullptr;
 	e->n = 0;
 	e->timed = false;
 }
@@ -142,6 +149,7 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	free_arrays(e);
 	if (e->ev_start) hipEventDestroy(e->ev_start);
 	if (e->ev_stop) hipEventDestroy(e->ev_stop);
+	if (e->ev_seed) hipEventDestroy(e->ev_seed);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
 	return CA3D_OK;
@@ -228,6 +236,70 @@ int ca3d_ensemble_upload_state(ca3d_ensemble_t *e, uint32_t first, uint32_t coun
 	HIP_TRY(hipStreamSynchronize(e->stream)); // the caller's buffer is consumed when the call returns
 	for (uint32_t u = first; u < first + count; u++)
 		if (!e->has_state[u]) { e->has_state[u] = 1; e->missing_state--; }
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_seed_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const ca3d_seed *specs, uint32_t n_specs) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!specs) return fail(CA3D_ERR_INVALID_ARGUMENT, "specs is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if (n_specs != 1u && n_specs != count) return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes take 1 or %u specs (got %u)", count, count, n_specs);
+	for (uint32_t k = 0; k < n_specs; k++)
+		if (const char *why = seed_spec_error(specs[k], 64u))
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "seed spec of universe %u: %s (box (%u, %u, %u) .. (%u, %u, %u), and_rounds %u)", first + k, why, specs[k].box_min[0],
+			            specs[k].box_min[1], specs[k].box_min[2], specs[k].box_max[0], specs[k].box_max[1], specs[k].box_max[2], specs[k].and_rounds);
+	HIP_TRY(hipSetDevice(e->device));
+	const ca3d_seed *on_device = nullptr; // one spec for all travels as a kernel argument
+	if (n_specs > 1u)
+	{
+		if (!e->seed_dev) HIP_TRY(hipMalloc((void **)&e->seed_dev, (size_t)e->n * sizeof(ca3d_seed)));
+		if (!e->seed_host) HIP_TRY(hipHostMalloc((void **)&e->seed_host, (size_t)e->n * sizeof(ca3d_seed), hipHostMallocDefault));
+		if (!e->ev_seed) HIP_TRY(hipEventCreateWithFlags(&e->ev_seed, hipEventDisableTiming));
+		else HIP_TRY(hipEventSynchronize(e->ev_seed)); // the staging copy is free again once the last call's copy out of it is done
+		// the caller's array is consumed here; the copy and the fill are stream-ordered behind whatever still reads the device copy
+		memcpy(e->seed_host, specs, (size_t)count * sizeof(ca3d_seed));
+		HIP_TRY(hipMemcpyAsync(e->seed_dev, e->seed_host, (size_t)count * sizeof(ca3d_seed), hipMemcpyHostToDevice, e->stream));
+		HIP_TRY(hipEventRecord(e->ev_seed, e->stream));
+		on_device = e->seed_dev;
+	}
+	HIP_TRY(launch_seed_ensemble(e->state, e->prev, first, count, on_device, specs[0], e->stream)); // both buffers of every universe in one pass
+	// the records of the new states: step 0, no previous state (the launch ca3d_ensemble_upload_state ends in)
+	EnsembleLaunch l = launch_of(e);
+	l.first = first; l.count = count;
+	l.reset = true;
+	l.final = true;
+	HIP_TRY(launch_ensemble(l, e->stream));
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_state[u]) { e->has_state[u] = 1; e->missing_state--; }
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_set_rule_tables(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *born_masks, const uint32_t *survive_masks,
+                                  uint32_t n_masks) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!born_masks || !survive_masks) return fail(CA3D_ERR_INVALID_ARGUMENT, "a mask array is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if (n_masks != 1u && n_masks != count) return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes take 1 or %u mask pairs (got %u)", count, count, n_masks);
+	std::vector<uint32_t> words(count);
+	for (uint32_t k = 0; k < count; k++)
+	{
+		const uint32_t b = born_masks[n_masks == 1u ? 0u : k], s = survive_masks[n_masks == 1u ? 0u : k];
+		if ((b | s) & ~0x7Fu)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "universe %u: born mask %#x / survive mask %#x — a von Neumann count is 0 .. 6, bits 7 and above mean nothing", first + k, b, s);
+		words[k] = (s & 0x7Fu) | (b & 0x7Fu) << 8; // the word ca3d_ensemble_set_rules stores (vn_tables)
+	}
+	HIP_TRY(hipSetDevice(e->device));
+	// stream-ordered behind the steps already enqueued, which keep the rules they were enqueued under; the source is consumed on return
+	HIP_TRY(hipMemcpyAsync(e->rules + first, words.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_rules[u]) { e->has_rules[u] = 1; e->missing_rules--; }
 	return CA3D_OK;
 }
 CA3D_API_CATCH

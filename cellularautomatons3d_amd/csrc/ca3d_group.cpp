@@ -279,6 +279,19 @@ int ca3d_group_upload_state(ca3d_group_t *g, const uint32_t *words, size_t n_wor
 }
 CA3D_API_CATCH
 
+int ca3d_group_seed_state(ca3d_group_t *g, const ca3d_seed *spec) CA3D_API_TRY
+{
+	if (!g) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL group handle");
+	if (!spec) return fail(CA3D_ERR_INVALID_ARGUMENT, "spec is NULL");
+	G_TRY(check_group(g, false));
+	for (ca3d_t *e : g->eng) G_TRY(ca3d_seed_state(e, spec)); // every rank fills its own planes on its own device: nothing is staged on the host
+	g->has_state = true;
+	g->ghosts_valid = false;
+	g->step = 0;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
 int ca3d_group_read_state(ca3d_group_t *g, uint32_t *words, size_t n_words) CA3D_API_TRY
 {
 	G_TRY(check_group(g, false));

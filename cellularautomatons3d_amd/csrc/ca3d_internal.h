@@ -215,6 +215,21 @@ struct EnsembleLaunch
 };
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream);
 int ensemble_workgroups_per_cu(); // what the runtime says of ca_ensemble_vn64 (0: it cannot tell)
+// ca_seed.hip: the counter-based fill of ca3d_seed (include/ca3d.h) written where the state lives. One launch covers the whole arrays of
+// both ping-pong buffers: array plane a is global plane z0 - ghost + a; the `ghost` planes below and above the owned ones are zeroed.
+struct SeedLaunch
+{
+	uint32_t *buf0, *buf1; // the two ping-pong arrays (ghosts included), nz + 2 * ghost planes each
+	uint32_t G;
+	int layout;
+	uint32_t z0, nz, ghost; // owned planes [z0, z0 + nz) of the grid (full grid: 0, G, 0)
+	ca3d_seed spec;         // validated by the caller (seed_spec_error)
+};
+hipError_t launch_seed(const SeedLaunch &l, hipStream_t stream);
+// universes [first, first + count) of an ensemble: universe first + k takes specs[k] (a DEVICE array) or, when specs is null, `one`
+hipError_t launch_seed_ensemble(uint32_t *state, uint32_t *prev, uint32_t first, uint32_t count, const ca3d_seed *specs, const ca3d_seed &one, hipStream_t stream);
+// why a spec is refused for a grid of G cells an edge, or null (ca3d_api.cpp; one decision for engines, groups and ensembles)
+const char *seed_spec_error(const ca3d_seed &s, uint32_t G);
 // ca_diag.hip: float4 device-to-device copy (measurement only)
 hipError_t launch_copy_f4(const void *in, void *out, size_t bytes, hipStream_t stream);
 // ca_diag.hip: do two (idle) streams run side by side, i.e. sit on different hardware queues? (probe: ~2 ms)

@@ -48,6 +48,17 @@ def _summary(s: "_capi.SummaryStruct", planes: Optional[np.ndarray]) -> Summary:
 STOP_EXTINCT, STOP_STILL = _capi.STOP_EXTINCT, _capi.STOP_STILL
 
 
+def _seed_spec(grid_size: int, seed: int, and_rounds: int = 0, box=None) -> "_capi.SeedStruct":
+    """`ca3d_seed` for a grid of `grid_size`; `box` = ((x0, y0, z0), (x1, y1, z1)) inclusive, None: the whole grid. Values are handed
+    over as given (modulo 2^32): the library refuses what does not fit the grid."""
+    lo, hi = ((0, 0, 0), (grid_size - 1,) * 3) if box is None else box
+    s = _capi.SeedStruct()
+    s.seed, s.and_rounds = int(seed) & 0xFFFFFFFF, int(and_rounds) & 0xFFFFFFFF
+    for i in range(3):
+        s.box_min[i], s.box_max[i] = int(lo[i]) & 0xFFFFFFFF, int(hi[i]) & 0xFFFFFFFF
+    return s
+
+
 class Engine:
     """One engine = one GPU, one HIP stream, two ping-pong state buffers."""
 
@@ -116,6 +127,12 @@ class Engine:
     def upload_state(self, words) -> None:
         w = _as_u32(words).ravel()
         _capi.check(self._lib.ca3d_upload_state(self._h, w.ctypes.data_as(_u32p), w.size))
+
+    def seed_state(self, seed: int, and_rounds: int = 0, box=None) -> None:
+        """`ca3d_seed_state`: the state `host.seeded_state(grid_size, seed, and_rounds, box, layout)` (a slab engine: its planes of it),
+        written on the device into both buffers — nothing is uploaded. Replaces the state as `upload_state` does; asynchronous."""
+        spec = _seed_spec(self.grid_size, seed, and_rounds, box)
+        _capi.check(self._lib.ca3d_seed_state(self._h, C.byref(spec)))
 
     def read_state(self) -> np.ndarray:
         out = np.empty(self.info().state_words, dtype=np.uint32)
@@ -368,6 +385,16 @@ class EngineGroup:
         w = _as_u32(words).ravel()
         _capi.check(self._lib.ca3d_group_upload_state(self._h, w.ctypes.data_as(_u32p), w.size))
         self._words = w.size
+
+    def seed_state(self, seed: int, and_rounds: int = 0, box=None) -> None:
+        """`ca3d_group_seed_state`: every rank seeds its own planes of `host.seeded_state(...)` on its own device; asynchronous."""
+        spec = _seed_spec(self.grid_size, seed, and_rounds, box)
+        _capi.check(self._lib.ca3d_group_seed_state(self._h, C.byref(spec)))
+        e = C.c_void_p()
+        _capi.check(self._lib.ca3d_group_engine(self._h, 0, C.byref(e)))
+        i = Info()
+        _capi.check(self._lib.ca3d_get_info(e, C.byref(i)))
+        self._words = int(i.state_words) * len(self.devices)
 
     def read_state(self) -> np.ndarray:
         out = np.empty(self._words, dtype=np.uint32)

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi, host
 from ._capi import ENSEMBLE_ALL, ENSEMBLE_WORDS, Stats
-from .engine import STOP_EXTINCT, STOP_STILL, Summary, _as_i32, _as_u32, _summary
+from .engine import STOP_EXTINCT, STOP_STILL, Summary, _as_i32, _as_u32, _seed_spec, _summary
 
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
@@ -74,6 +74,38 @@ class Ensemble:
         if w.size == 0 or w.size % ENSEMBLE_WORDS:
             raise ValueError("a universe holds 8192 words")
         _capi.check(self._lib.ca3d_ensemble_upload_state(self._h, first, w.size // ENSEMBLE_WORDS, w.ctypes.data_as(_u32p), w.size))
+
+    def seed_states(self, first: int, seeds, and_rounds=0, box=None, count: Optional[int] = None) -> None:
+        """`ca3d_ensemble_seed_state`: universe first + k becomes `host.seeded_state(64, seeds[k], and_rounds[k], box)`, written on the
+        device. `seeds` / `and_rounds`: arrays (one entry per universe) or scalars, which broadcast; all scalars: ONE spec for `count`
+        universes (default: all from `first`). A scalar beside an array broadcasts per universe (one spec each, the
+        scalar repeated); `count` is only needed in the all-scalar form. `box`: one for all. Records restart at step 0; the fill may still be running on return."""
+        sd, ar = np.atleast_1d(np.asarray(seeds, dtype=np.uint64)), np.atleast_1d(np.asarray(and_rounds, dtype=np.uint64))
+        scalar = np.ndim(seeds) == 0 and np.ndim(and_rounds) == 0
+        if scalar:
+            count = self.n - first if count is None else count
+            specs = (_capi.SeedStruct * 1)(_seed_spec(64, int(sd[0]), int(ar[0]), box))
+        else:
+            n = max(sd.size, ar.size)
+            if count is not None and count != n:
+                raise ValueError("count does not match the per-universe arrays")
+            sd, ar, count = np.broadcast_to(sd, n), np.broadcast_to(ar, n), n
+            specs = (_capi.SeedStruct * n)(*[_seed_spec(64, int(a), int(b), box) for a, b in zip(sd, ar)])
+        _capi.check(self._lib.ca3d_ensemble_seed_state(self._h, first, count, specs, len(specs)))
+
+    def set_rule_tables(self, first: int, born_masks, survive_masks, count: Optional[int] = None) -> None:
+        """`ca3d_ensemble_set_rule_tables`: von Neumann rules as masks (bit c = born / survive at count c, c in 0..6) for universes from
+        `first`, in one call. Arrays: one pair per universe (a scalar beside an array is repeated per universe); two scalars: that pair
+        for `count` universes (default: all from `first`). Waits for the stream, as `set_rules` does."""
+        b, s = np.atleast_1d(_as_u32(born_masks)), np.atleast_1d(_as_u32(survive_masks))
+        if np.ndim(born_masks) == 0 and np.ndim(survive_masks) == 0:
+            count = self.n - first if count is None else count
+        else:
+            n = max(b.size, s.size)
+            if count is not None and count != n:
+                raise ValueError("count does not match the per-universe arrays")
+            b, s, count = np.ascontiguousarray(np.broadcast_to(b, n)), np.ascontiguousarray(np.broadcast_to(s, n)), n
+        _capi.check(self._lib.ca3d_ensemble_set_rule_tables(self._h, first, count, b.ctypes.data_as(_u32p), s.ctypes.data_as(_u32p), b.size))
 
     def read_state(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         count = self.n - first if count is None else count

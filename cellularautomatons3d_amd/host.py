@@ -202,6 +202,58 @@ def random_fill(n_words: int, seed: int = 0xCA3D0001, and_rounds: int = 0) -> np
     return w
 
 
+def _seed_box(grid_size: int, box):
+    """((x0, y0, z0), (x1, y1, z1)) inclusive, None = the whole grid; validated as `ca3d_seed` is."""
+    G = int(grid_size)
+    if box is None:
+        return (0, 0, 0), (G - 1, G - 1, G - 1)
+    lo, hi = tuple(int(v) for v in box[0]), tuple(int(v) for v in box[1])
+    if len(lo) != 3 or len(hi) != 3 or any(a < 0 or a > b or b >= G for a, b in zip(lo, hi)):
+        raise ValueError(f"box {lo} .. {hi} does not lie in a grid of {G}")
+    return lo, hi
+
+
+def seeded_state(grid_size: int, seed: int, and_rounds: int = 0, box=None, layout: int = 0, z0: int = 0, nz: Optional[int] = None) -> np.ndarray:
+    """The definition of `ca3d_seed_state` (include/ca3d.h) in executable form: what the device kernels (csrc/ca_seed.hip) must write.
+
+    Planes [z0, z0 + nz) of a G^3 grid (default: all). PACKED32 (layout 0): word (x >> 5) + y * cols + z * cols * G of the FULL grid is the
+    `random_fill` word of that index, ANDed with the mask of its bits whose x lies in the box, and 0 when y or z is outside it. UNPACKED
+    (layout 1): cell (x, y, z) is 1 exactly when it is in the box and bit x & 31 of the packed word at (x >> 5) + y * ceil(G / 32) +
+    z * ceil(G / 32) * G is set. `box` = ((x0, y0, z0), (x1, y1, z1)) inclusive, global cell coordinates; None: the whole grid."""
+    G = int(grid_size)
+    if layout == 0:
+        _check_grid(G)
+    elif G <= 0 or G % 4:
+        raise ValueError(f"unpacked grid size must be a positive multiple of 4, got {G}")
+    if not 0 <= and_rounds <= 31:
+        raise ValueError("and_rounds must be in [0, 31]")
+    nz = G - z0 if nz is None else nz
+    if z0 < 0 or nz <= 0 or z0 + nz > G:
+        raise ValueError("planes outside the grid")
+    lo, hi = _seed_box(G, box)
+    cols = (G + 31) // 32
+    plane = cols * G
+    i = np.arange(z0 * plane, (z0 + nz) * plane, dtype=np.uint64)  # enters the hash modulo 2^32 (_mix32 masks)
+    w = _mix32(seed, i, 0)
+    for r in range(1, and_rounds + 1):
+        w &= _mix32(seed, i, r)
+    w = w.reshape(nz, G, cols)
+    xw = np.arange(cols, dtype=np.int64) * 32
+    first = np.clip(lo[0] - xw, 0, 32)  # bits below `first` and from `last` on lie outside the box
+    last = np.clip(hi[0] + 1 - xw, 0, 32)
+    ones = np.uint64(0xFFFFFFFF)
+    xmask = (((ones << first.astype(np.uint64)) & ones) & ~((ones << last.astype(np.uint64)) & ones) & ones).astype(np.uint32)
+    xmask[last <= first] = 0
+    w = w & xmask[None, None, :]
+    ys, zs = np.arange(G), np.arange(z0, z0 + nz)
+    w[:, (ys < lo[1]) | (ys > hi[1]), :] = 0
+    w[(zs < lo[2]) | (zs > hi[2]), :, :] = 0
+    if layout == 0:
+        return np.ascontiguousarray(w).reshape(-1)
+    bits = (w[:, :, :, None] >> np.arange(32, dtype=np.uint32)[None, None, None, :]) & np.uint32(1)
+    return np.ascontiguousarray(bits.reshape(nz, G, cols * 32)[:, :, :G]).reshape(-1)
+
+
 def cells_to_words(grid_size: int, cells: Iterable[Sequence[int]]) -> np.ndarray:
     """Packed state with exactly the listed (x, y, z) cells alive."""
     data = np.zeros(words_per_buffer(grid_size), dtype=np.uint32)

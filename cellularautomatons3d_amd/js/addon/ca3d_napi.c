@@ -1133,6 +1133,86 @@ static napi_value js_ensemble_stats(napi_env env, napi_callback_info info)
 	return o;
 }
 
+/*
+ * ca3d_seed_state and its kin: a spec crosses as eight u32 in ca3d_seed's own order — seed, andRounds, boxMin x y z, boxMax x y z
+ * (js/ca3d.js builds them: seedSpec).
+ */
+static const ca3d_seed *get_specs(napi_env env, napi_value v, size_t *n_specs)
+{
+	void *w;
+	size_t n;
+	if (!get_typed(env, v, napi_uint32_array, 0, &w, &n)) return NULL;
+	if (n == 0 || n % 8u)
+	{
+		napi_throw_range_error(env, NULL, "a seed spec holds 8 words: seed, andRounds, boxMin[3], boxMax[3]");
+		return NULL;
+	}
+	*n_specs = n / 8u;
+	return (const ca3d_seed *)w;
+}
+
+/* seedState(handle, Uint32Array(8)) */
+static napi_value js_seed_state(napi_env env, napi_callback_info info)
+{
+	napi_value argv[2];
+	if (!get_args(env, info, 2, argv)) return NULL;
+	ca3d_t *h = get_handle(env, argv[0]);
+	size_t n;
+	const ca3d_seed *spec = h ? get_specs(env, argv[1], &n) : NULL;
+	if (!spec) return NULL;
+	int rc = ca3d_seed_state(h, spec);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+/* groupSeedState(group, Uint32Array(8)) */
+static napi_value js_group_seed_state(napi_env env, napi_callback_info info)
+{
+	napi_value argv[2];
+	if (!get_args(env, info, 2, argv)) return NULL;
+	ca3d_group_t *g = get_group(env, argv[0]);
+	size_t n;
+	const ca3d_seed *spec = g ? get_specs(env, argv[1], &n) : NULL;
+	if (!spec) return NULL;
+	int rc = ca3d_group_seed_state(g, spec);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+/* ensembleSeedState(handle, first, count, Uint32Array(8 * (1 | count))) */
+static napi_value js_ensemble_seed_state(napi_env env, napi_callback_info info)
+{
+	napi_value argv[4];
+	if (!get_args(env, info, 4, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, count;
+	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count)) return NULL;
+	size_t n;
+	const ca3d_seed *specs = get_specs(env, argv[3], &n);
+	if (!specs) return NULL;
+	int rc = ca3d_ensemble_seed_state(e, first, count, specs, (uint32_t)n);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+/* ensembleSetRuleTables(handle, first, count, Uint32Array born masks, Uint32Array survive masks) — 1 or count entries each */
+static napi_value js_ensemble_set_rule_tables(napi_env env, napi_callback_info info)
+{
+	napi_value argv[5];
+	if (!get_args(env, info, 5, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, count;
+	void *b, *s;
+	size_t nb, ns;
+	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count) || !get_typed(env, argv[3], napi_uint32_array, 0, &b, &nb) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 0, &s, &ns))
+		return NULL;
+	if (nb != ns || nb == 0)
+	{
+		napi_throw_range_error(env, NULL, "born and survive masks must hold the same number of entries");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_set_rule_tables(e, first, count, (const uint32_t *)b, (const uint32_t *)s, (uint32_t)nb);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
 static napi_value js_recovered_launches(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1194,7 +1274,9 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleCreate", js_ensemble_create}, {"ensembleDestroy", js_ensemble_destroy}, {"ensembleConfigure", js_ensemble_configure},
 	    {"ensembleSetRules", js_ensemble_set_rules}, {"ensembleUploadState", js_ensemble_upload_state}, {"ensembleReadState", js_ensemble_read_state},
 	    {"ensembleStep", js_ensemble_step}, {"ensembleStepUntil", js_ensemble_step_until}, {"ensembleSummaries", js_ensemble_summaries},
-	    {"ensembleSynchronize", js_ensemble_synchronize}, {"ensembleStats", js_ensemble_stats}};
+	    {"ensembleSynchronize", js_ensemble_synchronize}, {"ensembleStats", js_ensemble_stats},
+	    {"seedState", js_seed_state}, {"groupSeedState", js_group_seed_state}, {"ensembleSeedState", js_ensemble_seed_state},
+	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

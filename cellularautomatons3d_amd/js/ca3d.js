@@ -135,6 +135,54 @@ function randomFill(nWords, seed, andRounds)
 	return out;
 }
 
+// The definition of ca3d_seed_state (include/ca3d.h) in executable form, twin of host.seeded_state: planes [z0, z0 + nz) of the state
+// a device seed leaves. opts: {andRounds, box: {min: [x, y, z], max: [x, y, z]} (inclusive; default the whole grid), layout, z0, nz}.
+// Packed: word (x >> 5) + y * cols + z * cols * G of the FULL grid is randomFill's word of that index, ANDed with the mask of its bits
+// whose x lies in the box, 0 when y or z is outside; unpacked: one 0 / 1 word per cell, cut from the same packed words.
+function seededState(gridSize, seed, opts)
+{
+	const o = opts || {};
+	const G = gridSize, layout = o.layout || LAYOUT_PACKED32, rounds = o.andRounds || 0;
+	if (layout === LAYOUT_PACKED32 ? (G <= 0 || G % 32) : (G <= 0 || G % 4)) { throw new RangeError("grid size " + G + " does not fit the layout"); }
+	if (rounds < 0 || rounds > 31) { throw new RangeError("andRounds must be in [0, 31]"); }
+	const z0 = o.z0 || 0, nz = o.nz === undefined ? G - z0 : o.nz;
+	if (z0 < 0 || nz <= 0 || z0 + nz > G) { throw new RangeError("planes outside the grid"); }
+	const lo = o.box ? o.box.min : [0, 0, 0], hi = o.box ? o.box.max : [G - 1, G - 1, G - 1];
+	for (let i = 0; i < 3; i++) { if (lo[i] < 0 || lo[i] > hi[i] || hi[i] >= G) { throw new RangeError("the box does not lie in the grid"); } }
+	seed = seed === undefined ? 0xCA3D0001 : seed;
+	const mix = (i, r) => { let x = (Math.imul(i, 0x9E3779B9) + seed + Math.imul(r, 0x85EBCA6B)) >>> 0; x ^= x >>> 16; x = Math.imul(x, 0x7FEB352D) >>> 0; x ^= x >>> 15; x = Math.imul(x, 0x846CA68B) >>> 0; x ^= x >>> 16; return x >>> 0; };
+	const cols = Math.ceil(G / 32);
+	const packed = layout === LAYOUT_PACKED32;
+	const out = new Uint32Array(packed ? cols * G * nz : G * G * nz);
+	for (let z = z0; z < z0 + nz; z++)
+	{
+		if (z < lo[2] || z > hi[2]) { continue; }
+		for (let y = lo[1]; y <= hi[1]; y++)
+		{
+			for (let xw = 0; xw < cols; xw++)
+			{
+				const a = Math.max(lo[0], 32 * xw), b = Math.min(hi[0], 32 * xw + 31);
+				if (a > b) { continue; }
+				const i = xw + y * cols + z * cols * G; // enters the hash modulo 2^32 (Math.imul)
+				let w = mix(i, 0);
+				for (let r = 1; r <= rounds; r++) { w &= mix(i, r); }
+				w = (w & ((0xFFFFFFFF << (a & 31)) & (0xFFFFFFFF >>> (31 - (b & 31))))) >>> 0;
+				if (packed) { out[xw + (y + (z - z0) * G) * cols] = w; }
+				else { for (let x = a; x <= b; x++) { out[x + (y + (z - z0) * G) * G] = (w >>> (x & 31)) & 1; } }
+			}
+		}
+	}
+	return out;
+}
+
+// ca3d_seed as the addon takes it: seed, andRounds, boxMin x y z, boxMax x y z
+function seedSpec(gridSize, spec)
+{
+	const s = spec || {};
+	const lo = s.box ? s.box.min : [0, 0, 0], hi = s.box ? s.box.max : [gridSize - 1, gridSize - 1, gridSize - 1];
+	return [(s.seed === undefined ? 0xCA3D0001 : s.seed) >>> 0, (s.andRounds || 0) >>> 0, lo[0] >>> 0, lo[1] >>> 0, lo[2] >>> 0, hi[0] >>> 0, hi[1] >>> 0, hi[2] >>> 0];
+}
+
 // Checkpoint file: 'CA3D' | u32 version | u32 grid | u32 layout | u64 step | u64 words | LE u32 words (host.py twin)
 function saveCheckpoint(file, words, gridSize, step, layout)
 {
@@ -211,6 +259,10 @@ class Engine
 
 	uploadState(words) { this._idle("uploadState"); this._a.uploadState(this._h, words); }
 
+	// ca3d_seed_state: the state seededState(gridSize, seed, {andRounds, box, layout}) written on the device into both buffers — nothing is
+	// uploaded. Replaces the state as uploadState does; only enqueues. spec: {seed, andRounds, box: {min: [x, y, z], max: [x, y, z]}}
+	seedState(spec) { this._idle("seedState"); this._a.seedState(this._h, Uint32Array.from(seedSpec(this.gridSize, spec))); }
+
 	readState()
 	{
 		this._idle("readState");
@@ -225,7 +277,7 @@ class Engine
 	flush() { this._idle("flush"); this._a.flush(this._h); }
 
 	// Z-slab mode (multi-GPU hosts; SURVEY 8(e)): see include/ca3d.h. phase: 0 whole batch, 1 edge zones, 2 interior.
-	configureSlab(gridSize, z0, nz, ghost, layout) { this._a.configureSlab(this._h, gridSize, layout === undefined ? LAYOUT_PACKED32 : layout, z0, nz, ghost); }
+	configureSlab(gridSize, z0, nz, ghost, layout) { this._a.configureSlab(this._h, gridSize, layout === undefined ? LAYOUT_PACKED32 : layout, z0, nz, ghost); this.gridSize = gridSize; }
 	slabStep(n) { this._a.slabStep(this._h, n); }
 	slabStepPhase(n, phase) { this._a.slabStepPhase(this._h, n, phase); }
 	// RCCL transport inside the engine: one process per GPU; rank 0 creates the id (Engine.commUniqueId()) and hands it to
@@ -314,7 +366,7 @@ class EngineGroup
 	}
 	close() { if (this._g) { this._a.groupDestroy(this._g); this._g = null; } }
 	/** ghost = planes kept of each neighbour = steps between two exchanges */
-	configure(gridSize, ghost, layout) { this._a.groupConfigure(this._g, gridSize, layout || LAYOUT_PACKED32, ghost); this.gridSize = gridSize; }
+	configure(gridSize, ghost, layout) { this._a.groupConfigure(this._g, gridSize, layout || LAYOUT_PACKED32, ghost); this.gridSize = gridSize; this.layout = layout || LAYOUT_PACKED32; }
 	setRules(mainOffsets, edgesOffsets, cornersOffsets, survive, born) { this._a.groupSetRules(this._g, mainOffsets, edgesOffsets, cornersOffsets, survive, born); }
 	setRuleStrings(rules)
 	{
@@ -323,6 +375,12 @@ class EngineGroup
 		this.setRules(NEIGHBOURHOOD_MAP[r.neighbourhood], NEIGHBOURHOOD_MAP["edges"], NEIGHBOURHOOD_MAP["corners"], lut.survive, lut.born);
 	}
 	uploadState(words) { this._a.groupUploadState(this._g, words); this._words = words.length; }
+	/** ca3d_group_seed_state: every rank seeds its own planes on its own device (spec as Engine.seedState) */
+	seedState(spec)
+	{
+		this._a.groupSeedState(this._g, Uint32Array.from(seedSpec(this.gridSize, spec)));
+		this._words = this.layout === LAYOUT_PACKED32 ? this.gridSize / 32 * this.gridSize * this.gridSize : this.gridSize ** 3;
+	}
 	readState() { const out = new Uint32Array(this._words); this._a.groupReadState(this._g, out); return out; }
 	step(n) { this._a.groupStep(this._g, n === undefined ? 1 : n); }
 	synchronize() { this._a.groupSynchronize(this._g); }
@@ -361,6 +419,24 @@ class Ensemble
 	}
 	/** words: Uint32Array(count * 8192), the states of universes first .. first + count - 1 */
 	uploadState(first, words) { this._a.ensembleUploadState(this._e, first, words); }
+	/** ca3d_ensemble_seed_state: `specs` — ONE spec object ({seed, andRounds, box}) for `count` universes from `first` (default: all of
+	 *  them), or an array with one spec per universe */
+	seedStates(first, specs, count)
+	{
+		const list = Array.isArray(specs) ? specs : [specs];
+		count = Array.isArray(specs) ? list.length : (count === undefined ? this.n - first : count);
+		const words = new Uint32Array(8 * list.length);
+		list.forEach((s, k) => words.set(seedSpec(64, s), 8 * k));
+		this._a.ensembleSeedState(this._e, first, count, words);
+	}
+	/** ca3d_ensemble_set_rule_tables: von Neumann rules as masks (bit c = born / survive at count c, c in 0..6), one pair per universe
+	 *  from `first` (arrays), or one pair (numbers) for `count` universes (default: all from `first`) — one call, one copy */
+	setRuleTables(first, bornMasks, surviveMasks, count)
+	{
+		const scalar = typeof bornMasks === "number";
+		const b = Uint32Array.from(scalar ? [bornMasks] : bornMasks), s = Uint32Array.from(scalar ? [surviveMasks] : surviveMasks);
+		this._a.ensembleSetRuleTables(this._e, first, scalar ? (count === undefined ? this.n - first : count) : b.length, b, s);
+	}
 	readState(first, count)
 	{
 		first = first || 0;
@@ -386,5 +462,5 @@ class Ensemble
 module.exports = {
 	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
-	initialState, dispatchShape, randomFill, loadAddon, saveCheckpoint, loadCheckpoint
+	initialState, dispatchShape, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
 };

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_* */
+#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_*; + ca3d_seed_state, ca3d_group_seed_state, ca3d_ensemble_seed_state, ca3d_ensemble_set_rule_tables */
 #define CA3D_LUT_LEN 81 /* 3 rule-sets x 27 slots (main_pathtraced.js:10, 155-159) */
 
 typedef struct ca3d_engine ca3d_t;
@@ -355,6 +355,56 @@ int ca3d_ensemble_step_until(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t ch
 int ca3d_ensemble_summarize(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_summary *out);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
+
+/*
+ * Seed states on the device (no reference counterpart: its start-up blob is drawn from Math.random on the host): the counter-based
+ * fill every test, bench.py, tools/ and js/ca3d.js already share (host.random_fill / randomFill), produced where the state lives —
+ * nothing state-sized crosses the bus, one kernel (csrc/ca_seed.hip) writes BOTH ping-pong buffers in one pass.
+ *
+ * The definition (host.seeded_state / seededState in executable form). With mix32(seed, i, r):
+ *   x = (uint32_t)i * 0x9E3779B9 + seed + r * 0x85EBCA6B   (all modulo 2^32: i enters the hash modulo 2^32)
+ *   x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16
+ * fill(i) = AND over r = 0 .. and_rounds of mix32(seed, i, r): every bit is set with probability 2^-(1 + and_rounds).
+ * PACKED32: with cols = G / 32, the word at i = (x >> 5) + y * cols + z * cols * G — its index in the FULL grid, the index the digest
+ * uses, so slabs compose — is fill(i) ANDed with the mask of its bits whose x lies in [box_min.x, box_max.x], and 0 when y or z is
+ * outside the box. With the whole-grid box the state equals host.random_fill(state_words, seed, and_rounds) exactly.
+ * UNPACKED: cell (x, y, z) is 1 exactly when it is inside the box and bit x & 31 of fill((x >> 5) + y * ceil(G / 32) + z * ceil(G / 32) * G)
+ * is set, else 0 — the same universe in both layouts when G is a multiple of 32, defined for every legal unpacked G.
+ * Slab engines fill their owned planes from the global indices and zero their ghosts. Ensembles index words inside the universe's own
+ * 8192-word array, as their digest does.
+ *
+ * A seed REPLACES the state exactly as ca3d_upload_state does (one function decides it for both): the same words in both ping-pong
+ * buffers, step counter 0, has_previous 0, queued steps dropped, pending resident launches forgotten, a pending edge phase abandoned,
+ * what the renderer derived from the state stale, frames in flight joined. Unlike an upload, ca3d_seed_state and ca3d_group_seed_state
+ * only ENQUEUE and return (the one exception: behind a resident multi-step launch whose completion has not been looked at yet the call
+ * waits for the stream first, as that launch's verdict must not arrive after the state it belonged to has gone). Rules need not be set.
+ *   ca3d_group_seed_state     one ca3d_seed_state per rank on that rank's device, nothing staged on the host; leaves the group as
+ *                             ca3d_group_upload_state does (ghosts not valid: refreshed by the next ca3d_group_step)
+ *   ca3d_ensemble_seed_state  universes [first, first + count): n_specs == 1 — every one of them gets specs[0] — or n_specs == count;
+ *                             followed by the zero-step record launch of ca3d_ensemble_upload_state (records at step 0, has_previous
+ *                             0); `specs` is consumed when the call returns, the fill may still be running. Universes outside the
+ *                             range keep state, step counter and record.
+ *   ca3d_ensemble_set_rule_tables  von Neumann tables for universes [first, first + count) as plain masks, in one copy: bit c (0..6) of
+ *                             born_masks[k] / survive_masks[k] = born / survive at count c (born "2,4", survive "1,3,5": 0x14, 0x2A);
+ *                             n_masks == 1 (every universe of the range gets the pair) or == count. What is stored is the word
+ *                             ca3d_ensemble_set_rules derives for the same rule. A bit at position 7 or above:
+ *                             CA3D_ERR_INVALID_ARGUMENT naming the universe. Unlike the seed calls this one WAITS for the stream
+ *                             (as ca3d_ensemble_set_rules does): the masks are consumed and the copy is done on return.
+ * NULL handle / spec: CA3D_ERR_INVALID_ARGUMENT ("NULL"), without touching a device. box_min > box_max on an axis, box_max >= G,
+ * and_rounds > 31, n_specs / n_masks neither 1 nor count: CA3D_ERR_INVALID_ARGUMENT. Not configured: CA3D_ERR_NOT_CONFIGURED.
+ */
+typedef struct ca3d_seed
+{
+	uint32_t seed;        /* host.random_fill's seed */
+	uint32_t and_rounds;  /* 0..31: density 2^-(1+and_rounds); > 31: CA3D_ERR_INVALID_ARGUMENT */
+	uint32_t box_min[3];  /* x, y, z inclusive, GLOBAL cell coordinates (as ca3d_summary's box) */
+	uint32_t box_max[3];  /* cells outside the box are dead; the whole grid is {0,0,0}..{G-1,G-1,G-1} */
+} ca3d_seed;
+int ca3d_seed_state(ca3d_t *h, const ca3d_seed *spec);
+int ca3d_group_seed_state(ca3d_group_t *g, const ca3d_seed *spec);
+int ca3d_ensemble_seed_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const ca3d_seed *specs, uint32_t n_specs);
+int ca3d_ensemble_set_rule_tables(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *born_masks, const uint32_t *survive_masks,
+                                  uint32_t n_masks);
 
 /* Resident launches that gave up (a wait for neighbour tile faces timed out: not all workgroups were on the chip) and
  * whose steps the engine re-ran through the per-step kernels, since ca3d_create. The calls that noticed returned CA3D_OK
