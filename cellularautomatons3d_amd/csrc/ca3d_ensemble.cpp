@@ -1,8 +1,8 @@
-// ca3d_ensemble_*: many independent 64^3 universes side by side on one device (include/ca3d.h). One workgroup of ca_ensemble_vn64
-// (ca_ensemble.hip) steps one universe with its state in registers; a launch over B workgroups is B universes, each with its own von
-// Neumann rule table, its own step counter, its own summary record and — in ca3d_ensemble_step_until — its own moment to stop. The host
-// side is bookkeeping: the per-universe arrays, the rule canonicalisation (the engine's own, rules.cpp), and cutting long calls into
-// launches of at most kEnsembleMaxSteps steps.
+// ca3d_ensemble_*: many independent 64^3 universes side by side on one device (include/ca3d.h). One workgroup of ca_ensemble_vn64 or
+// ca_ensemble_moore64 (ca_ensemble.hip; the ensemble's neighbourhood decides) steps one universe with its state in registers; a launch
+// over B workgroups is B universes, each with its own rule table pair, its own step counter, its own summary record and — in
+// ca3d_ensemble_step_until — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
+// (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
 #include <cstring>
 #include <new>
 #include <string>
@@ -18,6 +18,7 @@ struct ca3d_ensemble
 	hipStream_t stream = nullptr;
 	hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 	uint32_t n = 0; // universes; 0: not configured
+	int neighbourhood = CA3D_ENSEMBLE_VON_NEUMANN; // of every universe: the kernel, and ensemble_rule_words() words of `rules` each
 	uint32_t *state = nullptr, *prev = nullptr, *rules = nullptr, *steps_done = nullptr, *reason = nullptr;
 	ca3d_summary *records = nullptr;
 	// ca3d_ensemble_seed_state with one spec per universe: the specs on the device, their pinned staging copy (n entries each, allocated
@@ -69,10 +70,65 @@ EnsembleLaunch launch_of(const ca3d_ensemble *e)
 	EnsembleLaunch l{};
 	l.state = e->state; l.prev = e->prev;
 	l.rules = e->rules;
+	l.neighbourhood = e->neighbourhood;
 	l.records = e->records;
 	l.steps_done = e->steps_done; l.reason = e->reason;
 	l.first = 0; l.count = e->n;
 	return l;
+}
+
+bool moore(const ca3d_ensemble *e) { return e->neighbourhood == CA3D_ENSEMBLE_MOORE; }
+uint32_t table_bits(const ca3d_ensemble *e) { return moore(e) ? 27u : 7u; } // counts 0 .. 26 / 0 .. 6
+
+// what a universe's born / survive masks are stored as (ca_ensemble.hip reads it back: VnStep::load, MooreStep::load)
+void pack_rule(const ca3d_ensemble *e, uint32_t born, uint32_t survive, uint32_t *out)
+{
+	if (moore(e)) { out[0] = born; out[1] = survive; }
+	else out[0] = survive | born << 8;
+}
+
+// `words`: ensemble_rule_words() words for each of universes [first, first + count)
+int store_rules(ca3d_ensemble *e, uint32_t first, uint32_t count, const std::vector<uint32_t> &words)
+{
+	const uint32_t per = ensemble_rule_words(e->neighbourhood);
+	HIP_TRY(hipSetDevice(e->device));
+	// stream-ordered behind the steps already enqueued, which keep the rules they were enqueued under; the source is consumed on return
+	HIP_TRY(hipMemcpyAsync(e->rules + (size_t)first * per, words.data(), (size_t)count * per * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_rules[u]) { e->has_rules[u] = 1; e->missing_rules--; }
+	return CA3D_OK;
+}
+
+int configure_ensemble(ca3d_ensemble *e, uint32_t grid_size, uint32_t n_universes, int neighbourhood)
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (neighbourhood != CA3D_ENSEMBLE_VON_NEUMANN && neighbourhood != CA3D_ENSEMBLE_MOORE)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown ensemble neighbourhood %d (CA3D_ENSEMBLE_VON_NEUMANN = 0, CA3D_ENSEMBLE_MOORE = 1)", neighbourhood);
+	if (grid_size != 64u) return fail(CA3D_ERR_UNSUPPORTED, "an ensemble steps 64^3 universes only (got %u): one workgroup holds one universe in its registers", grid_size);
+	if (n_universes == 0 || n_universes > (1u << 20)) return fail(CA3D_ERR_INVALID_ARGUMENT, "an ensemble holds 1 to %u universes (got %u)", 1u << 20, n_universes);
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	free_arrays(e);
+	const size_t state_bytes = (size_t)n_universes * kEnsembleWords * sizeof(uint32_t), word_bytes = (size_t)n_universes * sizeof(uint32_t);
+	hipError_t err = hipMalloc((void **)&e->state, state_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->prev, state_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->rules, word_bytes * ensemble_rule_words(neighbourhood));
+	if (err == hipSuccess) err = hipMalloc((void **)&e->steps_done, word_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->reason, word_bytes);
+	if (err == hipSuccess) err = hipMalloc((void **)&e->records, (size_t)n_universes * sizeof(ca3d_summary));
+	if (err != hipSuccess)
+	{
+		free_arrays(e);
+		(void)hipGetLastError();
+		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating %u universes: %s", n_universes, hipGetErrorString(err));
+	}
+	e->n = n_universes;
+	e->neighbourhood = neighbourhood;
+	e->has_rules.assign(n_universes, 0);
+	e->has_state.assign(n_universes, 0);
+	e->missing_rules = e->missing_state = n_universes;
+	return CA3D_OK;
 }
 
 // `total` steps at most for every universe, as launches of at most kEnsembleMaxSteps steps whose ends fall on check points; with a
@@ -158,29 +214,21 @@ CA3D_API_CATCH
 
 int ca3d_ensemble_configure(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes) CA3D_API_TRY
 {
-	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
-	if (grid_size != 64u) return fail(CA3D_ERR_UNSUPPORTED, "an ensemble steps 64^3 universes only (got %u): one workgroup holds one universe in its registers", grid_size);
-	if (n_universes == 0 || n_universes > (1u << 20)) return fail(CA3D_ERR_INVALID_ARGUMENT, "an ensemble holds 1 to %u universes (got %u)", 1u << 20, n_universes);
-	HIP_TRY(hipSetDevice(e->device));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	free_arrays(e);
-	const size_t state_bytes = (size_t)n_universes * kEnsembleWords * sizeof(uint32_t), word_bytes = (size_t)n_universes * sizeof(uint32_t);
-	hipError_t err = hipMalloc((void **)&e->state, state_bytes);
-	if (err == hipSuccess) err = hipMalloc((void **)&e->prev, state_bytes);
-	if (err == hipSuccess) err = hipMalloc((void **)&e->rules, word_bytes);
-	if (err == hipSuccess) err = hipMalloc((void **)&e->steps_done, word_bytes);
-	if (err == hipSuccess) err = hipMalloc((void **)&e->reason, word_bytes);
-	if (err == hipSuccess) err = hipMalloc((void **)&e->records, (size_t)n_universes * sizeof(ca3d_summary));
-	if (err != hipSuccess)
-	{
-		free_arrays(e);
-		(void)hipGetLastError();
-		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating %u universes: %s", n_universes, hipGetErrorString(err));
-	}
-	e->n = n_universes;
-	e->has_rules.assign(n_universes, 0);
-	e->has_state.assign(n_universes, 0);
-	e->missing_rules = e->missing_state = n_universes;
+	return configure_ensemble(e, grid_size, n_universes, CA3D_ENSEMBLE_VON_NEUMANN);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_configure_neighbourhood(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes, int neighbourhood) CA3D_API_TRY
+{
+	return configure_ensemble(e, grid_size, n_universes, neighbourhood);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_get_neighbourhood(ca3d_ensemble_t *e, int *out) CA3D_API_TRY
+{
+	if (!e || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called");
+	*out = e->neighbourhood;
 	return CA3D_OK;
 }
 CA3D_API_CATCH
@@ -198,21 +246,29 @@ int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe, const int32_t
 	std::string err;
 	rc = canonicalize_rules(main_offsets, n_main, edges_offsets, n_edges, corners_offsets, n_corners, survive, born, &r, &err);
 	if (rc) return fail(rc, "%s: %s", who.c_str(), err.c_str());
-	if (!vn_rule_applies(r, -1))
-		return fail(CA3D_ERR_UNSUPPORTED, "%s: an ensemble takes rules that reduce to a von Neumann table pair (main list von Neumann, edges / corners tables that cannot fire)",
-		            who.c_str());
 	uint32_t lut_s, lut_b;
-	vn_tables(r, &lut_s, &lut_b);
-	const uint32_t word = (lut_s & 0x7Fu) | (lut_b & 0x7Fu) << 8;
+	if (moore(e))
+	{
+		if (r.main != MAIN_MOORE || !side_tables_silent(r))
+			return fail(CA3D_ERR_UNSUPPORTED, "%s: this ensemble is Moore and takes rules that reduce to a Moore table pair (main list Moore, edges / corners tables that cannot fire)",
+			            who.c_str());
+		lut_s = r.onset_survive[0];
+		lut_b = r.onset_born[0];
+	}
+	else
+	{
+		if (!vn_rule_applies(r, -1))
+			return fail(CA3D_ERR_UNSUPPORTED, "%s: an ensemble takes rules that reduce to a von Neumann table pair (main list von Neumann, edges / corners tables that cannot fire)",
+			            who.c_str());
+		vn_tables(r, &lut_s, &lut_b);
+	}
+	const uint32_t mask = (1u << table_bits(e)) - 1u, per = ensemble_rule_words(e->neighbourhood);
+	uint32_t one[2];
+	pack_rule(e, lut_b & mask, lut_s & mask, one);
 	const uint32_t first = all ? 0u : universe, count = all ? e->n : 1u;
-	const std::vector<uint32_t> words(count, word);
-	HIP_TRY(hipSetDevice(e->device));
-	// stream-ordered behind the steps already enqueued, which keep the rules they were enqueued under; the source is consumed on return
-	HIP_TRY(hipMemcpyAsync(e->rules + first, words.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	for (uint32_t u = first; u < first + count; u++)
-		if (!e->has_rules[u]) { e->has_rules[u] = 1; e->missing_rules--; }
-	return CA3D_OK;
+	std::vector<uint32_t> words((size_t)count * per);
+	for (size_t k = 0; k < words.size(); k++) words[k] = one[k % per];
+	return store_rules(e, first, count, words);
 }
 CA3D_API_CATCH
 
@@ -286,21 +342,17 @@ int ca3d_ensemble_set_rule_tables(ca3d_ensemble_t *e, uint32_t first, uint32_t c
 	int rc = check_range(e, first, count);
 	if (rc) return rc;
 	if (n_masks != 1u && n_masks != count) return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes take 1 or %u mask pairs (got %u)", count, count, n_masks);
-	std::vector<uint32_t> words(count);
+	const uint32_t bits = table_bits(e), per = ensemble_rule_words(e->neighbourhood);
+	std::vector<uint32_t> words((size_t)count * per);
 	for (uint32_t k = 0; k < count; k++)
 	{
 		const uint32_t b = born_masks[n_masks == 1u ? 0u : k], s = survive_masks[n_masks == 1u ? 0u : k];
-		if ((b | s) & ~0x7Fu)
-			return fail(CA3D_ERR_INVALID_ARGUMENT, "universe %u: born mask %#x / survive mask %#x — a von Neumann count is 0 .. 6, bits 7 and above mean nothing", first + k, b, s);
-		words[k] = (s & 0x7Fu) | (b & 0x7Fu) << 8; // the word ca3d_ensemble_set_rules stores (vn_tables)
+		if ((b | s) >> bits)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "universe %u: born mask %#x / survive mask %#x — a %s count is 0 .. %u, bits %u and above mean nothing", first + k, b, s,
+			            moore(e) ? "Moore" : "von Neumann", bits - 1u, bits);
+		pack_rule(e, b, s, &words[(size_t)k * per]); // what ca3d_ensemble_set_rules stores
 	}
-	HIP_TRY(hipSetDevice(e->device));
-	// stream-ordered behind the steps already enqueued, which keep the rules they were enqueued under; the source is consumed on return
-	HIP_TRY(hipMemcpyAsync(e->rules + first, words.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	for (uint32_t u = first; u < first + count; u++)
-		if (!e->has_rules[u]) { e->has_rules[u] = 1; e->missing_rules--; }
-	return CA3D_OK;
+	return store_rules(e, first, count, words);
 }
 CA3D_API_CATCH
 

@@ -202,7 +202,8 @@ constexpr uint32_t kEnsembleMaxSteps = 65536;  // steps of one launch at most: a
 struct EnsembleLaunch
 {
 	uint32_t *state, *prev;   // [B][8192] current state / the state one step earlier
-	const uint32_t *rules;    // [B] von Neumann tables: lut_s | lut_b << 8 (7 bits each, vn_tables)
+	const uint32_t *rules;    // von Neumann: [B] lut_s | lut_b << 8 (7 bits each, vn_tables); Moore: [B][2] born, survive (27 bits each)
+	int neighbourhood;        // CA3D_ENSEMBLE_VON_NEUMANN / CA3D_ENSEMBLE_MOORE: which kernel, and how `rules` reads
 	ca3d_summary *records;    // [B] what the last launch left of each universe
 	uint32_t *steps_done;     // [B] steps taken in the current step-until call (written when stop_mask != 0)
 	uint32_t *reason;         // [B] stop bits that fired in the current call; a universe whose word is set leaves at once
@@ -214,7 +215,8 @@ struct EnsembleLaunch
 	bool reset;               // after an upload: records are rebuilt with step 0 and no previous state (steps == 0)
 };
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream);
-int ensemble_workgroups_per_cu(); // what the runtime says of ca_ensemble_vn64 (0: it cannot tell)
+int ensemble_workgroups_per_cu(int neighbourhood); // what the runtime says of that neighbourhood's kernel (0: it cannot tell)
+constexpr uint32_t ensemble_rule_words(int neighbourhood) { return neighbourhood == CA3D_ENSEMBLE_MOORE ? 2u : 1u; } // per universe
 // ca_seed.hip: the counter-based fill of ca3d_seed (include/ca3d.h) written where the state lives. One launch covers the whole arrays of
 // both ping-pong buffers: array plane a is global plane z0 - ghost + a; the `ghost` planes below and above the owned ones are zeroed.
 struct SeedLaunch
@@ -252,6 +254,7 @@ hipError_t launch_packed_step(const PackedLaunch &l, hipStream_t stream);
 const char *packed_kernel_name(const CanonRules &r, uint32_t G, int variant);
 // ca_packed_vn.hip: the specialised von Neumann kernel (truth-table rules, power-of-two grids)
 bool vn_rule_applies(const CanonRules &r, int variant); // main list von Neumann, edges / corners rule-sets without effect
+bool side_tables_silent(const CanonRules &r);           // class main list, edges / corners tables that cannot fire: the rule IS its main table pair
 bool vn_kernel_applies(const CanonRules &r, uint32_t G, int variant);
 hipError_t launch_packed_vn(const PackedLaunch &l, hipStream_t stream);
 // Canonical truth tables of the von Neumann kernel for these rules (entry 7 is a don't-care: see ca_packed_vn.hip)

@@ -18,6 +18,10 @@
 //     reduction of two bits — any cell alive, any cell changed in the last step — at the price of one extra barrier per check. A
 //     universe whose condition holds writes its state and record and leaves; the CU takes the next workgroup.
 // There are no waits on other workgroups, no spins, and nothing but vector stores.
+//
+// Two kernels share everything but the step: ca_ensemble_vn64 (above) and ca_ensemble_moore64, whose rule is a Moore table pair (27 + 27
+// bits, two words per universe). The body — entry check from the stored record, check points, record reduction, write-back — is
+// ensemble_run<Step>; a Step policy (VnStep, MooreStep) owns the rule's registers, the size of the LDS exchange and one step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -59,23 +63,16 @@ __device__ __forceinline__ u32 wave_or(u32 v)
 	return v;
 }
 
-// Four waves per SIMD = up to 128 registers = one workgroup per CU: cut for 64 registers (two per CU) the step loop spills (DESIGN.md 13)
-__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a)
+// ---- von Neumann: the table pair in one word, lut_s | lut_b << 8 (7 bits each)
+struct VnStep
 {
-	__shared__ u32 xch[2u * kWaves * 2u * 2u * 64u]; // [step parity][wave][first / last plane][word][row]: 32 KiB
-	__shared__ __attribute__((aligned(16))) u32 chk[kWaves]; // per wave: bit 0 a cell is alive, bit 1 a cell changed in the last step
-	__shared__ u64 red64[kWaves][2];
-	__shared__ u32 red32[kWaves][6];
-	const u32 u = a.first + blockIdx.x;
-	const u32 tid = threadIdx.x, row = tid & 63u;
-	const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-	if (a.stop_mask && a.reason[u]) return; // stopped in an earlier launch of the same call
-	auto slot = [&](u32 buf, u32 w, u32 which, u32 h) { return (((buf * kWaves + w) * 2u + which) * 2u + h) * 64u + row; };
-
-	// the rule: leaf[c] = all-ones where a DEAD cell with c live neighbours is born, leaf[7 + c] where a LIVE one survives
+	static constexpr u32 kXchWords = 2u * kWaves * 2u * 2u * 64u; // [step parity][wave][first / last plane][word][row]: 32 KiB
+	// leaf[c] = all-ones where a DEAD cell with c live neighbours is born, leaf[7 + c] where a LIVE one survives
 	u32 leaf[14];
+
+	__device__ __forceinline__ void load(const u32 *rules, u32 u)
 	{
-		const u32 lut = a.rules[u];
+		const u32 lut = rules[u];
 #pragma unroll
 		for (int c = 0; c < 7; c++)
 		{
@@ -85,7 +82,8 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a)
 			asm volatile("" : "+v"(leaf[7 + c]));
 		}
 	}
-	auto rule = [&](u32 w, u32 l, u32 r, u32 ym, u32 yp, u32 below, u32 above) {
+	__device__ __forceinline__ u32 rule(u32 w, u32 l, u32 r, u32 ym, u32 yp, u32 below, u32 above) const
+	{
 		u32 p[3];
 		sum6(l, r, ym, yp, below, above, p);
 		u32 t[7];
@@ -93,7 +91,172 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a)
 		for (int c = 0; c < 7; c++) t[c] = mux(w, leaf[7 + c], leaf[c]);
 		const u32 q0 = mux(p[0], t[1], t[0]), q1 = mux(p[0], t[3], t[2]), q2 = mux(p[0], t[5], t[4]);
 		return mux(p[2], mux(p[1], t[6], q2), mux(p[1], q1, q0));
-	};
+	}
+	static __device__ __forceinline__ u32 slot(u32 buf, u32 w, u32 which, u32 h, u32 row) { return (((buf * kWaves + w) * 2u + which) * 2u + h) * 64u + row; }
+
+	// one step from `s` into `o` (resident64_run's, with the rule as data); buf: the step's parity
+	__device__ __forceinline__ void step(const u32 (&s)[kPT][2], u32 (&o)[kPT][2], u32 *xch, u32 buf, u32 wave, u32 row) const
+	{
+		xch[slot(buf, wave, 0u, 0u, row)] = s[0][0];
+		xch[slot(buf, wave, 0u, 1u, row)] = s[0][1];
+		xch[slot(buf, wave, 1u, 0u, row)] = s[kPT - 1][0];
+		xch[slot(buf, wave, 1u, 1u, row)] = s[kPT - 1][1];
+		auto plane = [&](u32 p, const u32 (&bl)[2], const u32 (&ab)[2]) {
+#pragma unroll
+			for (u32 h = 0; h < 2u; h++)
+			{
+				const u32 w = s[p][h], other = s[p][h ^ 1u];
+				const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
+				const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
+				const u32 ym = dpp_mov<kDppWaveShr1>(w);    // row y - 1 (zero into row 0)
+				const u32 yp = dpp_mov<kDppWaveRol1>(w);    // row y + 1 (row 0 into row 63)
+				o[p][h] = rule(w, l, r, ym, yp, bl[h], ab[h]);
+			}
+		};
+		// the planes that need nothing from another wave first, under the exchange's LDS writes and the other waves' way to the barrier
+#pragma unroll
+		for (u32 p = 1; p + 1u < kPT; p++) plane(p, s[p - 1], s[p + 1]);
+		__syncthreads();
+		u32 below[2], above[2];
+#pragma unroll
+		for (u32 h = 0; h < 2u; h++)
+		{
+			below[h] = wave ? xch[slot(buf, wave - 1u, 1u, h, row)] : 0u;       // z == -1 is dead
+			above[h] = xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)]; // z == 64 is plane 0
+		}
+		plane(0u, below, s[1]);
+		plane(kPT - 1u, s[kPT - 2], above);
+	}
+};
+
+// ---- Moore: two words per universe, born | survive, bit c (0 .. 26) = at c live neighbours of 26
+// The count is separable, the cell itself included: T = sum over the 3 x 3 x 3 cube, 0 .. 27. x: (left, self, right) of a word -> 2 bit
+// planes; y: plus the x-sums of rows y - 1 and y + 1 (DPP) -> 4 bit planes, the PLANE SUM 0 .. 9; z: plus the plane sums of planes z - 1
+// and z + 1 -> 5 bit planes. Every axis applies its own boundary (- dead, + wraps) to what the axis before it produced, which is the
+// reference's per-axis rule on edges and corners too. A dead cell looks up born[T], a live one survive[T - 1]: the survive table is
+// shifted by one when it is loaded and both are indexed by T.
+// The plane sums of a wave's first and last plane go through the LDS exchange (8 words a thread and plane, two ds_write_b128 /
+// ds_read_b128 each) instead of the raw words with the sums recomputed: 4 writes and 8 reads of 16 bytes a step against 4 + 4 of 4 bytes
+// and the x and y sums of four more words, 64 vector instructions.
+struct MooreStep
+{
+	static constexpr u32 kXchWords = 2u * kWaves * 2u * 2u * 64u * 4u; // [step parity][wave][first / last plane][word][row][sum plane]: 128 KiB
+	// The update is a multiplexer tree over (alive, T4 .. T0) with 28 + 28 workgroup-uniform leaves. A select reads ONE scalar operand, so
+	// the born leaves live in vector registers and the (shifted) survive leaves in scalar ones: the leaf level is 28 selects on the
+	// alive word with one operand of each kind.
+	u32 born[28], surv[28];
+
+	__device__ __forceinline__ void load(const u32 *rules, u32 u)
+	{
+		const u32 b = rules[2u * u] & 0x7FFFFFFu, sv = (rules[2u * u + 1u] & 0x7FFFFFFu) << 1; // a live cell has T >= 1
+#pragma unroll
+		for (int c = 0; c < 28; c++)
+		{
+			born[c] = 0u - ((b >> c) & 1u);
+			surv[c] = 0u - ((sv >> c) & 1u);
+			asm volatile("" : "+v"(born[c]));
+			asm volatile("" : "+s"(surv[c]));
+		}
+	}
+	struct Sum4 { u32 b[4]; }; // a plane sum (0 .. 9) of 32 cells as bit planes
+
+	// x and y of one word: the plane sum
+	static __device__ __forceinline__ Sum4 plane_sum(u32 w, u32 other, u32 h)
+	{
+		const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
+		const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
+		u32 x0, x1;
+		fa(l, w, r, x0, x1);
+		const u32 m0 = dpp_mov<kDppWaveShr1>(x0), m1 = dpp_mov<kDppWaveShr1>(x1); // row y - 1 (zero into row 0)
+		const u32 p0 = dpp_mov<kDppWaveRol1>(x0), p1 = dpp_mov<kDppWaveRol1>(x1); // row y + 1 (row 0 into row 63)
+		Sum4 q;
+		u32 c0, s1, c1, k;
+		fa(x0, m0, p0, q.b[0], c0);
+		fa(x1, m1, p1, s1, c1);
+		ha(s1, c0, q.b[1], k);
+		ha(c1, k, q.b[2], q.b[3]);
+		return q;
+	}
+	// z and the rule: three plane sums -> T (5 planes) -> the multiplexer
+	__device__ __forceinline__ u32 rule(u32 w, const Sum4 &a, const Sum4 &b, const Sum4 &c) const
+	{
+		u32 s0, k0, s1, k1, s2, k2, s3, k3;
+		fa(a.b[0], b.b[0], c.b[0], s0, k0);
+		fa(a.b[1], b.b[1], c.b[1], s1, k1);
+		fa(a.b[2], b.b[2], c.b[2], s2, k2);
+		fa(a.b[3], b.b[3], c.b[3], s3, k3);
+		u32 T[5], c1, c2, c3;
+		T[0] = s0;
+		ha(s1, k0, T[1], c1);
+		fa(s2, k1, c1, T[2], c2);
+		fa(s3, k2, c2, T[3], c3);
+		T[4] = k3 | c3; // T <= 27: no carry out
+		u32 t[28];
+#pragma unroll
+		for (int i = 0; i < 28; i++) t[i] = mux(w, surv[i], born[i]);
+#pragma unroll
+		for (int i = 0; i < 14; i++) t[i] = mux(T[0], t[2 * i + 1], t[2 * i]);
+#pragma unroll
+		for (int i = 0; i < 7; i++) t[i] = mux(T[1], t[2 * i + 1], t[2 * i]);
+#pragma unroll
+		for (int i = 0; i < 3; i++) t[i] = mux(T[2], t[2 * i + 1], t[2 * i]);
+		// (T = 28 .. 31 does not exist: counts 24 .. 27 need no select on plane 2)
+		return mux(T[4], mux(T[3], t[6], t[2]), mux(T[3], t[1], t[0]));
+	}
+	// in uint4: a row's four sum planes are one 16-byte access, a wave's 64 rows lie back to back
+	static __device__ __forceinline__ u32 slot(u32 buf, u32 w, u32 which, u32 h, u32 row) { return (((buf * kWaves + w) * 2u + which) * 2u + h) * 64u + row; }
+
+	__device__ __forceinline__ void step(const u32 (&s)[kPT][2], u32 (&o)[kPT][2], u32 *xch, u32 buf, u32 wave, u32 row) const
+	{
+		uint4 *x4 = reinterpret_cast<uint4 *>(xch);
+		auto put = [&](u32 which, u32 h, const Sum4 &v) { x4[slot(buf, wave, which, h, row)] = make_uint4(v.b[0], v.b[1], v.b[2], v.b[3]); };
+		auto get = [&](u32 w, u32 which, u32 h) -> Sum4 {
+			const uint4 v = x4[slot(buf, w, which, h, row)];
+			return Sum4{{v.x, v.y, v.z, v.w}};
+		};
+		// A wave's first and last plane sums go to the exchange and are NOT kept: after the barrier the thread reads its own two back
+		// beside its neighbours' (4 more ds_read_b128 a step), which frees 16 registers across the interior planes' rule evaluation.
+		Sum4 q[kPT - 2][2]; // the interior planes' sums, kept for the outer planes
+#pragma unroll
+		for (u32 h = 0; h < 2u; h++)
+		{
+			const Sum4 first = plane_sum(s[0][h], s[0][h ^ 1u], h), last = plane_sum(s[kPT - 1][h], s[kPT - 1][h ^ 1u], h);
+			put(0u, h, first);
+			put(1u, h, last);
+			// the planes that need nothing from another wave, under the exchange's LDS writes and the other waves' way to the barrier
+#pragma unroll
+			for (u32 p = 1; p + 1u < kPT; p++) q[p - 1u][h] = plane_sum(s[p][h], s[p][h ^ 1u], h);
+#pragma unroll
+			for (u32 p = 1; p + 1u < kPT; p++)
+				o[p][h] = rule(s[p][h], p == 1u ? first : q[p - 2u][h], q[p - 1u][h], p + 2u == kPT ? last : q[p][h]);
+		}
+		__syncthreads();
+#pragma unroll
+		for (u32 h = 0; h < 2u; h++)
+		{
+			Sum4 below = get(wave ? wave - 1u : 0u, 1u, h);
+			if (!wave) below = Sum4{{0u, 0u, 0u, 0u}}; // z == -1 is dead
+			o[0][h] = rule(s[0][h], below, get(wave, 0u, h), q[0][h]);
+			o[kPT - 1][h] = rule(s[kPT - 1][h], q[kPT - 3][h], get(wave, 1u, h), get((wave + 1u) & (kWaves - 1u), 0u, h)); // z == 64 is plane 0
+		}
+	}
+};
+
+// The launch of one universe, whatever its step
+template <typename Step>
+__device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
+{
+	__shared__ __attribute__((aligned(16))) u32 xch[Step::kXchWords];
+	__shared__ __attribute__((aligned(16))) u32 chk[kWaves]; // per wave: bit 0 a cell is alive, bit 1 a cell changed in the last step
+	__shared__ u64 red64[kWaves][2];
+	__shared__ u32 red32[kWaves][6];
+	const u32 u = a.first + blockIdx.x;
+	const u32 tid = threadIdx.x, row = tid & 63u;
+	const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+	if (a.stop_mask && a.reason[u]) return; // stopped in an earlier launch of the same call
+
+	Step step;
+	step.load(a.rules, u);
 
 	u32 *mine = a.state + (size_t)u * kEnsembleWords;
 	// Two register sets that change roles every step: the one a step reads still holds the state one step earlier afterwards,
@@ -153,37 +316,7 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a)
 		}
 		if (t == a.steps) return true;
 
-		// ---- one step (resident64_run's, with the rule as data)
-		const u32 buf = t & 1u;
-		xch[slot(buf, wave, 0u, 0u)] = s[0][0];
-		xch[slot(buf, wave, 0u, 1u)] = s[0][1];
-		xch[slot(buf, wave, 1u, 0u)] = s[kPT - 1][0];
-		xch[slot(buf, wave, 1u, 1u)] = s[kPT - 1][1];
-		auto plane = [&](u32 p, const u32 (&bl)[2], const u32 (&ab)[2]) {
-#pragma unroll
-			for (u32 h = 0; h < 2u; h++)
-			{
-				const u32 w = s[p][h], other = s[p][h ^ 1u];
-				const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
-				const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
-				const u32 ym = dpp_mov<kDppWaveShr1>(w);    // row y - 1 (zero into row 0)
-				const u32 yp = dpp_mov<kDppWaveRol1>(w);    // row y + 1 (row 0 into row 63)
-				o[p][h] = rule(w, l, r, ym, yp, bl[h], ab[h]);
-			}
-		};
-		// the planes that need nothing from another wave first, under the exchange's LDS writes and the other waves' way to the barrier
-#pragma unroll
-		for (u32 p = 1; p + 1u < kPT; p++) plane(p, s[p - 1], s[p + 1]);
-		__syncthreads();
-		u32 below[2], above[2];
-#pragma unroll
-		for (u32 h = 0; h < 2u; h++)
-		{
-			below[h] = wave ? xch[slot(buf, wave - 1u, 1u, h)] : 0u;       // z == -1 is dead
-			above[h] = xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h)]; // z == 64 is plane 0
-		}
-		plane(0u, below, s[1]);
-		plane(kPT - 1u, s[kPT - 2], above);
+		step.step(s, o, xch, t & 1u, wave, row);
 		t++;
 		until--;
 		return false;
@@ -292,6 +425,14 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a)
 	}
 }
 
+
+// Four waves per SIMD = up to 128 registers = one workgroup per CU: cut for 64 registers (two per CU) the step loop spills (DESIGN.md 13)
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a) { ensemble_run<VnStep>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64(EnsembleArgs a) { ensemble_run<MooreStep>(a); }
+
+// the one place that maps an ensemble's neighbourhood to its kernel
+auto kernel_of(int neighbourhood) -> void (*)(EnsembleArgs) { return neighbourhood == CA3D_ENSEMBLE_MOORE ? ca_ensemble_moore64 : ca_ensemble_vn64; }
+
 } // namespace
 
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
@@ -309,14 +450,14 @@ hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 	a.first_check = into ? l.check_every - into : 0u;
 	a.final = l.final ? 1u : 0u;
 	a.reset = l.reset ? 1u : 0u;
-	hipLaunchKernelGGL(ca_ensemble_vn64, dim3(l.count), dim3(kThreads), 0, stream, a);
+	hipLaunchKernelGGL(kernel_of(l.neighbourhood), dim3(l.count), dim3(kThreads), 0, stream, a);
 	return hipGetLastError();
 }
 
-int ensemble_workgroups_per_cu()
+int ensemble_workgroups_per_cu(int neighbourhood)
 {
 	int per_cu = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)ca_ensemble_vn64, (int)kThreads, 0) != hipSuccess)
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel_of(neighbourhood), (int)kThreads, 0) != hipSuccess)
 	{
 		(void)hipGetLastError();
 		return 0;

@@ -71,9 +71,9 @@ int log2_exact(u32 x)
 } // namespace
 
 // The rule reduces to two truth tables over the von Neumann count ...
-bool vn_rule_applies(const CanonRules &r, int variant)
+bool side_tables_silent(const CanonRules &r)
 {
-	if (variant == 1 || !r.fast || r.main != MAIN_VN) return false;
+	if (!r.fast) return false;
 	for (int s = 1; s < 3; s++)
 	{
 		const uint32_t reachable = (2u << r.lists.n[s]) - 1u;
@@ -81,6 +81,8 @@ bool vn_rule_applies(const CanonRules &r, int variant)
 	}
 	return true;
 }
+
+bool vn_rule_applies(const CanonRules &r, int variant) { return variant != 1 && r.main == MAIN_VN && side_tables_silent(r); }
 
 // ... and the grid is a power of two in [256, 8192].
 bool vn_kernel_applies(const CanonRules &r, uint32_t G, int variant)

@@ -1,6 +1,6 @@
 """`Ensemble`: many independent 64^3 universes stepped side by side by one kernel launch (`ca3d_ensemble_*`, include/ca3d.h).
 
-Every universe has its own von Neumann rule, its own step counter, its own summary record and — in `step_until` — its own moment
+Every universe has its own rule (a table pair of the ensemble's neighbourhood, von Neumann or Moore), its own step counter, its own summary record and — in `step_until` — its own moment
 to stop. No reference counterpart: its UI runs one grid.
 """
 from __future__ import annotations
@@ -18,6 +18,7 @@ _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
 
 ALL = ENSEMBLE_ALL
+NEIGHBOURHOODS = ("von neumann", "moore")  # index = enum ca3d_ensemble_neighbourhood
 
 
 class Ensemble:
@@ -48,9 +49,19 @@ class Ensemble:
     def __exit__(self, *exc):
         self.close()
 
-    def configure(self, n: int, grid_size: int = 64) -> None:
-        _capi.check(self._lib.ca3d_ensemble_configure(self._h, grid_size, n))
+    def configure(self, n: int, grid_size: int = 64, neighbourhood: str = "von neumann") -> None:
+        """`neighbourhood`: "von neumann" or "moore" — of every universe; the rules set afterwards must be of that kind."""
+        if neighbourhood not in NEIGHBOURHOODS:
+            raise ValueError(f"unknown ensemble neighbourhood {neighbourhood!r}: one of {NEIGHBOURHOODS}")
+        _capi.check(self._lib.ca3d_ensemble_configure_neighbourhood(self._h, grid_size, n, NEIGHBOURHOODS.index(neighbourhood)))
         self.n, self.grid_size = n, grid_size
+
+    @property
+    def neighbourhood(self) -> str:
+        """The configured neighbourhood (`Ca3dError` -2 before `configure`)."""
+        nb = C.c_int()
+        _capi.check(self._lib.ca3d_ensemble_get_neighbourhood(self._h, C.byref(nb)))
+        return NEIGHBOURHOODS[nb.value]
 
     def set_rules(self, u: int, main_offsets, edges_offsets, corners_offsets, survive, born) -> None:
         """The payload of `Engine.set_rules` for universe `u` (`ensemble.ALL`: every universe)."""
@@ -94,7 +105,7 @@ class Ensemble:
         _capi.check(self._lib.ca3d_ensemble_seed_state(self._h, first, count, specs, len(specs)))
 
     def set_rule_tables(self, first: int, born_masks, survive_masks, count: Optional[int] = None) -> None:
-        """`ca3d_ensemble_set_rule_tables`: von Neumann rules as masks (bit c = born / survive at count c, c in 0..6) for universes from
+        """`ca3d_ensemble_set_rule_tables`: rules as masks (bit c = born / survive at count c; c in 0..6, Moore ensembles 0..26) for universes from
         `first`, in one call. Arrays: one pair per universe (a scalar beside an array is repeated per universe); two scalars: that pair
         for `count` universes (default: all from `first`). Waits for the stream, as `set_rules` does."""
         b, s = np.atleast_1d(_as_u32(born_masks)), np.atleast_1d(_as_u32(survive_masks))

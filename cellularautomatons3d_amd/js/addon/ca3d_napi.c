@@ -1005,6 +1005,37 @@ static napi_value js_ensemble_configure(napi_env env, napi_callback_info info)
 	return undefined(env);
 }
 
+/* ensembleConfigureNeighbourhood(handle, gridSize, n, neighbourhood): 0 von Neumann, 1 Moore (enum ca3d_ensemble_neighbourhood) */
+static napi_value js_ensemble_configure_neighbourhood(napi_env env, napi_callback_info info)
+{
+	napi_value argv[4];
+	if (!get_args(env, info, 4, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t grid, n, nb;
+	if (!e || !get_u32(env, argv[1], &grid) || !get_u32(env, argv[2], &n) || !get_u32(env, argv[3], &nb)) return NULL;
+	int rc = ca3d_ensemble_configure_neighbourhood(e, grid, n, (int)nb);
+	if (rc) return throw_ca3d(env, rc);
+	void *p = NULL;
+	napi_get_value_external(env, argv[0], &p);
+	((EnsembleSlot *)p)->n = n;
+	return undefined(env);
+}
+
+/* ensembleNeighbourhood(handle) -> 0 | 1 */
+static napi_value js_ensemble_neighbourhood(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	if (!e) return NULL;
+	int nb = 0;
+	int rc = ca3d_ensemble_get_neighbourhood(e, &nb);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_int32(env, nb, &v);
+	return v;
+}
+
 /* ensembleSetRules(handle, universe | 0xFFFFFFFF, main, edges, corners, survive, born) */
 static napi_value js_ensemble_set_rules(napi_env env, napi_callback_info info)
 {
@@ -1276,7 +1307,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleStep", js_ensemble_step}, {"ensembleStepUntil", js_ensemble_step_until}, {"ensembleSummaries", js_ensemble_summaries},
 	    {"ensembleSynchronize", js_ensemble_synchronize}, {"ensembleStats", js_ensemble_stats},
 	    {"seedState", js_seed_state}, {"groupSeedState", js_group_seed_state}, {"ensembleSeedState", js_ensemble_seed_state},
-	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables}};
+	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables},
+	    {"ensembleConfigureNeighbourhood", js_ensemble_configure_neighbourhood}, {"ensembleNeighbourhood", js_ensemble_neighbourhood}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

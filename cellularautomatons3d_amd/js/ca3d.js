@@ -397,8 +397,10 @@ class EngineGroup
 }
 
 // ca3d_ensemble_*: `n` independent 64^3 universes (8192 packed words each) stepped side by side by one kernel launch, each with its
-// own von Neumann rule, step counter, summary record and — in stepUntil — its own moment to stop (include/ca3d.h). Synchronous.
+// own rule (a table pair of the ensemble's neighbourhood, von Neumann or Moore), step counter, summary record and — in stepUntil — its
+// own moment to stop (include/ca3d.h). Synchronous.
 const ENSEMBLE_ALL = 0xFFFFFFFF, ENSEMBLE_WORDS = 8192;
+const ENSEMBLE_NEIGHBOURHOODS = ["von neumann", "moore"]; // index = enum ca3d_ensemble_neighbourhood
 class Ensemble
 {
 	constructor(device)
@@ -408,7 +410,16 @@ class Ensemble
 		this.n = 0;
 	}
 	close() { if (this._e) { this._a.ensembleDestroy(this._e); this._e = null; } }
-	configure(n, gridSize) { this._a.ensembleConfigure(this._e, gridSize === undefined ? 64 : gridSize, n); this.n = n; }
+	/** neighbourhood: "von neumann" (default) or "moore" — of every universe; the rules set afterwards must be of that kind */
+	configure(n, gridSize, neighbourhood)
+	{
+		const nb = ENSEMBLE_NEIGHBOURHOODS.indexOf(neighbourhood === undefined ? "von neumann" : neighbourhood);
+		if (nb < 0) throw new Error(`unknown ensemble neighbourhood ${JSON.stringify(neighbourhood)}: "von neumann" or "moore"`);
+		this._a.ensembleConfigureNeighbourhood(this._e, gridSize === undefined ? 64 : gridSize, n, nb);
+		this.n = n;
+	}
+	/** the configured neighbourhood as its string (throws before configure) */
+	get neighbourhood() { return ENSEMBLE_NEIGHBOURHOODS[this._a.ensembleNeighbourhood(this._e)]; }
 	/** universe: an index, or ENSEMBLE_ALL */
 	setRules(universe, mainOffsets, edgesOffsets, cornersOffsets, survive, born) { this._a.ensembleSetRules(this._e, universe, mainOffsets, edgesOffsets, cornersOffsets, survive, born); }
 	setRuleStrings(universe, rules)
@@ -429,7 +440,7 @@ class Ensemble
 		list.forEach((s, k) => words.set(seedSpec(64, s), 8 * k));
 		this._a.ensembleSeedState(this._e, first, count, words);
 	}
-	/** ca3d_ensemble_set_rule_tables: von Neumann rules as masks (bit c = born / survive at count c, c in 0..6), one pair per universe
+	/** ca3d_ensemble_set_rule_tables: rules as masks (bit c = born / survive at count c; c in 0..6, Moore ensembles 0..26), one pair per universe
 	 *  from `first` (arrays), or one pair (numbers) for `count` universes (default: all from `first`) — one call, one copy */
 	setRuleTables(first, bornMasks, surviveMasks, count)
 	{

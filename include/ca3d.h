@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_*; + ca3d_seed_state, ca3d_group_seed_state, ca3d_ensemble_seed_state, ca3d_ensemble_set_rule_tables */
+#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_*; + ca3d_seed_state, ca3d_group_seed_state, ca3d_ensemble_seed_state, ca3d_ensemble_set_rule_tables; + ca3d_ensemble_configure_neighbourhood, ca3d_ensemble_get_neighbourhood */
 #define CA3D_LUT_LEN 81 /* 3 rule-sets x 27 slots (main_pathtraced.js:10, 155-159) */
 
 typedef struct ca3d_engine ca3d_t;
@@ -312,9 +312,11 @@ int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_
  * runs one grid). For hosts that ask "what becomes of this rule / seed?" of thousands of pairs: one ca3d_t steps one universe on one
  * CU of 256 and pays a launch, a rule set-up and a summary pass per universe; here one workgroup holds one universe in its registers
  * (the layout of the engine's own 64^3 resident kernel), a launch is B such workgroups, and every universe has
- *   - its own RULE, as data: the payload of ca3d_set_rules, canonicalised as there, which must reduce to a von Neumann table pair —
- *     main list von Neumann, edges / corners tables that cannot fire; anything else is refused with CA3D_ERR_UNSUPPORTED and a message
- *     that names the universe. Moore and clustered rules as data are out of scope here (a ca3d_t compiles them at run time);
+ *   - its own RULE, as data: the payload of ca3d_set_rules, canonicalised as there, which must reduce to the table pair of the
+ *     ENSEMBLE'S NEIGHBOURHOOD — main list von Neumann (7 + 7 table bits, counts 0 .. 6) or Moore (27 + 27 bits, counts 0 .. 26), edges /
+ *     corners tables that cannot fire; anything else is refused with CA3D_ERR_UNSUPPORTED and a message that names the universe. The
+ *     neighbourhood is chosen when the ensemble is configured and the two kinds never mix in one ensemble: a Moore ensemble refuses a von
+ *     Neumann payload and the other way round. Clustered rules as data are out of scope here (a ca3d_t compiles them at run time);
  *   - its own ca3d_summary RECORD, reduced from the registers at the end of every launch: ca3d_ensemble_summarize only copies records
  *     (nothing state-sized moves). Field meanings as above with G = 64; `step` counts the universe's own steps since its last upload,
  *     has_previous is 1 once it has taken one, and the digest's word index is the index in the universe's own array, so a record
@@ -341,7 +343,18 @@ struct ca3d_stats;
 #define CA3D_ENSEMBLE_ALL 0xFFFFFFFFu
 int ca3d_ensemble_create(int device, ca3d_ensemble_t **out);
 int ca3d_ensemble_destroy(ca3d_ensemble_t *e);
-int ca3d_ensemble_configure(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes);
+int ca3d_ensemble_configure(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes); /* the CA3D_ENSEMBLE_VON_NEUMANN case of the next one */
+/* The neighbourhood every universe of the ensemble counts over (one kernel each: ca_ensemble_vn64, ca_ensemble_moore64). Configuring
+ * again replaces universes, rules and neighbourhood. An unknown value: CA3D_ERR_INVALID_ARGUMENT. ca3d_ensemble_get_neighbourhood
+ * before any configure: CA3D_ERR_NOT_CONFIGURED. Everything else — upload, seed, read, step, step_until, summarize, get_stats — means
+ * in a Moore ensemble what it means in a von Neumann one. */
+enum ca3d_ensemble_neighbourhood
+{
+	CA3D_ENSEMBLE_VON_NEUMANN = 0,
+	CA3D_ENSEMBLE_MOORE = 1
+};
+int ca3d_ensemble_configure_neighbourhood(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes, int neighbourhood);
+int ca3d_ensemble_get_neighbourhood(ca3d_ensemble_t *e, int *out);
 int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe,
                             const int32_t *main_offsets, uint32_t n_main,
                             const int32_t *edges_offsets, uint32_t n_edges,
@@ -384,11 +397,12 @@ int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
  *                             followed by the zero-step record launch of ca3d_ensemble_upload_state (records at step 0, has_previous
  *                             0); `specs` is consumed when the call returns, the fill may still be running. Universes outside the
  *                             range keep state, step counter and record.
- *   ca3d_ensemble_set_rule_tables  von Neumann tables for universes [first, first + count) as plain masks, in one copy: bit c (0..6) of
+ *   ca3d_ensemble_set_rule_tables  the tables of universes [first, first + count) as plain masks, in one copy: bit c of
  *                             born_masks[k] / survive_masks[k] = born / survive at count c (born "2,4", survive "1,3,5": 0x14, 0x2A);
- *                             n_masks == 1 (every universe of the range gets the pair) or == count. What is stored is the word
- *                             ca3d_ensemble_set_rules derives for the same rule. A bit at position 7 or above:
- *                             CA3D_ERR_INVALID_ARGUMENT naming the universe. Unlike the seed calls this one WAITS for the stream
+ *                             c is 0..6 in a von Neumann ensemble and 0..26 in a Moore one (27-bit masks: born "5-7", survive
+ *                             "4-6": 0xE0, 0x70). n_masks == 1 (every universe of the range gets the pair) or == count. What is
+ *                             stored is what ca3d_ensemble_set_rules derives for the same rule. A bit at position 7 (27 in a Moore
+ *                             ensemble) or above: CA3D_ERR_INVALID_ARGUMENT naming the universe. Unlike the seed calls this one WAITS for the stream
  *                             (as ca3d_ensemble_set_rules does): the masks are consumed and the copy is done on return.
  * NULL handle / spec: CA3D_ERR_INVALID_ARGUMENT ("NULL"), without touching a device. box_min > box_max on an axis, box_max >= G,
  * and_rounds > 31, n_specs / n_masks neither 1 nor count: CA3D_ERR_INVALID_ARGUMENT. Not configured: CA3D_ERR_NOT_CONFIGURED.

@@ -9,6 +9,10 @@ through one engine would pay on top.
 
     python tools/bench_ensemble.py --out profiles/ensemble_64.json --commit <hash>
 
+--neighbourhood moore measures a Moore ensemble (ca_ensemble_moore64, rule B5-7 / S4-6) against the same sweep through one Engine, which
+for a Moore rule at 64^3 is one launch per step of the kernel compiled for the rule; same protocol, written to
+profiles/ensemble_moore_64.json unless --out says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -28,7 +32,8 @@ import numpy as np  # noqa: E402
 from cellularautomatons3d_amd import Engine, Ensemble, _capi, host  # noqa: E402
 
 G, W, CELLS = 64, 8192, 64 ** 3
-BORN, SURVIVE = "2,4", "1,3,5"
+RULES = {"von neumann": ("2,4", "1,3,5"), "moore": ("5-7", "4-6")}  # born, survive
+KERNELS = {"von neumann": "ca_ensemble_vn64", "moore": "ca_ensemble_moore64"}
 
 
 def fills(B):
@@ -67,9 +72,14 @@ def main():
     ap.add_argument("--steps", type=int, default=256, help="steps per launch")
     ap.add_argument("--repeats", type=int, default=5, help="alternating measurements per path; the median is reported")
     ap.add_argument("--min-seconds", type=float, default=0.25, help="work per measurement")
-    ap.add_argument("--out", default=None, help="JSON file to write")
+    ap.add_argument("--neighbourhood", choices=sorted(RULES), default="von neumann", help="of the ensemble and of the rule both paths run")
+    ap.add_argument("--out", default=None, help="JSON file to write (moore: profiles/ensemble_moore_64.json)")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
+    nb = args.neighbourhood
+    born, survive = RULES[nb]
+    if args.out is None and nb == "moore":
+        args.out = os.path.join(ROOT, "profiles", "ensemble_moore_64.json")
     commit = args.commit
     if commit is None:
         try:
@@ -79,13 +89,13 @@ def main():
 
     eng, ens = Engine(0), Ensemble(0)
     eng.configure(G)
-    eng.set_rule_strings(born=BORN, survive=SURVIVE)
+    eng.set_rule_strings(neighbourhood=nb, born=born, survive=survive)
     eng.set_option("stats", 0)  # no event pair per call: the baseline at its best
     rows = []
     for B in args.universes:
         words = fills(B)
-        ens.configure(B)
-        ens.set_rule_strings(_capi.ENSEMBLE_ALL, born=BORN, survive=SURVIVE)
+        ens.configure(B, neighbourhood=nb)
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood=nb, born=born, survive=survive)
         sample = range(B) if B <= 256 else sorted(set(range(0, B, max(1, B // 64))) | {255, 256, B - 1})
         verify(ens, eng, words, args.steps, sample)
         eng.upload_state(words[0])
@@ -120,9 +130,9 @@ def main():
     kernel = eng.info().kernel_name.decode()
     eng.close(); ens.close()
     result = {
-        "what": "B universes of 64^3, rule B2,4/S1,3,5, random fills (density 1/2): one Ensemble.step(steps) launch vs. B Engine.step(steps) calls",
+        "what": f"B universes of 64^3, {'Moore ' if nb == 'moore' else ''}rule B{born}/S{survive}, random fills (density 1/2): one Ensemble.step(steps) launch vs. B Engine.step(steps) calls",
         "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
-        "ensemble_kernel": "ca_ensemble_vn64 (rule as data)", "baseline_kernel": kernel,
+        "ensemble_kernel": f"{KERNELS[nb]} (rule as data)", "baseline_kernel": kernel,
         "timing": f"host clock around >= {args.min_seconds} s of calls ending in a synchronise; median of {args.repeats} alternating measurements",
         "rows": rows,
     }
