@@ -61,6 +61,7 @@ class SeedStruct(C.Structure):
 
 
 STOP_EXTINCT, STOP_STILL = 1, 2
+STOP_PERIODIC = 4  # ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle only
 ENSEMBLE_ALL = 0xFFFFFFFF
 ENSEMBLE_WORDS = 8192  # words of one 64^3 universe
 
@@ -130,6 +131,7 @@ SYMBOLS = [
     ("ca3d_summarize", C.c_int, [_H, C.POINTER(SummaryStruct), _u32p]),
     ("ca3d_get_summary_time", C.c_int, [_H, C.POINTER(C.c_double)]),
     ("ca3d_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct), _u32p, _u32p]),
+    ("ca3d_step_until_cycle", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct), _u32p, _u32p, _u32p]),
     ("ca3d_ensemble_create", C.c_int, [C.c_int, C.POINTER(_H)]),
     ("ca3d_ensemble_destroy", C.c_int, [_H]),
     ("ca3d_ensemble_configure", C.c_int, [_H, C.c_uint32, C.c_uint32]),
@@ -144,6 +146,7 @@ SYMBOLS = [
     ("ca3d_ensemble_set_rule_tables", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint32]),
     ("ca3d_ensemble_step", C.c_int, [_H, C.c_uint32]),
     ("ca3d_ensemble_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
+    ("ca3d_ensemble_step_until_cycle", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
     ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),

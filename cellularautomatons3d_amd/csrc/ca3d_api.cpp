@@ -113,6 +113,8 @@ static void free_buffers(ca3d_engine *h)
 	h->sum_dev = h->sum_host = nullptr;
 	h->sum_words = 0;
 	h->sum_ev_valid = false;
+	if (h->cycle_anchor) hipFree(h->cycle_anchor);
+	h->cycle_anchor = nullptr;
 }
 
 int bind_device(ca3d_engine *h, bool join)
@@ -642,6 +644,83 @@ int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_
 		rc = ca3d_step(h, n); // the very path of a caller's ca3d_step(n): queue, resident kernels, captured graphs
 		if (rc) return rc;
 		done += n;
+	}
+}
+CA3D_API_CATCH
+
+} // extern "C"
+
+// Is the current state (just summarised: the stream is idle, resident launches are settled) word for word the anchor? One compare kernel
+// (ca_summary.hip); its flag word is the summary block's unused header word 14 and comes back through the pinned copy.
+static int state_is_anchor(ca3d_engine *h, bool *same)
+{
+	uint32_t *flag = h->sum_dev + 14;
+	HIP_TRY(hipMemsetAsync(flag, 0, sizeof(uint32_t), h->stream));
+	hipError_t e = launch_state_equal(h->buf[h->cur], h->cycle_anchor, h->state_words(), flag, h->stream);
+	if (e != hipSuccess) return fail(CA3D_ERR_DEVICE, "compare kernel launch failed: %s", hipGetErrorString(e));
+	HIP_TRY(hipMemcpyAsync(h->sum_host + 14, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(hipStreamSynchronize(h->stream));
+	*same = h->sum_host[14] == 0u;
+	return CA3D_OK;
+}
+
+extern "C"
+{
+
+int ca3d_step_until_cycle(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, ca3d_summary *out, uint32_t *steps_done,
+                          uint32_t *reason, uint32_t *period) CA3D_API_TRY
+{
+	if (!h) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL engine handle");
+	if (steps_done) *steps_done = 0;
+	if (reason) *reason = 0;
+	if (period) *period = 0;
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	if (check_every == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "check_every must be at least 1");
+	if (stop_mask & ~(uint32_t)(CA3D_STOP_EXTINCT | CA3D_STOP_STILL | CA3D_STOP_PERIODIC)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in stop_mask %#x", stop_mask);
+	if (h->configured && h->slab) return fail(CA3D_ERR_UNSUPPORTED, "ca3d_step_until_cycle takes a full-grid engine: a slab's neighbours must step with it");
+	int rc = check_ready(h);
+	if (rc) return rc;
+	// ca3d_step_until's loop with an anchor on Brent's schedule (include/ca3d.h). The summary's digest is the filter: equal states have
+	// equal digests and populations, so anything else proves a difference; a stop is only declared by the compare kernel.
+	uint32_t done = 0, j = 0, anchor_step = 0;
+	uint64_t anchor_digest = 0, anchor_population = 0;
+	for (;;)
+	{
+		rc = summarize_state(h, out, nullptr);
+		if (rc) return rc;
+		uint32_t fired = 0;
+		if (out->population == 0) fired |= CA3D_STOP_EXTINCT;
+		if (out->has_previous && out->births + out->deaths == 0) fired |= CA3D_STOP_STILL;
+		if (j > 0 && (stop_mask & CA3D_STOP_PERIODIC) && out->digest == anchor_digest && out->population == anchor_population)
+		{
+			bool same = false;
+			rc = state_is_anchor(h, &same);
+			if (rc) return rc;
+			if (same) fired |= CA3D_STOP_PERIODIC;
+		}
+		fired &= stop_mask;
+		if (fired || done == max_steps)
+		{
+			if (steps_done) *steps_done = done;
+			if (reason) *reason = fired;
+			if (period && (fired & CA3D_STOP_PERIODIC)) *period = done - anchor_step;
+			return CA3D_OK;
+		}
+		if ((stop_mask & CA3D_STOP_PERIODIC) && (j & (j - 1u)) == 0u) // check points 0, 1, 2, 4, 8 ...: the anchor moves, AFTER the comparison
+		{
+			const size_t bytes = h->state_words() * sizeof(uint32_t);
+			if (!h->cycle_anchor) HIP_TRY(hipMalloc((void **)&h->cycle_anchor, bytes));
+			// the CURRENT buffer (resident launches rotate three): summarize_state settled them and left the stream idle
+			HIP_TRY(hipMemcpyAsync(h->cycle_anchor, h->buf[h->cur], bytes, hipMemcpyDeviceToDevice, h->stream));
+			anchor_step = done;
+			anchor_digest = out->digest;
+			anchor_population = out->population;
+		}
+		const uint32_t n = max_steps - done < check_every ? max_steps - done : check_every;
+		rc = ca3d_step(h, n); // the very path of a caller's ca3d_step(n): queue, resident kernels, captured graphs
+		if (rc) return rc;
+		done += n;
+		j++;
 	}
 }
 CA3D_API_CATCH

@@ -112,6 +112,9 @@ struct ca3d_engine
 	size_t sum_words = 0;
 	hipEvent_t sum_ev0 = nullptr, sum_ev1 = nullptr;
 	bool sum_ev_valid = false;
+	// ca3d_step_until_cycle: the anchor, a device copy of the state at an earlier check point of the call (state_words() words, allocated
+	// at the first call, freed with the buffers)
+	uint32_t *cycle_anchor = nullptr;
 	// the owned planes of buffer [(step + 1) % 2] hold the state one step earlier: set by the step paths that guarantee it, cleared by
 	// everything that writes a buffer any other way (upload, buffers handed out, gathers, the resident slab launch)
 	bool prev_ok = false;

@@ -1,7 +1,7 @@
 // ca3d_ensemble_*: many independent 64^3 universes side by side on one device (include/ca3d.h). One workgroup of ca_ensemble_vn64 or
 // ca_ensemble_moore64 (ca_ensemble.hip; the ensemble's neighbourhood decides) steps one universe with its state in registers; a launch
 // over B workgroups is B universes, each with its own rule table pair, its own step counter, its own summary record and — in
-// ca3d_ensemble_step_until — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
+// ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
 #include <cstring>
 #include <new>
@@ -21,6 +21,9 @@ struct ca3d_ensemble
 	int neighbourhood = CA3D_ENSEMBLE_VON_NEUMANN; // of every universe: the kernel, and ensemble_rule_words() words of `rules` each
 	uint32_t *state = nullptr, *prev = nullptr, *rules = nullptr, *steps_done = nullptr, *reason = nullptr;
 	ca3d_summary *records = nullptr;
+	// ca3d_ensemble_step_until_cycle: every universe's anchor state (n x 32 KiB) and its anchor step / anchor hash / period / unused
+	// (n x 4 words), allocated at the first call that watches CA3D_STOP_PERIODIC, gone with the other arrays at a configure
+	uint32_t *anchor = nullptr, *cycle = nullptr;
 	// ca3d_ensemble_seed_state with one spec per universe: the specs on the device, their pinned staging copy (n entries each, allocated
 	// at the first such call) and the event behind the copy out of it
 	ca3d_seed *seed_dev = nullptr, *seed_host = nullptr;
@@ -38,9 +41,9 @@ namespace
 
 void free_arrays(ca3d_ensemble *e)
 {
-	for (void *p : {(void *)e->state, (void *)e->prev, (void *)e->rules, (void *)e->steps_done, (void *)e->reason, (void *)e->records})
+	for (void *p : {(void *)e->state, (void *)e->prev, (void *)e->rules, (void *)e->steps_done, (void *)e->reason, (void *)e->records, (void *)e->anchor, (void *)e->cycle})
 		if (p) hipFree(p);
-	e->state = e->prev = e->rules = e->steps_done = e->reason = nullptr;
+	e->state = e->prev = e->rules = e->steps_done = e->reason = e->anchor = e->cycle = nullptr;
 	e->records = nullptr;
 	if (e->seed_dev) hipFree(e->seed_dev);
 	if (e->seed_host) hipHostFree(e->seed_host);
@@ -73,6 +76,7 @@ EnsembleLaunch launch_of(const ca3d_ensemble *e)
 	l.neighbourhood = e->neighbourhood;
 	l.records = e->records;
 	l.steps_done = e->steps_done; l.reason = e->reason;
+	l.anchor = e->anchor; l.cycle = e->cycle;
 	l.first = 0; l.count = e->n;
 	return l;
 }
@@ -159,6 +163,63 @@ int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_ma
 	HIP_TRY(hipEventRecord(e->ev_stop, e->stream));
 	e->timed = true;
 	e->last_launches = launches;
+	return CA3D_OK;
+}
+
+// ca3d_ensemble_step_until (known: EXTINCT | STILL, period null) and ca3d_ensemble_step_until_cycle (known: + PERIODIC). Without
+// CA3D_STOP_PERIODIC in the mask the launches are the first call's whatever the entry point: the *_cycle kernels run only when asked for.
+int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t known, uint32_t *steps_done, uint32_t *reason,
+               uint32_t *period)
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (check_every == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "check_every must be at least 1");
+	if (stop_mask & ~known) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in stop_mask %#x", stop_mask);
+	int rc = ensemble_ready(e);
+	if (rc) return rc;
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t word_bytes = (size_t)e->n * sizeof(uint32_t);
+	const bool cycle = (stop_mask & CA3D_STOP_PERIODIC) != 0u;
+	if (cycle && !e->anchor)
+	{
+		hipError_t err = hipMalloc((void **)&e->anchor, (size_t)e->n * kEnsembleWords * sizeof(uint32_t));
+		if (err == hipSuccess && !e->cycle) err = hipMalloc((void **)&e->cycle, 4u * word_bytes);
+		if (err != hipSuccess)
+		{
+			if (e->anchor) hipFree(e->anchor);
+			e->anchor = nullptr;
+			(void)hipGetLastError();
+			return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating the anchors of %u universes: %s", e->n, hipGetErrorString(err));
+		}
+	}
+	std::vector<uint32_t> done(e->n, stop_mask ? 0u : max_steps), fired(e->n, 0u), cyc(cycle ? 4u * (size_t)e->n : 0u, 0u);
+	e->last_launches = 0;
+	e->timed = false;
+	if (stop_mask)
+	{
+		// the kernel keeps both arrays: a universe whose reason word is set leaves the later launches of this call at once
+		HIP_TRY(hipMemsetAsync(e->steps_done, 0, word_bytes, e->stream));
+		HIP_TRY(hipMemsetAsync(e->reason, 0, word_bytes, e->stream));
+		if (cycle) HIP_TRY(hipMemsetAsync(e->cycle, 0, 4u * word_bytes, e->stream)); // no anchor survives a call
+		rc = run(e, max_steps, check_every, stop_mask); // max_steps == 0: one launch that only checks
+		if (rc) return rc;
+		HIP_TRY(hipMemcpyAsync(done.data(), e->steps_done, word_bytes, hipMemcpyDeviceToHost, e->stream));
+		HIP_TRY(hipMemcpyAsync(fired.data(), e->reason, word_bytes, hipMemcpyDeviceToHost, e->stream));
+		if (cycle) HIP_TRY(hipMemcpyAsync(cyc.data(), e->cycle, 4u * word_bytes, hipMemcpyDeviceToHost, e->stream));
+	}
+	else if (max_steps)
+	{
+		rc = run(e, max_steps, 1u, 0u); // nothing to watch: plain stepping
+		if (rc) return rc;
+	}
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	uint64_t sum = 0, most = 0;
+	for (uint32_t d : done) { sum += d; most = d > most ? d : most; }
+	e->last_steps = most;
+	e->last_cell_steps = (double)sum * (double)(64 * 64 * 64);
+	if (steps_done) memcpy(steps_done, done.data(), word_bytes);
+	if (reason) memcpy(reason, fired.data(), word_bytes);
+	if (period)
+		for (uint32_t u = 0; u < e->n; u++) period[u] = cycle ? cyc[4u * (size_t)u + 2u] : 0u;
 	return CA3D_OK;
 }
 
@@ -390,39 +451,14 @@ CA3D_API_CATCH
 int ca3d_ensemble_step_until(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
                              uint32_t *reason) CA3D_API_TRY
 {
-	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
-	if (check_every == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "check_every must be at least 1");
-	if (stop_mask & ~(uint32_t)(CA3D_STOP_EXTINCT | CA3D_STOP_STILL)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in stop_mask %#x", stop_mask);
-	int rc = ensemble_ready(e);
-	if (rc) return rc;
-	HIP_TRY(hipSetDevice(e->device));
-	const size_t word_bytes = (size_t)e->n * sizeof(uint32_t);
-	std::vector<uint32_t> done(e->n, stop_mask ? 0u : max_steps), fired(e->n, 0u);
-	e->last_launches = 0;
-	e->timed = false;
-	if (stop_mask)
-	{
-		// the kernel keeps both arrays: a universe whose reason word is set leaves the later launches of this call at once
-		HIP_TRY(hipMemsetAsync(e->steps_done, 0, word_bytes, e->stream));
-		HIP_TRY(hipMemsetAsync(e->reason, 0, word_bytes, e->stream));
-		rc = run(e, max_steps, check_every, stop_mask); // max_steps == 0: one launch that only checks
-		if (rc) return rc;
-		HIP_TRY(hipMemcpyAsync(done.data(), e->steps_done, word_bytes, hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipMemcpyAsync(fired.data(), e->reason, word_bytes, hipMemcpyDeviceToHost, e->stream));
-	}
-	else if (max_steps)
-	{
-		rc = run(e, max_steps, 1u, 0u); // nothing to watch: plain stepping
-		if (rc) return rc;
-	}
-	HIP_TRY(hipStreamSynchronize(e->stream));
-	uint64_t sum = 0, most = 0;
-	for (uint32_t d : done) { sum += d; most = d > most ? d : most; }
-	e->last_steps = most;
-	e->last_cell_steps = (double)sum * (double)(64 * 64 * 64);
-	if (steps_done) memcpy(steps_done, done.data(), word_bytes);
-	if (reason) memcpy(reason, fired.data(), word_bytes);
-	return CA3D_OK;
+	return step_until(e, max_steps, check_every, stop_mask, CA3D_STOP_EXTINCT | CA3D_STOP_STILL, steps_done, reason, nullptr);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_step_until_cycle(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                                   uint32_t *reason, uint32_t *period) CA3D_API_TRY
+{
+	return step_until(e, max_steps, check_every, stop_mask, CA3D_STOP_EXTINCT | CA3D_STOP_STILL | CA3D_STOP_PERIODIC, steps_done, reason, period);
 }
 CA3D_API_CATCH
 

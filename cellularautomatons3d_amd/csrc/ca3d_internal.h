@@ -195,6 +195,9 @@ struct SummaryLaunch
 	uint32_t z0, nz; // owned planes [z0, z0 + nz) of the grid
 };
 hipError_t launch_summary(const SummaryLaunch &l, hipStream_t stream);
+// ca_summary.hip: ORs 1 into *flag (a device word the caller has zeroed) when the two arrays of n_words words (a multiple of 4, both
+// 16-byte aligned) differ anywhere
+hipError_t launch_state_equal(const uint32_t *a, const uint32_t *b, size_t n_words, uint32_t *flag, hipStream_t stream);
 // ca_ensemble.hip: one launch over universes [first, first + count) of an ensemble of independent 64^3 grids, one workgroup each;
 // every array is indexed by universe (ca3d_ensemble.cpp owns them)
 constexpr uint32_t kEnsembleWords = 8192;      // words of one 64^3 universe
@@ -207,6 +210,8 @@ struct EnsembleLaunch
 	ca3d_summary *records;    // [B] what the last launch left of each universe
 	uint32_t *steps_done;     // [B] steps taken in the current step-until call (written when stop_mask != 0)
 	uint32_t *reason;         // [B] stop bits that fired in the current call; a universe whose word is set leaves at once
+	uint32_t *anchor;         // [B][8192] the state at each universe's anchor check point; [B][4] anchor step, anchor hash, period, unused —
+	uint32_t *cycle;          // both only when stop_mask holds CA3D_STOP_PERIODIC (the *_cycle kernels), else unused and may be null
 	uint32_t first, count;
 	uint32_t steps;           // <= kEnsembleMaxSteps
 	uint32_t base;            // steps the earlier launches of the same call took

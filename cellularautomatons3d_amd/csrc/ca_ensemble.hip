@@ -47,9 +47,23 @@ struct EnsembleArgs
 	u32 first, steps, base;
 	u32 check_every, first_check, stop_mask; // first_check: steps of this launch before the call's next check point (0: on entry)
 	u32 final, reset;
+	// the *_cycle kernels only (ca3d_ensemble_step_until_cycle); appended, so that the kernels above read what they always read
+	u32 *anchor;    // [B][8192]: the state at the universe's anchor check point
+	u32 *cycle;     // [B][4]: anchor step, anchor hash, period, unused — next to steps_done / reason
+	u32 next_check; // number j of the call's next regular check point (the one first_check steps into this launch)
 };
 
 __device__ __forceinline__ u32 mux(u32 sel, u32 one, u32 zero) { return next_state(sel, one, zero); } // sel ? one : zero, bit by bit
+
+// The cycle filter's hash of one word: a sum of these over a universe's words is equal for equal states, so a mismatch proves a
+// difference. 32 bits, one multiply a word (digest_mix's 64-bit multiplies would cost more than a von Neumann step).
+__device__ __forceinline__ u32 cycle_mix(u32 idx, u32 w)
+{
+	// (the word's upper half is folded into its lower half first: a product only carries upwards, and without the fold two words that differ
+	// from zero in bit 31 alone cancel in the sum — an and-rounds fill dying out did exactly that one step before it was empty)
+	const u32 x = (w ^ (w >> 16) ^ (idx * 0x9E3779B1u)) * 0x85EBCA6Bu;
+	return x ^ (x >> 15);
+}
 
 template <typename T>
 __device__ __forceinline__ T wave_add(T v)
@@ -242,12 +256,22 @@ struct MooreStep
 	}
 };
 
-// The launch of one universe, whatever its step
-template <typename Step>
+// The launch of one universe, whatever its step. Cycle: CA3D_STOP_PERIODIC is watched too (include/ca3d.h, ca3d_ensemble_step_until_cycle).
+// Every universe keeps ONE anchor — the state at an earlier check point of the call, moved at check points 0, 1, 2, 4, 8 ... (Brent) — in
+// a third per-universe buffer: a thread stores and later loads exactly the eight words it owns, so nobody reads what another thread
+// wrote. At a check point the threads hash their words, the per-wave sums ride the chk exchange and its barrier, and only when the
+// universe's hash equals the anchor's (held wave-uniform) are the anchor's words loaded and compared: one more reduction and barrier,
+// and the only way PERIODIC is ever declared.
+template <typename Step, bool Cycle>
 __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 {
 	__shared__ __attribute__((aligned(16))) u32 xch[Step::kXchWords];
-	__shared__ __attribute__((aligned(16))) u32 chk[kWaves]; // per wave: bit 0 a cell is alive, bit 1 a cell changed in the last step
+	// per wave: bit 0 a cell is alive, bit 1 a cell changed in the last step; Cycle: + the wave's hash sum, + "differs from the anchor"
+	// Cycle, behind those (one array, so that nothing moves in the kernels without it): the anchor's step and hash and the period found,
+	// one copy PER WAVE (written by its lane 0, read by the wave itself: LDS order within a wave, no barrier) — in LDS, because the
+	// Moore step has no scalar registers to spare across the steps either
+	__shared__ __attribute__((aligned(16))) u32 chk[Cycle ? 7u * kWaves : kWaves];
+	u32(*cyc)[4] = reinterpret_cast<u32(*)[4]>(chk + (Cycle ? 3u * kWaves : 0u));
 	__shared__ u64 red64[kWaves][2];
 	__shared__ u32 red32[kWaves][6];
 	const u32 u = a.first + blockIdx.x;
@@ -270,25 +294,41 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 		rb[p][0] = 0u; rb[p][1] = 0u;
 	}
 	const ca3d_summary *rec = a.records + u;
-	const u64 step0 = a.reset ? 0ull : rec->step;
+	const u64 step0 = Cycle ? 0ull : a.reset ? 0ull : rec->step; // (Cycle: read where it is used, by the thread that then rewrites the record)
 
 	u32 t = 0, fired = 0, until = a.first_check;
+	u32 jn = 0; // Cycle: the number of the next regular check point
+	// Cycle: what only a check point needs is read from the kernel's arguments there and then, not held across the steps
+	const volatile EnsembleArgs *ka = Cycle ? (const volatile EnsembleArgs *)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
+	// The index of the thread's first word in the universe's array, worked out again at every check point: nothing of a check (indices,
+	// their products, addresses) may stay in registers across the steps, where the Moore step has none to spare
+	auto own = [&]() __attribute__((always_inline)) -> u32 {
+		u32 r = row, w = wave;
+		asm volatile("" : "+v"(r), "+s"(w));
+		return (w * kPT * 64u + r) * 2u;
+	};
+	if (Cycle)
+	{
+		jn = a.next_check;
+		if (row == 0u)
+		{
+			// the anchor the launch before left (the call's first launch sets it on entry)
+			cyc[wave][0] = a.base ? a.cycle[4u * u] : 0u;
+			cyc[wave][1] = a.base ? a.cycle[4u * u + 1u] : 0u;
+			cyc[wave][2] = 0u;
+		}
+	}
 	// One round of the loop: the check that is due on the state in `s` (previous state in `o`), then one step from `s` into `o`.
 	// Returns true when the launch is over for this universe, the state in `s` and the one before it in `o`.
 	auto round = [&](const u32 (&s)[kPT][2], u32 (&o)[kPT][2]) __attribute__((always_inline)) -> bool {
 		if (a.stop_mask && (until == 0u || (t == a.steps && a.final)))
 		{
 			bool alive, changed, has_prev;
-			if (t == 0u)
-			{
-				// nothing stepped in this launch yet: the record describes the state
-				alive = rec->population != 0ull;
-				has_prev = !a.reset && rec->has_previous != 0u;
-				changed = rec->births + rec->deaths != 0ull;
-			}
-			else
-			{
-				u32 al = 0, ch = 0;
+			u32 hash = 0; // Cycle: of the state in `s`
+			// the workgroup's two bits (and hash) of the state in `s` against `o`
+			auto look = [&]() __attribute__((always_inline)) -> u32 {
+				u32 al = 0, ch = 0, hs = 0;
+				const u32 first = Cycle ? own() : 0u;
 #pragma unroll
 				for (u32 p = 0; p < kPT; p++)
 #pragma unroll
@@ -296,22 +336,91 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 					{
 						al |= s[p][h];
 						ch |= s[p][h] ^ o[p][h];
+						if (Cycle) hs += cycle_mix(first + p * 128u + h, s[p][h]); // the word's index in the universe's array
 					}
 				const u32 f = (__ballot(al != 0u) ? 1u : 0u) | (__ballot(ch != 0u) ? 2u : 0u);
+				if (Cycle) hs = wave_add(hs);
 				// (chk is rewritten at the next check at the earliest: a step — and its barrier — lies in between)
-				if (row == 0u) chk[wave] = f;
+				if (row == 0u)
+				{
+					chk[wave] = f;
+					if (Cycle) chk[kWaves + wave] = hs;
+				}
 				__syncthreads();
 				const uint4 *c4 = reinterpret_cast<const uint4 *>(chk);
 				uint4 m = c4[0];
 #pragma unroll
 				for (int i = 1; i < (int)kWaves / 4; i++) { const uint4 n = c4[i]; m.x |= n.x; m.y |= n.y; m.z |= n.z; m.w |= n.w; }
-				const u32 all = (u32)__builtin_amdgcn_readfirstlane((int)(m.x | m.y | m.z | m.w));
+				if (Cycle)
+				{
+					uint4 hsum = c4[kWaves / 4];
+#pragma unroll
+					for (int i = 1; i < (int)kWaves / 4; i++) { const uint4 n = c4[kWaves / 4 + i]; hsum.x += n.x; hsum.y += n.y; hsum.z += n.z; hsum.w += n.w; }
+					hash = (u32)__builtin_amdgcn_readfirstlane((int)(hsum.x + hsum.y + hsum.z + hsum.w));
+				}
+				return (u32)__builtin_amdgcn_readfirstlane((int)(m.x | m.y | m.z | m.w));
+			};
+			if (t == 0u)
+			{
+				// nothing stepped in this launch yet: the record describes the state
+				alive = rec->population != 0ull;
+				has_prev = !a.reset && rec->has_previous != 0u;
+				changed = rec->births + rec->deaths != 0ull;
+				if (Cycle) (void)look(); // ... the hash comes from the registers just loaded
+			}
+			else
+			{
+				const u32 all = look();
 				alive = (all & 1u) != 0u;
 				changed = (all & 2u) != 0u;
 				has_prev = true;
 			}
 			fired = ((alive ? 0u : (u32)CA3D_STOP_EXTINCT) | (has_prev && !changed ? (u32)CA3D_STOP_STILL : 0u)) & a.stop_mask;
+			u32 j = 0;
+			if (Cycle)
+			{
+				// check point number j of the call: a regular one, or the last one at max_steps between two regular ones. A check point that
+				// ended the launch before and is looked at again on entry of this one has the same number and (k == astep) is not compared
+				// with itself when the anchor moved there.
+				const u32 k = ka->base + t;
+				j = jn;
+				if (until == 0u) jn++;
+				const uint2 av = *reinterpret_cast<const uint2 *>(cyc[wave]);
+				const u32 astep = (u32)__builtin_amdgcn_readfirstlane((int)av.x), ahash = (u32)__builtin_amdgcn_readfirstlane((int)av.y);
+				if (j != 0u && k != astep && hash == ahash)
+				{
+					u32 diff = 0;
+					const u32 *anchor = ka->anchor + (size_t)u * kEnsembleWords + own();
+#pragma unroll
+					for (u32 p = 0; p < kPT; p++)
+					{
+						const uint2 v = *reinterpret_cast<const uint2 *>(anchor + p * 128u);
+						diff |= (v.x ^ s[p][0]) | (v.y ^ s[p][1]);
+					}
+					// every lane votes: the ballot is taken BEFORE the branch that leaves lane 0 alone
+					const u32 differs = __ballot(diff != 0u) ? 1u : 0u;
+					// (the third part of chk is written here only: a step's barrier, or the record's, lies before the next time)
+					if (row == 0u) chk[2u * kWaves + wave] = differs;
+					__syncthreads();
+					const uint4 *d4 = reinterpret_cast<const uint4 *>(chk) + 2u * kWaves / 4u;
+					uint4 m = d4[0];
+#pragma unroll
+					for (int i = 1; i < (int)kWaves / 4; i++) { const uint4 n = d4[i]; m.x |= n.x; m.y |= n.y; m.z |= n.z; m.w |= n.w; }
+					if (__builtin_amdgcn_readfirstlane((int)(m.x | m.y | m.z | m.w)) == 0 && (a.stop_mask & (u32)CA3D_STOP_PERIODIC))
+					{
+						fired |= (u32)CA3D_STOP_PERIODIC;
+						if (row == 0u) cyc[wave][2] = k - astep;
+					}
+				}
+			}
 			if (fired) return true;
+			if (Cycle && (j & (j - 1u)) == 0u) // check points 0, 1, 2, 4, 8 ...: the anchor moves here, AFTER the comparison
+			{
+				u32 *anchor = ka->anchor + (size_t)u * kEnsembleWords + own();
+#pragma unroll
+				for (u32 p = 0; p < kPT; p++) *reinterpret_cast<uint2 *>(anchor + p * 128u) = make_uint2(s[p][0], s[p][1]);
+				if (row == 0u) *reinterpret_cast<uint2 *>(cyc[wave]) = make_uint2(ka->base + t, hash);
+			}
 			until = a.check_every;
 		}
 		if (t == a.steps) return true;
@@ -338,6 +447,13 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 	{
 		a.steps_done[u] = a.base + t;
 		a.reason[u] = fired;
+		if (Cycle)
+		{
+			u32 *out = ka->cycle + 4u * u; // (thread 0 reads what it wrote itself)
+			out[0] = cyc[0][0];
+			out[1] = cyc[0][1];
+			out[2] = cyc[0][2];
+		}
 	}
 	if (t == 0u && !a.reset) return; // nothing moved: state and record stand
 
@@ -391,7 +507,7 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 			r[4] |= red32[w][4];
 		}
 		ca3d_summary o;
-		o.step = step0 + t;
+		o.step = (Cycle ? (a.reset ? 0ull : a.records[u].step) : step0) + t;
 		o.population = r[0];
 		o.births = r[1];
 		o.deaths = r[2];
@@ -419,7 +535,7 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 #pragma unroll
 	for (u32 p = 0; p < kPT; p++)
 	{
-		const size_t i = ((size_t)((wave * kPT + p) * 64u + row)) * 2u;
+		const size_t i = Cycle ? (size_t)own() + p * 128u : ((size_t)((wave * kPT + p) * 64u + row)) * 2u; // (Cycle: as at the check points)
 		*reinterpret_cast<uint2 *>(mine + i) = make_uint2(s[p][0], s[p][1]);
 		*reinterpret_cast<uint2 *>(old + i) = make_uint2(q[p][0], q[p][1]);
 	}
@@ -427,17 +543,25 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 
 
 // Four waves per SIMD = up to 128 registers = one workgroup per CU: cut for 64 registers (two per CU) the step loop spills
-__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a) { ensemble_run<VnStep>(a); }
-__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64(EnsembleArgs a) { ensemble_run<MooreStep>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a) { ensemble_run<VnStep, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64(EnsembleArgs a) { ensemble_run<MooreStep, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64_cycle(EnsembleArgs a) { ensemble_run<VnStep, true>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_cycle(EnsembleArgs a) { ensemble_run<MooreStep, true>(a); }
 
-// the one place that maps an ensemble's neighbourhood to its kernel
-auto kernel_of(int neighbourhood) -> void (*)(EnsembleArgs) { return neighbourhood == CA3D_ENSEMBLE_MOORE ? ca_ensemble_moore64 : ca_ensemble_vn64; }
+// the one place that maps an ensemble's neighbourhood (and whether CA3D_STOP_PERIODIC is watched) to its kernel
+auto kernel_of(int neighbourhood, bool cycle) -> void (*)(EnsembleArgs)
+{
+	if (neighbourhood == CA3D_ENSEMBLE_MOORE) return cycle ? ca_ensemble_moore64_cycle : ca_ensemble_moore64;
+	return cycle ? ca_ensemble_vn64_cycle : ca_ensemble_vn64;
+}
 
 } // namespace
 
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 {
 	if (l.count == 0 || l.steps > kEnsembleMaxSteps || (l.stop_mask && l.check_every == 0)) return hipErrorInvalidValue;
+	const bool cycle = (l.stop_mask & (uint32_t)CA3D_STOP_PERIODIC) != 0u;
+	if (cycle && (!l.anchor || !l.cycle)) return hipErrorInvalidValue;
 	EnsembleArgs a;
 	a.state = l.state; a.prev = l.prev;
 	a.rules = l.rules;
@@ -450,14 +574,17 @@ hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 	a.first_check = into ? l.check_every - into : 0u;
 	a.final = l.final ? 1u : 0u;
 	a.reset = l.reset ? 1u : 0u;
-	hipLaunchKernelGGL(kernel_of(l.neighbourhood), dim3(l.count), dim3(kThreads), 0, stream, a);
+	a.anchor = l.anchor;
+	a.cycle = l.cycle;
+	a.next_check = l.stop_mask ? l.base / l.check_every + (into ? 1u : 0u) : 0u; // launches are cut ON check points: one that ends a launch and opens the next counts once
+	hipLaunchKernelGGL(kernel_of(l.neighbourhood, cycle), dim3(l.count), dim3(kThreads), 0, stream, a);
 	return hipGetLastError();
 }
 
 int ensemble_workgroups_per_cu(int neighbourhood)
 {
 	int per_cu = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel_of(neighbourhood), (int)kThreads, 0) != hipSuccess)
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel_of(neighbourhood, false), (int)kThreads, 0) != hipSuccess)
 	{
 		(void)hipGetLastError();
 		return 0;

@@ -211,7 +211,55 @@ __global__ __launch_bounds__(kThreads) void ca_summary(SummaryArgs a)
 	}
 }
 
+// ca3d_step_until_cycle's comparison of the state with the anchor: 16-byte loads over both arrays, every lane its kPer of both before the
+// first use; a workgroup that saw a difference ORs 1 into the flag word (one atomic per workgroup at most)
+__global__ __launch_bounds__(kThreads) void ca_state_equal(const u32x4 *a, const u32x4 *b, u64 n_vecs, u32 *flag)
+{
+	__shared__ u32 lds[kWaves];
+	u32 diff = 0;
+	for (u64 base = (u64)blockIdx.x * kTileVecs; base < n_vecs; base += (u64)gridDim.x * kTileVecs)
+	{
+		u32x4 x[kPer], y[kPer];
+#pragma unroll
+		for (int k = 0; k < kPer; k++)
+		{
+			const u64 i = base + threadIdx.x + (u64)k * kThreads;
+			const bool in = i < n_vecs;
+			x[k] = in ? a[i] : (u32x4){0u, 0u, 0u, 0u};
+			y[k] = in ? b[i] : (u32x4){0u, 0u, 0u, 0u};
+		}
+#pragma unroll
+		for (int k = 0; k < kPer; k++)
+		{
+			const u32x4 d = x[k] ^ y[k];
+			diff |= d[0] | d[1] | d[2] | d[3];
+		}
+	}
+	const u32 any = __ballot(diff != 0u) ? 1u : 0u;
+	if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = any;
+	__syncthreads();
+	if (threadIdx.x == 0u)
+	{
+		u32 t = 0;
+		for (int w = 0; w < kWaves; w++) t |= lds[w];
+		if (t) atomicOr(flag, 1u);
+	}
+}
+
 } // namespace
+
+hipError_t launch_state_equal(const uint32_t *a, const uint32_t *b, size_t n_words, uint32_t *flag, hipStream_t stream)
+{
+	if (!a || !b || !flag || n_words == 0 || n_words % 4u) return hipErrorInvalidValue;
+	const u64 n_vecs = n_words / 4u, tiles = (n_vecs + kTileVecs - 1u) / kTileVecs;
+	int dev = 0, cus = 0;
+	hipError_t e = hipGetDevice(&dev);
+	if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+	if (e != hipSuccess) return e;
+	const u64 cap = (u64)(cus > 0 ? cus : 256) * 8u;
+	hipLaunchKernelGGL(ca_state_equal, dim3((u32)(tiles < cap ? tiles : cap)), dim3(kThreads), 0, stream, (const u32x4 *)a, (const u32x4 *)b, n_vecs, flag);
+	return hipGetLastError();
+}
 
 hipError_t launch_summary(const SummaryLaunch &l, hipStream_t stream)
 {

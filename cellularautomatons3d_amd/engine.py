@@ -45,7 +45,7 @@ def _summary(s: "_capi.SummaryStruct", planes: Optional[np.ndarray]) -> Summary:
                    tuple(int(v) for v in s.box_min), tuple(int(v) for v in s.box_max), planes)
 
 
-STOP_EXTINCT, STOP_STILL = _capi.STOP_EXTINCT, _capi.STOP_STILL
+STOP_EXTINCT, STOP_STILL, STOP_PERIODIC = _capi.STOP_EXTINCT, _capi.STOP_STILL, _capi.STOP_PERIODIC
 
 
 def _seed_spec(grid_size: int, seed: int, and_rounds: int = 0, box=None) -> "_capi.SeedStruct":
@@ -185,6 +185,18 @@ class Engine:
         mask = (STOP_EXTINCT if extinct else 0) | (STOP_STILL if still else 0)
         _capi.check(self._lib.ca3d_step_until(self._h, max_steps, check_every, mask, C.byref(st), C.byref(done), C.byref(reason)))
         return int(done.value), int(reason.value), _summary(st, None)
+
+    def step_until_cycle(self, max_steps: int, check_every: int = 8, extinct: bool = True, still: bool = True, periodic: bool = True):
+        """`ca3d_step_until_cycle`: `step_until` with a third condition — the state at a check point equals, bit for bit, the state
+        at an earlier check point of this call (`periodic`). -> (steps_done, reason, period, Summary); reason: STOP_EXTINCT |
+        STOP_STILL | STOP_PERIODIC bits; period: steps between the two equal states (a multiple of the true period, the least period
+        itself with `check_every` 1), 0 unless STOP_PERIODIC fired."""
+        st = _capi.SummaryStruct()
+        done, reason, period = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        mask = (STOP_EXTINCT if extinct else 0) | (STOP_STILL if still else 0) | (STOP_PERIODIC if periodic else 0)
+        _capi.check(self._lib.ca3d_step_until_cycle(self._h, max_steps, check_every, mask, C.byref(st), C.byref(done), C.byref(reason),
+                                                    C.byref(period)))
+        return int(done.value), int(reason.value), int(period.value), _summary(st, None)
 
     def slab_step(self, n_steps: int) -> None:
         _capi.check(self._lib.ca3d_slab_step(self._h, n_steps))

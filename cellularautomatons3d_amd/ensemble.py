@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi, host
 from ._capi import ENSEMBLE_ALL, ENSEMBLE_WORDS, Stats
-from .engine import STOP_EXTINCT, STOP_STILL, Summary, _as_i32, _as_u32, _seed_spec, _summary
+from .engine import STOP_EXTINCT, STOP_PERIODIC, STOP_STILL, Summary, _as_i32, _as_u32, _seed_spec, _summary
 
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
@@ -134,6 +134,14 @@ class Ensemble:
         _capi.check(self._lib.ca3d_ensemble_step_until(self._h, max_steps, check_every, stop_mask, done.ctypes.data_as(_u32p),
                                                        reason.ctypes.data_as(_u32p)))
         return done, reason
+
+    def step_until_cycle(self, max_steps: int, check_every: int = 8,
+                         stop_mask: int = STOP_EXTINCT | STOP_STILL | STOP_PERIODIC) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`Engine.step_until_cycle` per universe, decided inside the kernel -> (steps_done u32[n], reason u32[n], period u32[n])."""
+        done, reason, period = (np.empty(self.n, dtype=np.uint32) for _ in range(3))
+        _capi.check(self._lib.ca3d_ensemble_step_until_cycle(self._h, max_steps, check_every, stop_mask, done.ctypes.data_as(_u32p),
+                                                             reason.ctypes.data_as(_u32p), period.ctypes.data_as(_u32p)))
+        return done, reason, period
 
     def summaries(self, first: int = 0, count: Optional[int] = None) -> List[Summary]:
         """The universes' records (no per-plane counts): copied, not computed — every launch leaves them up to date."""

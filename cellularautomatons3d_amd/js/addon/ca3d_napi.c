@@ -530,8 +530,8 @@ typedef struct
 	napi_async_work work;
 	napi_deferred deferred;
 	ca3d_t *h;
-	int kind; /* 0 readState, 1 render, 2 synchronize, 3 stepUntil */
-	uint32_t max_steps, check_every, stop_mask, steps_done, reason;
+	int kind; /* 0 readState, 1 render, 2 synchronize, 3 stepUntil, 4 stepUntilCycle */
+	uint32_t max_steps, check_every, stop_mask, steps_done, reason, period;
 	ca3d_summary summary;
 	int rc;
 	char err[512];
@@ -553,6 +553,8 @@ static void job_execute(napi_env env, void *data)
 	if (j->kind == 0) j->rc = ca3d_read_state(j->h, j->words, j->n_words);
 	else if (j->kind == 1) j->rc = ca3d_render(j->h, j->uniforms, j->w, j->hh, j->spp, j->pres, j->light, j->depth);
 	else if (j->kind == 3) j->rc = ca3d_step_until(j->h, j->max_steps, j->check_every, j->stop_mask, &j->summary, &j->steps_done, &j->reason);
+	else if (j->kind == 4)
+		j->rc = ca3d_step_until_cycle(j->h, j->max_steps, j->check_every, j->stop_mask, &j->summary, &j->steps_done, &j->reason, &j->period);
 	else j->rc = ca3d_synchronize(j->h);
 	if (j->rc) snprintf(j->err, sizeof j->err, "ca3d error %d: %s", j->rc, ca3d_last_error()); /* ca3d_last_error is per thread */
 }
@@ -563,11 +565,12 @@ static void job_complete(napi_env env, napi_status status, void *data)
 	napi_value v;
 	if (status == napi_ok && j->rc == 0)
 	{
-		if (j->kind == 3)
+		if (j->kind == 3 || j->kind == 4)
 		{
 			napi_create_object(env, &v);
 			set_num(env, v, "stepsDone", j->steps_done);
 			set_num(env, v, "reason", j->reason);
+			if (j->kind == 4) set_num(env, v, "period", j->period);
 			napi_set_named_property(env, v, "summary", summary_object(env, &j->summary, NULL));
 		}
 		else napi_get_undefined(env, &v);
@@ -688,6 +691,21 @@ static napi_value js_step_until_async(napi_env env, napi_callback_info info)
 	j->h = h; j->kind = 3; j->max_steps = max_steps; j->check_every = every; j->stop_mask = mask;
 	job_hold_engine(env, j, argv[0]);
 	return job_start(env, j, "ca3d.stepUntil");
+}
+
+/* stepUntilCycleAsync(handle, maxSteps, checkEvery, stopMask) -> Promise<{stepsDone, reason, period, summary}> */
+static napi_value js_step_until_cycle_async(napi_env env, napi_callback_info info)
+{
+	napi_value argv[4];
+	if (!get_args(env, info, 4, argv)) return NULL;
+	ca3d_t *h = get_handle(env, argv[0]);
+	uint32_t max_steps, every, mask;
+	if (!h || !get_u32(env, argv[1], &max_steps) || !get_u32(env, argv[2], &every) || !get_u32(env, argv[3], &mask)) return NULL;
+	AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
+	if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+	j->h = h; j->kind = 4; j->max_steps = max_steps; j->check_every = every; j->stop_mask = mask;
+	job_hold_engine(env, j, argv[0]);
+	return job_start(env, j, "ca3d.stepUntilCycle");
 }
 
 /* ---- ca3d_group_*: one JS thread drives the Z-slab split over several GPUs (include/ca3d.h) ---------------------------- */
@@ -1116,6 +1134,30 @@ static napi_value js_ensemble_step_until(napi_env env, napi_callback_info info)
 	return rc ? throw_ca3d(env, rc) : undefined(env);
 }
 
+/* ensembleStepUntilCycle(handle, maxSteps, checkEvery, stopMask, Uint32Array(n) stepsDone, Uint32Array(n) reason, Uint32Array(n) period) */
+static napi_value js_ensemble_step_until_cycle(napi_env env, napi_callback_info info)
+{
+	napi_value argv[7];
+	if (!get_args(env, info, 7, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t max_steps, every, mask;
+	void *done, *reason, *period;
+	size_t nd, nr, np;
+	if (!e || !get_u32(env, argv[1], &max_steps) || !get_u32(env, argv[2], &every) || !get_u32(env, argv[3], &mask) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 0, &done, &nd) || !get_typed(env, argv[5], napi_uint32_array, 0, &reason, &nr) ||
+	    !get_typed(env, argv[6], napi_uint32_array, 0, &period, &np))
+		return NULL;
+	void *p = NULL;
+	napi_get_value_external(env, argv[0], &p);
+	if (nd != ((EnsembleSlot *)p)->n || nr != nd || np != nd)
+	{
+		napi_throw_range_error(env, NULL, "stepsDone, reason and period must hold one entry per universe");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_step_until_cycle(e, max_steps, every, mask, (uint32_t *)done, (uint32_t *)reason, (uint32_t *)period);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
 /* ensembleSummaries(handle, first, count) -> [summary object, ...] */
 static napi_value js_ensemble_summaries(napi_env env, napi_callback_info info)
 {
@@ -1301,10 +1343,10 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"groupUploadState", js_group_upload_state}, {"groupReadState", js_group_read_state}, {"groupStep", js_group_step},
 	    {"groupSynchronize", js_group_synchronize}, {"groupSetOption", js_group_set_option}, {"groupInfo", js_group_info}, {"groupRender", js_group_render},
 	    {"readStateAsync", js_read_state_async}, {"renderAsync", js_render_async}, {"synchronizeAsync", js_synchronize_async},
-	    {"summary", js_summary}, {"groupSummary", js_group_summary}, {"stepUntilAsync", js_step_until_async},
+	    {"summary", js_summary}, {"groupSummary", js_group_summary}, {"stepUntilAsync", js_step_until_async}, {"stepUntilCycleAsync", js_step_until_cycle_async},
 	    {"ensembleCreate", js_ensemble_create}, {"ensembleDestroy", js_ensemble_destroy}, {"ensembleConfigure", js_ensemble_configure},
 	    {"ensembleSetRules", js_ensemble_set_rules}, {"ensembleUploadState", js_ensemble_upload_state}, {"ensembleReadState", js_ensemble_read_state},
-	    {"ensembleStep", js_ensemble_step}, {"ensembleStepUntil", js_ensemble_step_until}, {"ensembleSummaries", js_ensemble_summaries},
+	    {"ensembleStep", js_ensemble_step}, {"ensembleStepUntil", js_ensemble_step_until}, {"ensembleStepUntilCycle", js_ensemble_step_until_cycle}, {"ensembleSummaries", js_ensemble_summaries},
 	    {"ensembleSynchronize", js_ensemble_synchronize}, {"ensembleStats", js_ensemble_stats},
 	    {"seedState", js_seed_state}, {"groupSeedState", js_group_seed_state}, {"ensembleSeedState", js_ensemble_seed_state},
 	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables},

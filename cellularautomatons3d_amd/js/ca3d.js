@@ -218,6 +218,7 @@ function loadAddon()
 }
 
 const STOP_EXTINCT = 1, STOP_STILL = 2; // ca3d_step_until: bits of `reason`
+const STOP_PERIODIC = 4; // ... and of ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle, which alone take it
 
 class Engine
 {
@@ -342,6 +343,16 @@ class Engine
 		const mask = (o.extinct ? STOP_EXTINCT : 0) | (o.still ? STOP_STILL : 0);
 		return this._queue(() => this._a.stepUntilAsync(this._h, maxSteps, o.checkEvery, mask));
 	}
+	// ca3d_step_until_cycle: stepUntil with a third condition (periodic, default true) — the state at a check point equals, bit for bit,
+	// the state at an earlier check point of this call. period: the steps between the two (a multiple of the true period, the least
+	// period itself with checkEvery 1), 0 unless STOP_PERIODIC is in reason.
+	// -> Promise<{stepsDone, reason (STOP_EXTINCT | STOP_STILL | STOP_PERIODIC bits; 0: maxSteps reached), period, summary}>
+	stepUntilCycle(maxSteps, opts)
+	{
+		const o = Object.assign({ checkEvery: 8, extinct: true, still: true, periodic: true }, opts || {});
+		const mask = (o.extinct ? STOP_EXTINCT : 0) | (o.still ? STOP_STILL : 0) | (o.periodic ? STOP_PERIODIC : 0);
+		return this._queue(() => this._a.stepUntilCycleAsync(this._h, maxSteps, o.checkEvery, mask));
+	}
 
 	info() { this._idle("info"); return this._a.info(this._h); }
 	stats() { this._idle("stats"); return this._a.stats(this._h); }
@@ -464,6 +475,14 @@ class Ensemble
 		this._a.ensembleStepUntil(this._e, maxSteps, o.checkEvery, o.stopMask, stepsDone, reason);
 		return { stepsDone, reason };
 	}
+	/** -> {stepsDone, reason, period: Uint32Array(n) each} (reason: + STOP_PERIODIC; period[u]: 0 unless STOP_PERIODIC is in reason[u]) */
+	stepUntilCycle(maxSteps, opts)
+	{
+		const o = Object.assign({ checkEvery: 8, stopMask: STOP_EXTINCT | STOP_STILL | STOP_PERIODIC }, opts || {});
+		const stepsDone = new Uint32Array(this.n), reason = new Uint32Array(this.n), period = new Uint32Array(this.n);
+		this._a.ensembleStepUntilCycle(this._e, maxSteps, o.checkEvery, o.stopMask, stepsDone, reason, period);
+		return { stepsDone, reason, period };
+	}
 	/** the universes' records, as Engine.summary() objects without planePopulation */
 	summaries(first, count) { first = first || 0; return this._a.ensembleSummaries(this._e, first, count === undefined ? this.n - first : count); }
 	synchronize() { this._a.ensembleSynchronize(this._e); }
@@ -471,7 +490,7 @@ class Ensemble
 }
 
 module.exports = {
-	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
+	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
 	initialState, dispatchShape, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
 };

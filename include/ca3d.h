@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_*; + ca3d_seed_state, ca3d_group_seed_state, ca3d_ensemble_seed_state, ca3d_ensemble_set_rule_tables; + ca3d_ensemble_configure_neighbourhood, ca3d_ensemble_get_neighbourhood */
+#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_*; + ca3d_seed_state, ca3d_group_seed_state, ca3d_ensemble_seed_state, ca3d_ensemble_set_rule_tables; + ca3d_ensemble_configure_neighbourhood, ca3d_ensemble_get_neighbourhood; + CA3D_STOP_PERIODIC, ca3d_step_until_cycle, ca3d_ensemble_step_until_cycle */
 #define CA3D_LUT_LEN 81 /* 3 rule-sets x 27 slots (main_pathtraced.js:10, 155-159) */
 
 typedef struct ca3d_engine ca3d_t;
@@ -302,10 +302,44 @@ int ca3d_get_summary_time(ca3d_t *h, double *gpu_ms);
 enum
 {
 	CA3D_STOP_EXTINCT = 1,
-	CA3D_STOP_STILL = 2
+	CA3D_STOP_STILL = 2,
+	CA3D_STOP_PERIODIC = 4 /* ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle only: the two calls above it refuse the bit */
 };
 int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, ca3d_summary *out, uint32_t *steps_done,
                     uint32_t *reason);
+
+/*
+ * Stop on a cycle: ca3d_step_until with a third condition, exact period detection.
+ *   CA3D_STOP_PERIODIC  the state at a check point equals, bit for bit, the state at an earlier check point of the same call
+ * Check points are numbered j = 0 (on entry), 1, 2, ...: every check_every steps, plus a last one at max_steps if that is no multiple.
+ * A call keeps ONE anchor, the state at an earlier check point of THIS call, on Brent's schedule: the entry state first; at check
+ * points j = 1, 2, 4, 8, ... the anchor moves to the state just checked, AFTER that state was compared with the old anchor. At every
+ * check point j > 0 the state is compared with the anchor; if they are equal the call stops with CA3D_STOP_PERIODIC in *reason and
+ * *period = steps_done - (the anchor's step). In executable form, with t[k] the state k steps after the call began:
+ *     k = j = anchor = 0
+ *     loop: fired = (t[k] empty ? EXTINCT : 0) | ((has_previous or k > 0) and t[k] == t[k-1] ? STILL : 0)
+ *                 | (j > 0 and t[k] == t[anchor] ? PERIODIC : 0),  fired &= stop_mask
+ *           if fired or k == max_steps: return (steps_done = k, reason = fired, period = fired & PERIODIC ? k - anchor : 0)
+ *           if j is 0 or a power of two: anchor = k
+ *           k += min(check_every, max_steps - k), j += 1
+ * What follows from it:
+ *   - It is EXACT. Digests and hashes only filter; a stop is declared after a comparison of every word of the two states. No false stops.
+ *   - PERIODIC never fires on entry, and the anchor does not survive the call: every call starts from its own entry state.
+ *   - *period is a multiple of the true period: lcm(true period, check_every) when the match is at a regular check point, the least
+ *     period itself when check_every == 1. 0 when PERIODIC did not fire.
+ *   - A fixed point or an empty grid that has reached the anchor reports PERIODIC as well (period: a multiple of check_every), beside
+ *     STILL / EXTINCT when those bits are in stop_mask.
+ *   - A cycle of period p entered after a transient of m steps is found at step a + lcm(p, check_every), a the first anchor step with
+ *     a >= m and the next anchor move at least that lcm away: at most about 3 x max(m, lcm) steps after the start.
+ *   - The state afterwards is bit for bit the state after ca3d_step(steps_done), as for the other conditions.
+ *   - Patterns that translate are not cycles: nothing is compared modulo shifts.
+ * stop_mask: any subset of the three bits. *steps_done, *reason, *period are nullable. The anchor is a device copy of the state,
+ * allocated at the first call and freed by ca3d_configure / ca3d_destroy; the filter is the summary's digest, which every check point
+ * computes anyway, and equal digests start one compare kernel over the two buffers. Stepping goes through ca3d_step as in
+ * ca3d_step_until. Both layouts, any grid; errors as ca3d_step_until (unknown bits: 8 and above). A slab engine: CA3D_ERR_UNSUPPORTED.
+ */
+int ca3d_step_until_cycle(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, ca3d_summary *out, uint32_t *steps_done,
+                          uint32_t *reason, uint32_t *period);
 
 /*
  * Ensemble: B independent 64^3 universes on one device, stepped side by side by ONE kernel launch (no reference counterpart: its UI
@@ -365,6 +399,15 @@ int ca3d_ensemble_read_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count,
 int ca3d_ensemble_step(ca3d_ensemble_t *e, uint32_t n_steps);
 int ca3d_ensemble_step_until(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
                              uint32_t *reason);
+/* ca3d_step_until_cycle per universe, decided inside the kernel (ca_ensemble_vn64_cycle / ca_ensemble_moore64_cycle): the definition
+ * above holds for every universe on its own, with its own anchor (a third per-universe buffer on the device, B x 32 KiB, allocated at
+ * the first call with CA3D_STOP_PERIODIC in stop_mask, freed by a configure), also across the launches a long call is cut into. At a
+ * check point the workgroup hashes its registers (32 bits) and compares with the anchor's hash; only equal hashes start the comparison
+ * of all words, and only that declares a stop. stop_mask: any subset of the three bits; without CA3D_STOP_PERIODIC the call IS
+ * ca3d_ensemble_step_until. steps_done, reason, period: B entries each, nullable; period[u] is 0 unless reason[u] holds
+ * CA3D_STOP_PERIODIC. Everything else — launch cutting at 65 536 steps, stats, records, readiness errors — as ca3d_ensemble_step_until. */
+int ca3d_ensemble_step_until_cycle(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                                   uint32_t *reason, uint32_t *period);
 int ca3d_ensemble_summarize(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_summary *out);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);

@@ -13,6 +13,13 @@ through one engine would pay on top.
 for a Moore rule at 64^3 is one launch per step of the kernel compiled for the rule; same protocol, written to
 profiles/ensemble_moore_64.json unless --out says otherwise.
 
+--cycle measures what watching CA3D_STOP_PERIODIC costs, for both neighbourhoods: Ensemble.step_until_cycle (stop mask 7, the *_cycle
+kernels) against Ensemble.step_until (stop mask 3, the kernels above) on the same universes — B = 256 and 1024, 256 steps, check_every 1
+and 8, density-1/2 fills on which nothing stops within the call, so every check is paid. Before timing, both calls must have left the same
+states with every universe still running; then the two alternate from freshly uploaded states and the medians of the hipEvent time around
+the launch (Ensemble.stats) and of the host clock around the call are reported. Written to profiles/ensemble_cycle_64.json unless --out
+says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -66,16 +73,61 @@ def timed(fn, sync, min_seconds):
     return (time.perf_counter() - t0) / reps
 
 
+def cycle_rows(args):
+    """step_until_cycle (mask 7) against step_until (mask 3): one row per (neighbourhood, B, check_every)."""
+    ens = Ensemble(0)
+    rows = []
+    for nb in ("von neumann", "moore"):
+        born, survive = RULES[nb]
+        for B in args.universes:
+            words = fills(B)
+            ens.configure(B, neighbourhood=nb)
+            ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood=nb, born=born, survive=survive)
+            for every in (1, 8):
+                def call(cycle):
+                    """One call from the uploaded fills -> (event ms, wall ms, steps_done, reason)."""
+                    ens.upload_state(0, words)
+                    t0 = time.perf_counter()
+                    out = ens.step_until_cycle(args.steps, check_every=every, stop_mask=7) if cycle else ens.step_until(args.steps, check_every=every, stop_mask=3)
+                    wall = (time.perf_counter() - t0) * 1e3
+                    return ens.stats().gpu_ms, wall, out[0], out[1]
+
+                _, _, done, reason = call(True)
+                with_cycle = ens.read_state()
+                _, _, done0, reason0 = call(False)
+                if not np.array_equal(with_cycle, ens.read_state()):
+                    raise SystemExit(f"{nb} B={B} check_every={every}: step_until_cycle and step_until left different states")
+                if reason.any() or reason0.any() or (done != args.steps).any() or (done0 != args.steps).any():
+                    raise SystemExit(f"{nb} B={B} check_every={every}: a universe stopped within {args.steps} steps — not every check would be paid")
+                tc, tp = [], []
+                for _ in range(args.repeats):
+                    tc.append(call(True)[:2])
+                    tp.append(call(False)[:2])
+                ev_c, ev_p = statistics.median(t[0] for t in tc), statistics.median(t[0] for t in tp)
+                wall_c, wall_p = statistics.median(t[1] for t in tc), statistics.median(t[1] for t in tp)
+                row = {"neighbourhood": nb, "universes": B, "steps": args.steps, "check_every": every,
+                       "step_until_cycle": {"event_us": ev_c * 1e3, "event_us_min_max": [min(t[0] for t in tc) * 1e3, max(t[0] for t in tc) * 1e3], "wall_us": wall_c * 1e3},
+                       "step_until": {"event_us": ev_p * 1e3, "event_us_min_max": [min(t[0] for t in tp) * 1e3, max(t[0] for t in tp) * 1e3], "wall_us": wall_p * 1e3},
+                       "cycle_over_plain_event": ev_c / ev_p, "cycle_over_plain_wall": wall_c / wall_p, "states_verified": B}
+                rows.append(row)
+                print(json.dumps(row))
+    ens.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--universes", type=int, nargs="+", default=[1, 256, 1024, 4096])
+    ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
     ap.add_argument("--steps", type=int, default=256, help="steps per launch")
     ap.add_argument("--repeats", type=int, default=5, help="alternating measurements per path; the median is reported")
     ap.add_argument("--min-seconds", type=float, default=0.25, help="work per measurement")
     ap.add_argument("--neighbourhood", choices=sorted(RULES), default="von neumann", help="of the ensemble and of the rule both paths run")
     ap.add_argument("--out", default=None, help="JSON file to write (moore: profiles/ensemble_moore_64.json)")
+    ap.add_argument("--cycle", action="store_true", help="measure step_until_cycle against step_until instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
+    if args.universes is None:
+        args.universes = [256, 1024] if args.cycle else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     born, survive = RULES[nb]
     if args.out is None and nb == "moore":
@@ -86,6 +138,22 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.cycle:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_cycle_64.json")
+        result = {
+            "what": "B universes of 64^3, random fills (density 1/2), rules B2,4/S1,3,5 (von Neumann) and B5-7/S4-6 (Moore): Ensemble.step_until_cycle(steps, stop mask 7) "
+                    "vs. Ensemble.step_until(steps, stop mask 3); nothing stops, every check is paid",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {nb_: [KERNELS[nb_] + "_cycle", KERNELS[nb_]] for nb_ in sorted(KERNELS)},
+            "timing": f"one call from freshly uploaded states; hipEvent time around the launch and host clock around the call; medians of {args.repeats} alternating measurements",
+            "rows": cycle_rows(args),
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
 
     eng, ens = Engine(0), Ensemble(0)
     eng.configure(G)
