@@ -12,6 +12,9 @@
 //   * the rule is the synthesised function of ca_jit_rule.inc (rule_synth.cpp) or the truth tables.
 // Run-time compiled only (ca_jit.cpp). Needs ca_bitslice.inc, ca_packed_roll_kernel.inc, ca_resident_kernel.inc.
 
+#ifndef CA3D_RC_PIN_SWEEP
+#define CA3D_RC_PIN_SWEEP 1 // 0: the sweep's arithmetic is free to sink behind the request for the next faces
+#endif
 #ifndef CA3D_RC_PREFETCH_K
 #define CA3D_RC_PREFETCH_K 9 // 512^3: sweep iteration at which the next faces are asked for (see there; 3 - 10 measure 9.4 - 9.7 us per step for the clustered rule-set, from 11 on the allocation spills: 10.3 us and up)
 #endif
@@ -322,6 +325,15 @@ __device__ __forceinline__ void resident_class_run(const ResidentArgs &a, char *
 				}
 				if (k == (kPrefetchK > 2 ? kPrefetchK : 2) && !last)
 				{
+					// the planes formed so far stay in front of the request: nothing but the image write reads them, and the compiler
+					// sank their arithmetic behind this branch — the request then left right after the z faces (the order up to round 5)
+					if (CA3D_RC_PIN_SWEEP)
+					{
+#pragma unroll
+						for (int q = 0; q <= i - 2; q++) asm volatile("" : "+v"(s[q]));
+#pragma unroll
+						for (int q = j < PZT ? j : PZT; q <= PZT - 1; q++) asm volatile("" : "+v"(s[q]));
+					}
 					ask_ahead();
 				}
 			}

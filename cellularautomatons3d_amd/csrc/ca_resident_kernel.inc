@@ -118,6 +118,9 @@ __device__ __forceinline__ u32 res_right_w(u32 w, bool last_word)
 // mailboxes, same tags. Built to test whether two waves per SIMD were what held the kernel at 0.32 of the VALU peak: they were
 // not — a wave of this kernel has 32 independent planes to issue from, and ZS = 2 measures 2.61 against 2.52 us per step at
 // 512^3 (1.37 / 1.26 at 256^3; with 16-row tiles, two workgroups per CU, it wins: 2.89 / 3.31). The default stays ZS = 1.
+#ifndef CA3D_RES_PIN_PASS
+#define CA3D_RES_PIN_PASS 1 // 0: the main pass is free to sink behind the request for the next faces (the order up to round 5)
+#endif
 template <int LS, int LB, int RY, int CW = 16, int PZ = 32, int ZS = 1>
 __device__ __forceinline__ void resident_run(const ResidentArgs &a, char *lds)
 {
@@ -375,7 +378,18 @@ __device__ __forceinline__ void resident_run(const ResidentArgs &a, char *lds)
 				have_pre = true;
 			}
 		};
-		if (!kPreAfterImage) prefetch_faces();
+		if (!kPreAfterImage)
+		{
+			// "after the main pass" has to be said to the compiler: nothing but the image write reads the new words, so the pass's
+			// arithmetic sank behind the branch inside prefetch_faces() and the request went out at the HEAD of the pass (up to round 5)
+			if (CA3D_RES_PIN_PASS)
+			{
+#pragma unroll
+				for (int p = 1; p < (int)PT - 1; p++) asm volatile("" : "+v"(s[p]));
+				__builtin_amdgcn_sched_barrier(0);
+			}
+			prefetch_faces();
+		}
 		s[0] = n0;
 		s[PT - 1] = nl;
 		RES_STAMP(5);
@@ -423,6 +437,21 @@ __device__ __forceinline__ void resident_run(const ResidentArgs &a, char *lds)
 //     (95 % of the steps): CA3D_RES_PAIR_PRE0 = 2 lets it poll in the ordinary way behind the image write (stale 0 - 3 %, one round
 //     trip, and it still waits ~1 100 cycles at the barrier for the partner): 2.351 -> 2.339 us; 1 (asking behind the image write
 //     AND keeping the compiler from moving that): 2.46.
+// What the compiler made of that placement (round 6, profiles/r6_a_resident_request_placement.txt). The scheduling barriers only order
+// instructions inside one basic block, and the request sits behind branches (asks_ahead, !last). Once the step read one register set and
+// wrote the other (round 4's last change), nothing but the image write read the new words: the arithmetic of planes 1 .. 12 sank behind
+// the branch, only the (convergent) DPP moves stayed, and the emitted kernel asked BEFORE the first arithmetic instruction of the pass —
+// with 48 fetched words live across the request, 216 VGPRs. The plane figures above and the stale counts were taken on the order the
+// in-place step had; nothing measured the production order, the stamps build (RES_STAMP) changes what may move. Now the words of
+// planes 1 .. CA3D_RES_PAIR_PRE are made opaque in front of the request (pin_planes: an empty asm volatile, CA3D_RES_PAIR_PIN): the
+// request is emitted behind that many planes, each plane's DPP moves beside its arithmetic, 194 VGPRs, no spill; tests/
+// test_resident_codegen.py reads that order out of the assembly. -DCA3D_RES_COUNT_STALE counts the first polls of a step that found an
+// old tag without a stamp or a wait (one scalar add per poll, one store per wave at the end; resident_probe mode 33 prints it).
+// The sweep on the emitted order (4 096-step launches, us per step): the order up to round 5 2.10 (and only 1 - 7 % of its first polls
+// were stale: "stale in most steps" was not true of it); held, first group not asking, planes 5 / 9 / 12 / 14 / behind the pass:
+// 1.99 / 2.00 / 1.99 / 2.00 / 1.99 — the plane no longer matters, what the 5 % buy is each plane's DPP moves beside its arithmetic;
+// first group asking behind its image write (PRE0 = 1): 1.87 / 1.91 / 1.88 / 1.96 / 2.42, asking like the second (0): 2.15 / 2.04 /
+// 2.09 / 2.20 / 2.20. Defaults: plane 5, PRE0 = 1. The figures of round 4 above belong to the order of their day.
 // With the requests placed like this the static issue priority round 4 first gave the older half (s_setprio 1: 2.479 -> 2.385 with
 // the compiler's placement) no longer matters (2.353 - 2.363 without, 2.357 - 2.379 with: CA3D_RES_PAIR_PRIO, off); priorities that
 // alternate between the two waves during the main pass (per plane, per four planes, per half) cost 4 - 7 %.
@@ -434,10 +463,13 @@ __device__ __forceinline__ void resident_run(const ResidentArgs &a, char *lds)
 // the younger wave's pass does not get shorter, it is starved for as long as the older one computes); the give-up flag read after
 // the face pass instead of right behind the barrier (no change); -amdgpu-sched-strategy=max-ilp / iterative-ilp (2.39 / 2.46).
 #ifndef CA3D_RES_PAIR_PRE0
-#define CA3D_RES_PAIR_PRE0 2 // first z group: 0 asks like the second, 1 asks behind the image write, 2 does not ask ahead
+#define CA3D_RES_PAIR_PRE0 1 // first z group: 0 asks like the second, 1 asks behind the image write, 2 does not ask ahead (round 6, emitted order: 2.04 / 1.87 / 1.99 us)
 #endif
 #ifndef CA3D_RES_PAIR_PRE
-#define CA3D_RES_PAIR_PRE 12 // the plane of the main pass after which the next faces are asked for (15: behind the pass)
+#define CA3D_RES_PAIR_PRE 5 // the plane of the main pass after which the next faces are asked for (15: behind the pass)
+#endif
+#ifndef CA3D_RES_PAIR_PIN
+#define CA3D_RES_PAIR_PIN 1 // 0: the arithmetic of the planes in front of the request is free to sink behind it (the order up to round 5)
 #endif
 #ifndef CA3D_RES_PAIR_LOADS_FIRST
 #define CA3D_RES_PAIR_LOADS_FIRST 0
@@ -519,6 +551,8 @@ __device__ __forceinline__ void resident_pair_run(const ResidentArgs &a, char *l
 #ifdef CA3D_RES_STAMPS
 	unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = 0; // as resident_run: cycles per phase, every wave of tile 37
 	u32 stale = 0;
+#elif defined(CA3D_RES_COUNT_STALE)
+	u32 stale = 0; // first polls of a step that found an old tag — counted in the production instruction order: no stamp, no wait
 #endif
 
 	// One step: state t in `si`, state t + 1 into `so`. The step loop below calls it with the two register sets changing roles — written as
@@ -559,6 +593,8 @@ __device__ __forceinline__ void resident_pair_run(const ResidentArgs &a, char *l
 #ifdef CA3D_RES_STAMPS_POLL
 				if (spins == 0) { __builtin_amdgcn_sched_barrier(0); RES_STAMP(7); __builtin_amdgcn_sched_barrier(0); } // the answer to the request made ahead is there
 #endif
+#elif defined(CA3D_RES_COUNT_STALE)
+				if (spins == 0 && !__all(ok)) stale++;
 #endif
 				if (__all(ok)) break;
 				if ((spins & 63u) == 63u)
@@ -702,6 +738,11 @@ __device__ __forceinline__ void resident_pair_run(const ResidentArgs &a, char *l
 				have_pre = true;
 			}
 		};
+		// the words of planes 1 .. n are made before what follows (see above resident_pair_run: CA3D_RES_PAIR_PIN)
+		auto pin_planes = [&](int n) __attribute__((always_inline)) {
+#pragma unroll
+			for (int q = 1; q <= n; q++) asm volatile("" : "+v"(so[0][q]), "+v"(so[1][q]));
+		};
 #pragma unroll
 		for (int p = 1; p < (int)PT - 1; p++)
 		{
@@ -710,6 +751,7 @@ __device__ __forceinline__ void resident_pair_run(const ResidentArgs &a, char *l
 			so[1][p] = res_rule<LS, LB>(w1, res_left(w1), res_right(w1), w0, yp[p], si[1][p - 1], si[1][p + 1]);
 			if (p == CA3D_RES_PAIR_PRE && asks_ahead)
 			{
+				if (CA3D_RES_PAIR_PIN) pin_planes(p);
 				__builtin_amdgcn_sched_barrier(0);
 				prefetch_faces();
 				__builtin_amdgcn_sched_barrier(0);
@@ -717,6 +759,7 @@ __device__ __forceinline__ void resident_pair_run(const ResidentArgs &a, char *l
 		}
 		if (CA3D_RES_PAIR_PRE >= (int)PT - 1 && asks_ahead)
 		{
+			if (CA3D_RES_PAIR_PIN) pin_planes((int)PT - 2);
 			__builtin_amdgcn_sched_barrier(0);
 			prefetch_faces();
 			__builtin_amdgcn_sched_barrier(0);
@@ -769,6 +812,8 @@ __device__ __forceinline__ void resident_pair_run(const ResidentArgs &a, char *l
 		for (int i = 0; i < 8; i++) a.status[600 + (tid >> 6) * 8 + i] = (u32)(st_acc[i] / a.steps);
 		a.status[680 + (tid >> 6)] = (u32)((unsigned long long)stale * 1000u / a.steps);
 	}
+#elif defined(CA3D_RES_COUNT_STALE)
+	if (tile == 37u && (tid & 63u) == 0) a.status[680 + (tid >> 6)] = (u32)((unsigned long long)stale * 1000u / a.steps); // every wave of the tile
 #endif
 #pragma unroll
 	for (int r = 0; r < 2; r++)

@@ -73,6 +73,16 @@ int main(int argc, char **argv)
 			else if (rows == 33) { for (int w = 0; w < 8; w++) { printf("  wave %d cycles/step:", w); u32 tot = 0; for (int i = 0; i < 7; i++) { printf(" %s %u", nm[i], tt[600 + w * 8 + i]); tot += tt[600 + w * 8 + i]; } printf("  total %u  (request answered %u) stale polls per 1000 steps %u\n", tot, tt[600 + w * 8 + 7], tt[680 + w]); } }
 			else for (int w = 0; w < 2; w++) { printf("  wave %d cycles/step:", w * (rows >= 32 ? 4 : 2) * zs); u32 tot = 0; for (int i = 0; i < 7; i++) { printf(" %s %u", nm[i], tt[600 + w * 8 + i]); tot += tt[600 + w * 8 + i]; } printf("  total %u\n", tot); }
 		}
+#elif defined(CA3D_RES_COUNT_STALE)
+		// the row-pair form's count of stale first polls, taken in the production instruction order (waves 0 - 3: first z group, 4 - 7: second)
+		if (rows == 33)
+		{
+			std::vector<u32> tt(700);
+			CK(hipMemcpy(tt.data(), status, 700 * 4, hipMemcpyDeviceToHost));
+			printf("  stale first polls per 1000 steps, waves 0-7 of tile 37:");
+			for (int w = 0; w < 8; w++) printf(" %u", tt[680 + w]);
+			printf("\n");
+		}
 #endif
 		if (st[0])
 		{
