@@ -62,7 +62,6 @@ struct RowsJit
 	uint32_t G = 0;
 	int zrun = 0, main = -1;
 	bool e = false, c = false;
-	uint32_t tables[6]{};
 };
 
 // Run-time compiled class kernels (rule as compile-time truth tables) for one (main table, live rule-sets, rule)
@@ -73,7 +72,6 @@ struct ClassJit
 	void *deep_np2 = nullptr, *flat_np2 = nullptr;             // the same for rows of whole uint4 that are not a power of two of them
 	int main = -1;
 	bool e = false, c = false;
-	uint32_t tables[6] = {0, 0, 0, 0, 0, 0}; // survive / born of main, edges, corners (bit k = value at count k)
 };
 
 // Run-time compiled rolling-window class kernels (ca_packed_roll_kernel.inc) for one (grid, main table, live rule-sets,
@@ -91,7 +89,6 @@ struct RollJit
 	int cvl = -1;                              // log2(G / 128); -1: none
 	int main = -1;
 	bool e = false, c = false;
-	uint32_t tables[6] = {0, 0, 0, 0, 0, 0};
 };
 
 struct PackedLaunch

@@ -1,0 +1,11 @@
+#include "ca_device_types.h"
+namespace ca3d
+{
+namespace jit
+{
+#include "ca_bitops.inc"
+#include "ca_jit_rule.inc"
+#include "ca_bitslice.inc"
+#include "ca_packed_class_kernel.inc"
+}
+}

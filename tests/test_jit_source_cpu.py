@@ -1,21 +1,38 @@
 """The device sources the engine hands to hiprtc at run time (csrc/ca_jit.cpp) must compile for gfx950: checked
-here with hiprtc itself, which needs no GPU. The engine's own JIT path is exercised on the GPU by
+here with hiprtc itself, which needs no GPU. The programs and the header list are read from the files the library embeds
+(csrc/Makefile: JIT_PROGRAMS, JIT_SOURCES), not restated. The engine's own JIT path is exercised on the GPU by
 tests/test_gpu_ca_parity.py::test_vn_truth_table_kernel_random_tables."""
 import ctypes as C
 import os
+import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cellularautomatons3d_amd", "csrc")
 
-PROGRAM = b"""
-namespace ca3d_jit
-{
-#include "ca_bitops.inc"
-#include "ca_packed_vn_kernel.inc"
-}
-"""
+
+def _make_list(name):
+    """A `NAME := words` variable of csrc/Makefile: the one list the embedded sources are generated from."""
+    m = re.search(r"^%s\s*:=\s*(.*)$" % name, open(os.path.join(CSRC, "Makefile")).read(), re.M)
+    assert m, f"{name} not found in csrc/Makefile"
+    return m.group(1).split()
+
+
+def _program(family):
+    """The translation unit of one kernel family as the library embeds it: a newline, then the file (the Makefile's `embed`)."""
+    name = "ca_jit_prog_%s.inc" % family
+    assert name in _make_list("JIT_PROGRAMS"), name
+    return b"\n" + open(os.path.join(CSRC, name), "rb").read()
+
+
+HEADERS = [n.encode() for n in _make_list("JIT_SOURCES")]
+PROGRAM = _program("vn")
+CLASS_PROGRAM = _program("class")
+ROLL_PROGRAM = _program("roll")
+RESIDENT_PROGRAM = _program("resident")
+RESIDENT_CLASS_PROGRAM = _program("resident_class")
+ROWS_PROGRAM = _program("rows")
 
 
 def _hiprtc():
@@ -25,76 +42,6 @@ def _hiprtc():
         except OSError:
             continue
     pytest.skip("hiprtc is not installed")
-
-
-CLASS_PROGRAM = b"""
-#include "ca_device_types.h"
-namespace ca3d
-{
-namespace jit
-{
-#include "ca_bitops.inc"
-#include "ca_jit_rule.inc"
-#include "ca_bitslice.inc"
-#include "ca_packed_class_kernel.inc"
-}
-}
-"""
-
-ROLL_PROGRAM = b"""
-#include "ca_device_types.h"
-namespace ca3d
-{
-namespace jit
-{
-#include "ca_bitops.inc"
-#include "ca_jit_rule.inc"
-#include "ca_bitslice.inc"
-#include "ca_packed_roll_kernel.inc"
-}
-}
-"""
-
-RESIDENT_PROGRAM = b"""
-namespace ca3d_jit
-{
-#include "ca_bitops.inc"
-#include "ca_resident_kernel.inc"
-}
-"""
-
-RESIDENT_CLASS_PROGRAM = b"""
-#include "ca_device_types.h"
-namespace ca3d
-{
-namespace jit
-{
-#include "ca_bitops.inc"
-#include "ca_jit_rule.inc"
-#include "ca_bitslice.inc"
-#include "ca_packed_roll_kernel.inc"
-#include "ca_resident_kernel.inc"
-#include "ca_resident_class_kernel.inc"
-}
-}
-"""
-
-ROWS_PROGRAM = b"""
-#include "ca_device_types.h"
-namespace ca3d
-{
-namespace jit
-{
-#include "ca_bitops.inc"
-#include "ca_jit_rule.inc"
-#include "ca_bitslice.inc"
-#include "ca_packed_rows_kernel.inc"
-}
-}
-"""
-
-HEADERS = [b"ca_bitops.inc", b"ca_packed_vn_kernel.inc", b"ca_device_types.h", b"ca_bitslice.inc", b"ca_packed_class_kernel.inc",
-           b"ca_packed_roll_kernel.inc", b"ca_resident_kernel.inc", b"ca_resident_class_kernel.inc", b"ca_packed_rows_kernel.inc"]
 
 
 #: the clustered rule as rule_synth.cpp writes it (the generated header the engine passes as "ca_jit_rule.inc")
@@ -116,6 +63,17 @@ __device__ __forceinline__ u32 jit_rule_word(u32 alive, const u32 *mn, const u32
 	return bitop3<0xCA>(alive, t18, t24);
 }
 """
+
+
+def test_programs_include_only_embedded_headers():
+    """A program may name the headers hiprtc is given and nothing else: JIT_SOURCES, and the per-compile ca_jit_rule.inc."""
+    programs = _make_list("JIT_PROGRAMS")
+    assert programs and not set(programs) & set(_make_list("JIT_SOURCES"))
+    for name in programs:
+        includes = re.findall(rb'^\s*#\s*include\s*[<"]([^>"]+)[>"]', open(os.path.join(CSRC, name), "rb").read(), re.M)
+        assert includes, name
+        for inc in includes:
+            assert inc in HEADERS or inc == b"ca_jit_rule.inc", (name, inc)
 
 
 def _compile(rtc, program, name, defines, rule_fn=b"// no synthesised rule\n"):
