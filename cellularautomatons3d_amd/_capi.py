@@ -147,6 +147,7 @@ SYMBOLS = [
     ("ca3d_ensemble_step", C.c_int, [_H, C.c_uint32]),
     ("ca3d_ensemble_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     ("ca3d_ensemble_step_until_cycle", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
+    ("ca3d_ensemble_step_until_trace", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, _u32p]),
     ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),

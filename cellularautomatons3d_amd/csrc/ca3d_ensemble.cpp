@@ -1,7 +1,7 @@
 // ca3d_ensemble_*: many independent 64^3 universes side by side on one device (include/ca3d.h). One workgroup of ca_ensemble_vn64 or
 // ca_ensemble_moore64 (ca_ensemble.hip; the ensemble's neighbourhood decides) steps one universe with its state in registers; a launch
 // over B workgroups is B universes, each with its own rule table pair, its own step counter, its own summary record and — in
-// ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
+// ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle / ca3d_ensemble_step_until_trace — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
 #include <cstring>
 #include <new>
@@ -24,6 +24,10 @@ struct ca3d_ensemble
 	// ca3d_ensemble_step_until_cycle: every universe's anchor state (n x 32 KiB) and its anchor step / anchor hash / period / unused
 	// (n x 4 words), allocated at the first call that watches CA3D_STOP_PERIODIC, gone with the other arrays at a configure
 	uint32_t *anchor = nullptr, *cycle = nullptr;
+	// ca3d_ensemble_step_until_trace: the samples of the call under way, [n][K][3] words; grown when a call needs more than
+	// trace_words, gone with the other arrays at a configure
+	uint32_t *trace = nullptr;
+	size_t trace_words = 0;
 	// ca3d_ensemble_seed_state with one spec per universe: the specs on the device, their pinned staging copy (n entries each, allocated
 	// at the first such call) and the event behind the copy out of it
 	ca3d_seed *seed_dev = nullptr, *seed_host = nullptr;
@@ -41,9 +45,10 @@ namespace
 
 void free_arrays(ca3d_ensemble *e)
 {
-	for (void *p : {(void *)e->state, (void *)e->prev, (void *)e->rules, (void *)e->steps_done, (void *)e->reason, (void *)e->records, (void *)e->anchor, (void *)e->cycle})
+	for (void *p : {(void *)e->state, (void *)e->prev, (void *)e->rules, (void *)e->steps_done, (void *)e->reason, (void *)e->records, (void *)e->anchor, (void *)e->cycle, (void *)e->trace})
 		if (p) hipFree(p);
-	e->state = e->prev = e->rules = e->steps_done = e->reason = e->anchor = e->cycle = nullptr;
+	e->state = e->prev = e->rules = e->steps_done = e->reason = e->anchor = e->cycle = e->trace = nullptr;
+	e->trace_words = 0;
 	e->records = nullptr;
 	if (e->seed_dev) hipFree(e->seed_dev);
 	if (e->seed_host) hipHostFree(e->seed_host);
@@ -136,9 +141,11 @@ int configure_ensemble(ca3d_ensemble *e, uint32_t grid_size, uint32_t n_universe
 }
 
 // `total` steps at most for every universe, as launches of at most kEnsembleMaxSteps steps whose ends fall on check points; with a
-// stop mask a universe leaves at the first check point at which one of its conditions holds
-int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_mask)
+// stop mask a universe leaves at the first check point at which one of its conditions holds. samples_per_universe != 0: a traced run —
+// check points are reached whatever the mask, and each leaves a sample in e->trace
+int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_mask, uint32_t samples_per_universe = 0)
 {
+	const bool checks = stop_mask || samples_per_universe;
 	HIP_TRY(hipEventRecord(e->ev_start, e->stream));
 	uint64_t launches = 0;
 	uint32_t base = 0;
@@ -148,7 +155,7 @@ int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_ma
 		if (n > kEnsembleMaxSteps)
 		{
 			n = kEnsembleMaxSteps;
-			if (stop_mask && check_every <= kEnsembleMaxSteps) n -= (base + n) % check_every; // end on a check point (base is one)
+			if (checks && check_every <= kEnsembleMaxSteps) n -= (base + n) % check_every; // end on a check point (base is one)
 		}
 		EnsembleLaunch l = launch_of(e);
 		l.steps = n;
@@ -156,6 +163,7 @@ int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_ma
 		l.check_every = check_every;
 		l.stop_mask = stop_mask;
 		l.final = base + n == total;
+		if (samples_per_universe) { l.samples = e->trace; l.sample_stride = samples_per_universe; }
 		HIP_TRY(launch_ensemble(l, e->stream));
 		launches++;
 		base += n;
@@ -168,17 +176,50 @@ int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_ma
 
 // ca3d_ensemble_step_until (known: EXTINCT | STILL, period null) and ca3d_ensemble_step_until_cycle (known: + PERIODIC). Without
 // CA3D_STOP_PERIODIC in the mask the launches are the first call's whatever the entry point: the *_cycle kernels run only when asked for.
+// ca3d_ensemble_step_until_trace passes `trace` (known: EXTINCT | STILL): the *_trace kernels run whatever the mask, 0 included.
+struct TraceOut
+{
+	uint32_t *samples, samples_per_universe, *n_samples;
+};
+// samples of one universe in a traced call: check points 0, check_every, ... and the last one at max_steps
+uint64_t trace_capacity(uint32_t max_steps, uint32_t check_every) { return ((uint64_t)max_steps + check_every - 1u) / check_every + 1u; }
+
 int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t known, uint32_t *steps_done, uint32_t *reason,
-               uint32_t *period)
+               uint32_t *period, const TraceOut *trace = nullptr)
 {
 	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
 	if (check_every == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "check_every must be at least 1");
 	if (stop_mask & ~known) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in stop_mask %#x", stop_mask);
 	int rc = ensemble_ready(e);
 	if (rc) return rc;
+	const uint64_t K = trace ? trace_capacity(max_steps, check_every) : 0u;
+	if (trace && !trace->samples) return fail(CA3D_ERR_INVALID_ARGUMENT, "samples is NULL");
+	if (trace && trace->samples_per_universe < K)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "samples_per_universe %u: %u steps checked every %u leave K = %llu samples per universe", trace->samples_per_universe,
+		            max_steps, check_every, (unsigned long long)K);
 	HIP_TRY(hipSetDevice(e->device));
 	const size_t word_bytes = (size_t)e->n * sizeof(uint32_t);
 	const bool cycle = (stop_mask & CA3D_STOP_PERIODIC) != 0u;
+	const size_t sample_words = (size_t)e->n * (size_t)K * 3u;
+	if (trace && sample_words > e->trace_words)
+	{
+		// the new array first: a failure leaves the handle as it was
+		uint32_t *grown = nullptr;
+		hipError_t err = hipMalloc((void **)&grown, sample_words * sizeof(uint32_t));
+		if (err != hipSuccess)
+		{
+			(void)hipGetLastError();
+			return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating %llu samples of %u universes: %s", (unsigned long long)K, e->n,
+			            hipGetErrorString(err));
+		}
+		if (e->trace)
+		{
+			HIP_TRY(hipStreamSynchronize(e->stream));
+			hipFree(e->trace);
+		}
+		e->trace = grown;
+		e->trace_words = sample_words;
+	}
 	if (cycle && !e->anchor)
 	{
 		hipError_t err = hipMalloc((void **)&e->anchor, (size_t)e->n * kEnsembleWords * sizeof(uint32_t));
@@ -192,19 +233,28 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 		}
 	}
 	std::vector<uint32_t> done(e->n, stop_mask ? 0u : max_steps), fired(e->n, 0u), cyc(cycle ? 4u * (size_t)e->n : 0u, 0u);
+	std::vector<uint32_t> got(sample_words); // [n][K][3]: staged, so that a failure below leaves the caller's array as it was
 	e->last_launches = 0;
 	e->timed = false;
-	if (stop_mask)
+	if (stop_mask || trace)
 	{
-		// the kernel keeps both arrays: a universe whose reason word is set leaves the later launches of this call at once
-		HIP_TRY(hipMemsetAsync(e->steps_done, 0, word_bytes, e->stream));
-		HIP_TRY(hipMemsetAsync(e->reason, 0, word_bytes, e->stream));
+		if (stop_mask)
+		{
+			// the kernel keeps both arrays: a universe whose reason word is set leaves the later launches of this call at once
+			HIP_TRY(hipMemsetAsync(e->steps_done, 0, word_bytes, e->stream));
+			HIP_TRY(hipMemsetAsync(e->reason, 0, word_bytes, e->stream));
+		}
 		if (cycle) HIP_TRY(hipMemsetAsync(e->cycle, 0, 4u * word_bytes, e->stream)); // no anchor survives a call
-		rc = run(e, max_steps, check_every, stop_mask); // max_steps == 0: one launch that only checks
+		if (trace) HIP_TRY(hipMemsetAsync(e->trace, 0, sample_words * sizeof(uint32_t), e->stream)); // slots no check point reaches stay zero
+		rc = run(e, max_steps, check_every, stop_mask, trace ? (uint32_t)K : 0u); // max_steps == 0: one launch that only checks
 		if (rc) return rc;
-		HIP_TRY(hipMemcpyAsync(done.data(), e->steps_done, word_bytes, hipMemcpyDeviceToHost, e->stream));
-		HIP_TRY(hipMemcpyAsync(fired.data(), e->reason, word_bytes, hipMemcpyDeviceToHost, e->stream));
+		if (stop_mask)
+		{
+			HIP_TRY(hipMemcpyAsync(done.data(), e->steps_done, word_bytes, hipMemcpyDeviceToHost, e->stream));
+			HIP_TRY(hipMemcpyAsync(fired.data(), e->reason, word_bytes, hipMemcpyDeviceToHost, e->stream));
+		}
 		if (cycle) HIP_TRY(hipMemcpyAsync(cyc.data(), e->cycle, 4u * word_bytes, hipMemcpyDeviceToHost, e->stream));
+		if (trace) HIP_TRY(hipMemcpyAsync(got.data(), e->trace, sample_words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
 	}
 	else if (max_steps)
 	{
@@ -220,6 +270,17 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 	if (reason) memcpy(reason, fired.data(), word_bytes);
 	if (period)
 		for (uint32_t u = 0; u < e->n; u++) period[u] = cycle ? cyc[4u * (size_t)u + 2u] : 0u;
+	if (trace)
+	{
+		const size_t per = (size_t)trace->samples_per_universe * 3u, mine = (size_t)K * 3u;
+		for (uint32_t u = 0; u < e->n; u++)
+		{
+			memcpy(trace->samples + u * per, got.data() + u * mine, mine * sizeof(uint32_t));
+			memset(trace->samples + u * per + mine, 0, (per - mine) * sizeof(uint32_t));
+			// a universe reached the check points up to the one it left at: steps_done is a multiple of check_every, or max_steps
+			if (trace->n_samples) trace->n_samples[u] = (uint32_t)trace_capacity(done[u], check_every);
+		}
+	}
 	return CA3D_OK;
 }
 
@@ -459,6 +520,14 @@ int ca3d_ensemble_step_until_cycle(ca3d_ensemble_t *e, uint32_t max_steps, uint3
                                    uint32_t *reason, uint32_t *period) CA3D_API_TRY
 {
 	return step_until(e, max_steps, check_every, stop_mask, CA3D_STOP_EXTINCT | CA3D_STOP_STILL | CA3D_STOP_PERIODIC, steps_done, reason, period);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_step_until_trace(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                                   uint32_t *reason, uint32_t *samples, uint32_t samples_per_universe, uint32_t *n_samples) CA3D_API_TRY
+{
+	const TraceOut out{samples, samples_per_universe, n_samples};
+	return step_until(e, max_steps, check_every, stop_mask, CA3D_STOP_EXTINCT | CA3D_STOP_STILL, steps_done, reason, nullptr, &out);
 }
 CA3D_API_CATCH
 

@@ -209,6 +209,8 @@ struct EnsembleLaunch
 	uint32_t *reason;         // [B] stop bits that fired in the current call; a universe whose word is set leaves at once
 	uint32_t *anchor;         // [B][8192] the state at each universe's anchor check point; [B][4] anchor step, anchor hash, period, unused —
 	uint32_t *cycle;          // both only when stop_mask holds CA3D_STOP_PERIODIC (the *_cycle kernels), else unused and may be null
+	uint32_t *samples;        // [B][sample_stride][3] population, births, deaths per check point of the call (the *_trace kernels); null: no trace.
+	uint32_t sample_stride;   // Every check point is then reached whatever stop_mask holds, CA3D_STOP_PERIODIC is refused
 	uint32_t first, count;
 	uint32_t steps;           // <= kEnsembleMaxSteps
 	uint32_t base;            // steps the earlier launches of the same call took

@@ -21,7 +21,8 @@
 //
 // Two kernels share everything but the step: ca_ensemble_vn64 (above) and ca_ensemble_moore64, whose rule is a Moore table pair (27 + 27
 // bits, two words per universe). The body — entry check from the stored record, check points, record reduction, write-back — is
-// ensemble_run<Step>; a Step policy (VnStep, MooreStep) owns the rule's registers, the size of the LDS exchange and one step.
+// ensemble_run<Step, Cycle, Trace>; a Step policy (VnStep, MooreStep) owns the rule's registers, the size of the LDS exchange and one step.
+// The *_cycle kernels watch CA3D_STOP_PERIODIC as well; the *_trace kernels leave a sample (population, births, deaths) per check point.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,6 +52,9 @@ struct EnsembleArgs
 	u32 *anchor;    // [B][8192]: the state at the universe's anchor check point
 	u32 *cycle;     // [B][4]: anchor step, anchor hash, period, unused — next to steps_done / reason
 	u32 next_check; // number j of the call's next regular check point (the one first_check steps into this launch)
+	// the *_trace kernels only (ca3d_ensemble_step_until_trace); appended likewise
+	u32 *samples;      // [B][sample_stride][3]: population, births, deaths at check point j of the call
+	u32 sample_stride; // samples of one universe: the call's K = ceil(max_steps / check_every) + 1
 };
 
 __device__ __forceinline__ u32 mux(u32 sel, u32 one, u32 zero) { return next_state(sel, one, zero); } // sel ? one : zero, bit by bit
@@ -75,6 +79,24 @@ __device__ __forceinline__ u32 wave_or(u32 v)
 {
 	for (int o = 32; o > 0; o >>= 1) v |= (u32)__shfl_xor(v, o);
 	return v;
+}
+
+// The trace's sum over a wave, wave-uniform: four DPP adds leave every row of 16 lanes with its sum (lane ^ 1, lane ^ 2, the other quad
+// pair, the other half), four v_readlane and three scalar adds join the rows. No LDS, and no lane-address registers that would stay
+// alive across the steps, where the Moore step has none to spare (__shfl_xor's do).
+__device__ __forceinline__ u32 row16_sum(u32 v)
+{
+	v += dpp_mov<1 | (0 << 2) | (3 << 4) | (2 << 6)>(v); // quad_perm:[1,0,3,2]
+	v += dpp_mov<2 | (3 << 2) | (0 << 4) | (1 << 6)>(v); // quad_perm:[2,3,0,1]
+	v += dpp_mov<0x141>(v);                              // row_half_mirror
+	v += dpp_mov<0x140>(v);                              // row_mirror
+	return v;
+}
+__device__ __forceinline__ u32 wave_sum_uniform(u32 v)
+{
+	v = row16_sum(v);
+	return (u32)__builtin_amdgcn_readlane((int)v, 0) + (u32)__builtin_amdgcn_readlane((int)v, 16) + (u32)__builtin_amdgcn_readlane((int)v, 32) +
+	       (u32)__builtin_amdgcn_readlane((int)v, 48);
 }
 
 // ---- von Neumann: the table pair in one word, lut_s | lut_b << 8 (7 bits each)
@@ -262,15 +284,21 @@ struct MooreStep
 // wrote. At a check point the threads hash their words, the per-wave sums ride the chk exchange and its barrier, and only when the
 // universe's hash equals the anchor's (held wave-uniform) are the anchor's words loaded and compared: one more reduction and barrier,
 // and the only way PERIODIC is ever declared.
-template <typename Step, bool Cycle>
+// Trace: every check point is reached whatever the stop mask, and leaves one sample — population, births, deaths of the state in the
+// registers against the one a step earlier — in samples[u][j] (include/ca3d.h, ca3d_ensemble_step_until_trace). The per-thread counts
+// are reduced over the wave, ride the chk exchange and its barrier as the hash does, and thread 0 sums the 16 partials and stores the
+// three words. Births and deaths travel as ONE word, births | deaths << 16: a wave's 512 words hold 16 384 of each at most. The number j
+// is worked out at the check point from base, t and check_every (read from the kernel's arguments there and then).
+template <typename Step, bool Cycle, bool Trace>
 __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 {
 	__shared__ __attribute__((aligned(16))) u32 xch[Step::kXchWords];
-	// per wave: bit 0 a cell is alive, bit 1 a cell changed in the last step; Cycle: + the wave's hash sum, + "differs from the anchor"
+	// per wave: bit 0 a cell is alive, bit 1 a cell changed in the last step; Cycle: + the wave's hash sum, + "differs from the anchor";
+	// Trace: + the wave's population, + its births | deaths << 16
 	// Cycle, behind those (one array, so that nothing moves in the kernels without it): the anchor's step and hash and the period found,
 	// one copy PER WAVE (written by its lane 0, read by the wave itself: LDS order within a wave, no barrier) — in LDS, because the
 	// Moore step has no scalar registers to spare across the steps either
-	__shared__ __attribute__((aligned(16))) u32 chk[Cycle ? 7u * kWaves : kWaves];
+	__shared__ __attribute__((aligned(16))) u32 chk[Cycle ? 7u * kWaves : Trace ? 3u * kWaves : kWaves];
 	u32(*cyc)[4] = reinterpret_cast<u32(*)[4]>(chk + (Cycle ? 3u * kWaves : 0u));
 	__shared__ u64 red64[kWaves][2];
 	__shared__ u32 red32[kWaves][6];
@@ -294,12 +322,12 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 		rb[p][0] = 0u; rb[p][1] = 0u;
 	}
 	const ca3d_summary *rec = a.records + u;
-	const u64 step0 = Cycle ? 0ull : a.reset ? 0ull : rec->step; // (Cycle: read where it is used, by the thread that then rewrites the record)
+	const u64 step0 = Cycle || Trace ? 0ull : a.reset ? 0ull : rec->step; // (Cycle, Trace: read where it is used, by the thread that then rewrites the record)
 
 	u32 t = 0, fired = 0, until = a.first_check;
 	u32 jn = 0; // Cycle: the number of the next regular check point
-	// Cycle: what only a check point needs is read from the kernel's arguments there and then, not held across the steps
-	const volatile EnsembleArgs *ka = Cycle ? (const volatile EnsembleArgs *)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
+	// Cycle, Trace: what only a check point needs is read from the kernel's arguments there and then, not held across the steps
+	const volatile EnsembleArgs *ka = Cycle || Trace ? (const volatile EnsembleArgs *)__builtin_amdgcn_kernarg_segment_ptr() : nullptr;
 	// The index of the thread's first word in the universe's array, worked out again at every check point: nothing of a check (indices,
 	// their products, addresses) may stay in registers across the steps, where the Moore step has none to spare
 	auto own = [&]() __attribute__((always_inline)) -> u32 {
@@ -321,7 +349,7 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 	// One round of the loop: the check that is due on the state in `s` (previous state in `o`), then one step from `s` into `o`.
 	// Returns true when the launch is over for this universe, the state in `s` and the one before it in `o`.
 	auto round = [&](const u32 (&s)[kPT][2], u32 (&o)[kPT][2]) __attribute__((always_inline)) -> bool {
-		if (a.stop_mask && (until == 0u || (t == a.steps && a.final)))
+		if ((Trace || a.stop_mask) && (until == 0u || (t == a.steps && a.final)))
 		{
 			bool alive, changed, has_prev;
 			u32 hash = 0; // Cycle: of the state in `s`
@@ -346,6 +374,21 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 					chk[wave] = f;
 					if (Cycle) chk[kWaves + wave] = hs;
 				}
+				if (Trace)
+				{
+					u32 pop = 0, bd = 0; // the thread's population; its births | deaths << 16 (256 of each at most)
+#pragma unroll
+					for (u32 p = 0; p < kPT; p++)
+#pragma unroll
+						for (u32 h = 0; h < 2u; h++)
+						{
+							pop += (u32)__popc(s[p][h]);
+							bd += (u32)__popc(s[p][h] & ~o[p][h]) + ((u32)__popc(o[p][h] & ~s[p][h]) << 16);
+						}
+					pop = wave_sum_uniform(pop);
+					bd = wave_sum_uniform(bd);
+					if (row == 0u) { chk[kWaves + wave] = pop; chk[2u * kWaves + wave] = bd; }
+				}
 				__syncthreads();
 				const uint4 *c4 = reinterpret_cast<const uint4 *>(chk);
 				uint4 m = c4[0];
@@ -367,10 +410,40 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 				has_prev = !a.reset && rec->has_previous != 0u;
 				changed = rec->births + rec->deaths != 0ull;
 				if (Cycle) (void)look(); // ... the hash comes from the registers just loaded
+				// Trace: sample 0 is the record as it stands, on the call's first launch only — a check point that ended the launch
+				// before has been sampled there, from the registers
+				if (Trace && wave == 0u && row == 0u && ka->base == 0u)
+				{
+					u32 *out = ka->samples + (size_t)(a.first + blockIdx.x) * ka->sample_stride * 3u; // (not `u`: nothing new held across the steps)
+					out[0] = (u32)rec->population;
+					out[1] = (u32)rec->births;
+					out[2] = (u32)rec->deaths;
+				}
 			}
 			else
 			{
 				const u32 all = look();
+				// Trace: the partials look() left behind its barrier become the sample (chk is rewritten after the next step's barrier at the earliest)
+				if (Trace && wave == 0u)
+				{
+					// Lanes 0 .. 15 of wave 0 take one wave's partials each (every row of 16 lanes does, so that the DPP sums below are over
+					// whole rows) and lane 0 stores the sample. Births or deaths of a universe do not fit 16 bits: unpacked before they are summed.
+					u32 r = row;
+					asm volatile("" : "+v"(r)); // (worked out here, not held across the steps: see own())
+					const u32 pw = chk[kWaves + (r & 15u)], bw = chk[2u * kWaves + (r & 15u)];
+					const u32 ps = row16_sum(pw), bs = row16_sum(bw & 0xFFFFu), ds = row16_sum(bw >> 16);
+					if (r == 0u)
+					{
+						// check point number j of the call: a regular one, or the last one at max_steps between two regular ones
+						// (j <= ceil(max_steps / check_every) = sample_stride - 1: launch_ensemble refuses a launch that could pass it)
+						const u32 k = ka->base + t, every = ka->check_every;
+						const u32 j = k / every + (k % every ? 1u : 0u);
+						u32 *out = ka->samples + ((size_t)(a.first + blockIdx.x) * ka->sample_stride + j) * 3u;
+						out[0] = ps;
+						out[1] = bs;
+						out[2] = ds;
+					}
+				}
 				alive = (all & 1u) != 0u;
 				changed = (all & 2u) != 0u;
 				has_prev = true;
@@ -507,7 +580,7 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 			r[4] |= red32[w][4];
 		}
 		ca3d_summary o;
-		o.step = (Cycle ? (a.reset ? 0ull : a.records[u].step) : step0) + t;
+		o.step = (Cycle || Trace ? (a.reset ? 0ull : a.records[u].step) : step0) + t;
 		o.population = r[0];
 		o.births = r[1];
 		o.deaths = r[2];
@@ -535,7 +608,7 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 #pragma unroll
 	for (u32 p = 0; p < kPT; p++)
 	{
-		const size_t i = Cycle ? (size_t)own() + p * 128u : ((size_t)((wave * kPT + p) * 64u + row)) * 2u; // (Cycle: as at the check points)
+		const size_t i = Cycle || Trace ? (size_t)own() + p * 128u : ((size_t)((wave * kPT + p) * 64u + row)) * 2u; // (Cycle, Trace: as at the check points)
 		*reinterpret_cast<uint2 *>(mine + i) = make_uint2(s[p][0], s[p][1]);
 		*reinterpret_cast<uint2 *>(old + i) = make_uint2(q[p][0], q[p][1]);
 	}
@@ -543,14 +616,17 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 
 
 // Four waves per SIMD = up to 128 registers = one workgroup per CU: cut for 64 registers (two per CU) the step loop spills
-__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a) { ensemble_run<VnStep, false>(a); }
-__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64(EnsembleArgs a) { ensemble_run<MooreStep, false>(a); }
-__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64_cycle(EnsembleArgs a) { ensemble_run<VnStep, true>(a); }
-__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_cycle(EnsembleArgs a) { ensemble_run<MooreStep, true>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64(EnsembleArgs a) { ensemble_run<VnStep, false, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64(EnsembleArgs a) { ensemble_run<MooreStep, false, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64_cycle(EnsembleArgs a) { ensemble_run<VnStep, true, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_cycle(EnsembleArgs a) { ensemble_run<MooreStep, true, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64_trace(EnsembleArgs a) { ensemble_run<VnStep, false, true>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_trace(EnsembleArgs a) { ensemble_run<MooreStep, false, true>(a); }
 
-// the one place that maps an ensemble's neighbourhood (and whether CA3D_STOP_PERIODIC is watched) to its kernel
-auto kernel_of(int neighbourhood, bool cycle) -> void (*)(EnsembleArgs)
+// the one place that maps an ensemble's neighbourhood (and whether CA3D_STOP_PERIODIC is watched, or samples are recorded) to its kernel
+auto kernel_of(int neighbourhood, bool cycle, bool trace) -> void (*)(EnsembleArgs)
 {
+	if (trace) return neighbourhood == CA3D_ENSEMBLE_MOORE ? ca_ensemble_moore64_trace : ca_ensemble_vn64_trace; // (never with cycle: launch_ensemble)
 	if (neighbourhood == CA3D_ENSEMBLE_MOORE) return cycle ? ca_ensemble_moore64_cycle : ca_ensemble_moore64;
 	return cycle ? ca_ensemble_vn64_cycle : ca_ensemble_vn64;
 }
@@ -559,9 +635,12 @@ auto kernel_of(int neighbourhood, bool cycle) -> void (*)(EnsembleArgs)
 
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 {
-	if (l.count == 0 || l.steps > kEnsembleMaxSteps || (l.stop_mask && l.check_every == 0)) return hipErrorInvalidValue;
-	const bool cycle = (l.stop_mask & (uint32_t)CA3D_STOP_PERIODIC) != 0u;
-	if (cycle && (!l.anchor || !l.cycle)) return hipErrorInvalidValue;
+	const bool cycle = (l.stop_mask & (uint32_t)CA3D_STOP_PERIODIC) != 0u, trace = l.samples != nullptr;
+	const bool checks = l.stop_mask || trace; // the launch has check points
+	if (l.count == 0 || l.steps > kEnsembleMaxSteps || (checks && l.check_every == 0)) return hipErrorInvalidValue;
+	if (cycle && (!l.anchor || !l.cycle || trace)) return hipErrorInvalidValue;
+	// the last sample a universe can write is number ceil((base + steps) / check_every): inside its sample_stride slots, or no launch
+	if (trace && ((uint64_t)l.base + l.steps + l.check_every - 1u) / l.check_every >= l.sample_stride) return hipErrorInvalidValue;
 	EnsembleArgs a;
 	a.state = l.state; a.prev = l.prev;
 	a.rules = l.rules;
@@ -570,21 +649,23 @@ hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 	a.first = l.first; a.steps = l.steps; a.base = l.base;
 	a.check_every = l.check_every;
 	a.stop_mask = l.stop_mask;
-	const uint32_t into = l.stop_mask ? l.base % l.check_every : 0u; // steps since the call's last check point
+	const uint32_t into = checks ? l.base % l.check_every : 0u; // steps since the call's last check point
 	a.first_check = into ? l.check_every - into : 0u;
 	a.final = l.final ? 1u : 0u;
 	a.reset = l.reset ? 1u : 0u;
 	a.anchor = l.anchor;
 	a.cycle = l.cycle;
 	a.next_check = l.stop_mask ? l.base / l.check_every + (into ? 1u : 0u) : 0u; // launches are cut ON check points: one that ends a launch and opens the next counts once
-	hipLaunchKernelGGL(kernel_of(l.neighbourhood, cycle), dim3(l.count), dim3(kThreads), 0, stream, a);
+	a.samples = l.samples;
+	a.sample_stride = l.sample_stride;
+	hipLaunchKernelGGL(kernel_of(l.neighbourhood, cycle, trace), dim3(l.count), dim3(kThreads), 0, stream, a);
 	return hipGetLastError();
 }
 
 int ensemble_workgroups_per_cu(int neighbourhood)
 {
 	int per_cu = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel_of(neighbourhood, false), (int)kThreads, 0) != hipSuccess)
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel_of(neighbourhood, false, false), (int)kThreads, 0) != hipSuccess)
 	{
 		(void)hipGetLastError();
 		return 0;

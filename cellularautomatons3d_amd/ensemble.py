@@ -143,6 +143,22 @@ class Ensemble:
                                                              reason.ctypes.data_as(_u32p), period.ctypes.data_as(_u32p)))
         return done, reason, period
 
+    def step_trace(self, max_steps: int, check_every: int = 8,
+                   stop_mask: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """`step_until` that records every universe's population curve inside the kernel (`ca3d_ensemble_step_until_trace`): one sample
+        (population, births, deaths) per check point, K = `host.trace_samples(max_steps, check_every)` of them at most
+        -> (samples u32[n, K, 3], n_samples u32[n], steps_done u32[n], reason u32[n]). Slots past n_samples[u] are zero. `stop_mask`:
+        STOP_EXTINCT | STOP_STILL bits; 0 (the default): nothing stops and every universe has K samples."""
+        if self.n == 0 or check_every < 1:  # no K to size the array with: the library names the error
+            _capi.check(self._lib.ca3d_ensemble_step_until_trace(self._h, max_steps, check_every, stop_mask, None, None, None, 0, None))
+        k = host.trace_samples(max_steps, check_every)
+        samples = np.zeros((self.n, k, 3), dtype=np.uint32)
+        count, done, reason = (np.empty(self.n, dtype=np.uint32) for _ in range(3))
+        _capi.check(self._lib.ca3d_ensemble_step_until_trace(self._h, max_steps, check_every, stop_mask, done.ctypes.data_as(_u32p),
+                                                             reason.ctypes.data_as(_u32p), samples.ctypes.data_as(_u32p), k,
+                                                             count.ctypes.data_as(_u32p)))
+        return samples, count, done, reason
+
     def summaries(self, first: int = 0, count: Optional[int] = None) -> List[Summary]:
         """The universes' records (no per-plane counts): copied, not computed — every launch leaves them up to date."""
         count = self.n - first if count is None else count

@@ -130,6 +130,14 @@ def words_per_buffer(grid_size: int) -> int:
     return (grid_size // 32) * grid_size * grid_size
 
 
+def trace_samples(max_steps: int, check_every: int) -> int:
+    """K of `ca3d_ensemble_step_until_trace` (include/ca3d.h): the samples one universe can leave — one per check point at steps 0,
+    check_every, 2 check_every ... of the call, and the last one at max_steps."""
+    if check_every < 1 or max_steps < 0:
+        raise ValueError("check_every must be at least 1 and max_steps at least 0")
+    return -(-max_steps // check_every) + 1
+
+
 def get_cluster_idx_from_grid_coordinates(grid_size: int, x: int, y: int, z: int) -> int:
     """`_getClusterIdxFromGridCoordinates` (main_pathtraced.js:1170-1178)."""
     cols = grid_size // 32

@@ -120,6 +120,14 @@ function dispatchShape(gridSize)
 	return [gridSize / 32, wg, wg]; // main_pathtraced.js:1805-1806
 }
 
+// K of ca3d_ensemble_step_until_trace (include/ca3d.h; host.trace_samples): the samples one universe can leave — one per check point at
+// steps 0, checkEvery, 2 checkEvery ... of the call, and the last one at maxSteps
+function traceSamples(maxSteps, checkEvery)
+{
+	if (!(checkEvery >= 1) || !(maxSteps >= 0)) { throw new RangeError("checkEvery must be at least 1 and maxSteps at least 0"); }
+	return Math.ceil(maxSteps / checkEvery) + 1;
+}
+
 // counter-based synthetic fill shared with host.py / the oracle (SURVEY 8(d))
 function randomFill(nWords, seed, andRounds)
 {
@@ -483,6 +491,20 @@ class Ensemble
 		this._a.ensembleStepUntilCycle(this._e, maxSteps, o.checkEvery, o.stopMask, stepsDone, reason, period);
 		return { stepsDone, reason, period };
 	}
+	/** stepUntil that records every universe's population curve inside the kernel: one sample (population, births, deaths) per check
+	 *  point -> {samples: Uint32Array(n * samplesPerUniverse * 3), samplesPerUniverse, nSamples, stepsDone, reason}; sample j of universe u
+	 *  starts at samples[(u * samplesPerUniverse + j) * 3], slots past nSamples[u] are zero. stopMask: STOP_EXTINCT | STOP_STILL bits;
+	 *  0 (the default): nothing stops and every universe has samplesPerUniverse samples. */
+	stepTrace(maxSteps, checkEvery, stopMask)
+	{
+		checkEvery = checkEvery === undefined ? 8 : checkEvery;
+		// (checkEvery 0: no K to size the array with — the library names the error)
+		const samplesPerUniverse = checkEvery >= 1 ? traceSamples(maxSteps, checkEvery) : 1;
+		const samples = new Uint32Array(this.n * samplesPerUniverse * 3);
+		const nSamples = new Uint32Array(this.n), stepsDone = new Uint32Array(this.n), reason = new Uint32Array(this.n);
+		this._a.ensembleStepUntilTrace(this._e, maxSteps, checkEvery, stopMask || 0, stepsDone, reason, samples, samplesPerUniverse, nSamples);
+		return { samples, samplesPerUniverse, nSamples, stepsDone, reason };
+	}
 	/** the universes' records, as Engine.summary() objects without planePopulation */
 	summaries(first, count) { first = first || 0; return this._a.ensembleSummaries(this._e, first, count === undefined ? this.n - first : count); }
 	synchronize() { this._a.ensembleSynchronize(this._e); }
@@ -492,5 +514,5 @@ class Ensemble
 module.exports = {
 	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
-	initialState, dispatchShape, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
+	initialState, dispatchShape, traceSamples, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
 };

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_*; + ca3d_seed_state, ca3d_group_seed_state, ca3d_ensemble_seed_state, ca3d_ensemble_set_rule_tables; + ca3d_ensemble_configure_neighbourhood, ca3d_ensemble_get_neighbourhood; + CA3D_STOP_PERIODIC, ca3d_step_until_cycle, ca3d_ensemble_step_until_cycle */
+#define CA3D_ABI_VERSION 7 /* 5: + ca3d_get_kernel_variant; 6: + ca3d_selftest_exception, the kernel cache (ca3d_get_jit_log reports it); 7: + ca3d_get_render_pipeline; still 7 (additions only): + ca3d_summarize, ca3d_group_summarize, ca3d_step_until, ca3d_get_summary_time; + ca3d_ensemble_*; + ca3d_seed_state, ca3d_group_seed_state, ca3d_ensemble_seed_state, ca3d_ensemble_set_rule_tables; + ca3d_ensemble_configure_neighbourhood, ca3d_ensemble_get_neighbourhood; + CA3D_STOP_PERIODIC, ca3d_step_until_cycle, ca3d_ensemble_step_until_cycle; + ca3d_ensemble_step_until_trace */
 #define CA3D_LUT_LEN 81 /* 3 rule-sets x 27 slots (main_pathtraced.js:10, 155-159) */
 
 typedef struct ca3d_engine ca3d_t;
@@ -408,6 +408,27 @@ int ca3d_ensemble_step_until(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t ch
  * CA3D_STOP_PERIODIC. Everything else — launch cutting at 65 536 steps, stats, records, readiness errors — as ca3d_ensemble_step_until. */
 int ca3d_ensemble_step_until_cycle(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
                                    uint32_t *reason, uint32_t *period);
+/* ca3d_ensemble_step_until that also RECORDS each universe's population curve, written by the kernel (ca_ensemble_vn64_trace /
+ * ca_ensemble_moore64_trace): one sample — population, births, deaths, meaning what they mean in ca3d_summary, births and deaths against
+ * the state one step earlier — per check point and universe, with no launch, synchronisation or read-back per sample.
+ * The definition. A call (max_steps, check_every, stop_mask) visits the check points of ca3d_ensemble_step_until: steps 0, check_every,
+ * 2 check_every ... of the call, and one last at max_steps when max_steps is no multiple of check_every. Check point number j of
+ * universe u fills samples[u][j]:
+ *   j = 0 (entry): the universe's stored record as it stands — its population, births, deaths; births and deaths are 0 when
+ *     has_previous is 0, as after an upload or a seed;
+ *   j > 0: from the registers, the current state against the state one step earlier.
+ * A universe that stops at a check point has that check point's sample as its last: the sample is taken before the stop decision.
+ * n_samples[u] is the number of check points the universe reached, entry included; slots past it are zero.
+ * samples: [B][samples_per_universe][3] words (population, births, deaths), required. samples_per_universe must be at least
+ * K = ceil(max_steps / check_every) + 1, else CA3D_ERR_INVALID_ARGUMENT with a message that names K; slots K and above are zeroed.
+ * steps_done, reason, n_samples: B entries each, nullable. stop_mask: any subset of CA3D_STOP_EXTINCT | CA3D_STOP_STILL; 0 is allowed —
+ * nothing stops, every universe has K samples and steps_done[u] == max_steps. CA3D_STOP_PERIODIC is refused here (unknown bits,
+ * CA3D_ERR_INVALID_ARGUMENT) as ca3d_ensemble_step_until refuses it. The samples live in a device array on the handle (B x K x 3 words,
+ * grown when a call needs more, freed by a configure; CA3D_ERR_OUT_OF_MEMORY when it cannot be had, the other arrays untouched). A
+ * refused call leaves the caller's arrays as they were. Everything else — steps_done and reason, states and records after the call,
+ * stats, readiness errors, launch cutting at 65 536 steps — as ca3d_ensemble_step_until. */
+int ca3d_ensemble_step_until_trace(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                                   uint32_t *reason, uint32_t *samples, uint32_t samples_per_universe, uint32_t *n_samples);
 int ca3d_ensemble_summarize(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_summary *out);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);

@@ -20,6 +20,16 @@ states with every universe still running; then the two alternate from freshly up
 the launch (Ensemble.stats) and of the host clock around the call are reported. Written to profiles/ensemble_cycle_64.json unless --out
 says otherwise.
 
+--trace measures what a population curve costs, for both neighbourhoods: (a) Ensemble.step_trace(steps, check_every, stop mask 0) — the
+*_trace kernels write one sample (population, births, deaths) per check point and universe — against (b) the path without it, K - 1
+rounds of ca3d_ensemble_step(check_every) + ca3d_ensemble_summarize collecting the same three numbers from the records (through the C
+ABI into one preallocated array, no Python object per record: the loop at its best), and (c) a plain step(steps) as the floor — B = 256
+and 1024, 256 steps, check_every 1 and 8, density-1/2 fills. Before timing, (a) and (b) must give identical arrays; then the three
+alternate from freshly uploaded states and the medians of the hipEvent time around the launches (Ensemble.stats; (b): summed over its
+launches, in a run of its own) and of the host clock around the call are reported with their spread. The host clock is the fair one for (b), whose cost is
+its synchronisations. Written to profiles/ensemble_trace_64.json unless --out says otherwise; the tool fails when (a) does not beat
+(b) by the host clock by more than the spread, after the file is written.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -115,6 +125,87 @@ def cycle_rows(args):
     return rows
 
 
+def trace_rows(args):
+    """step_trace against the step + summaries loop and against plain stepping: one row per (neighbourhood, B, check_every)."""
+    import ctypes as C
+
+    lib = _capi.load()
+    ens = Ensemble(0)
+    rows = []
+    for nb in ("von neumann", "moore"):
+        born, survive = RULES[nb]
+        for B in args.universes:
+            words = fills(B)
+            ens.configure(B, neighbourhood=nb)
+            ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood=nb, born=born, survive=survive)
+            recs = (_capi.SummaryStruct * B)()
+            view = np.frombuffer(recs, dtype=np.dtype(_capi.SummaryStruct))
+            for every in (1, 8):
+                K = host.trace_samples(args.steps, every)
+
+                def traced():
+                    """(a) -> (event ms, wall ms, samples)"""
+                    ens.upload_state(0, words)
+                    t0 = time.perf_counter()
+                    samples = ens.step_trace(args.steps, check_every=every, stop_mask=0)[0]
+                    wall = (time.perf_counter() - t0) * 1e3
+                    return ens.stats().gpu_ms, wall, samples
+
+                def looped(events=False):
+                    """(b) -> (event ms summed over the launches when asked for — a call per round the host clock should not pay, wall ms, samples)"""
+                    ens.upload_state(0, words)
+                    t0 = time.perf_counter()
+                    samples = np.zeros((B, K, 3), dtype=np.uint32)
+                    event = 0.0
+                    done = 0
+                    for j in range(K):
+                        if j:
+                            n = min(every, args.steps - done)
+                            ens.step(n)
+                            done += n
+                        _capi.check(lib.ca3d_ensemble_summarize(ens._h, 0, B, recs))  # synchronises the stream
+                        samples[:, j, 0], samples[:, j, 1], samples[:, j, 2] = view["population"], view["births"], view["deaths"]
+                        if j and events:
+                            event += ens.stats().gpu_ms
+                    wall = (time.perf_counter() - t0) * 1e3
+                    return event, wall, samples
+
+                def plain():
+                    """(c) -> (event ms, wall ms, None)"""
+                    ens.upload_state(0, words)
+                    t0 = time.perf_counter()
+                    ens.step(args.steps)
+                    ens.synchronize()
+                    wall = (time.perf_counter() - t0) * 1e3
+                    return ens.stats().gpu_ms, wall, None
+
+                a, b = traced()[2], looped()[2]
+                if not np.array_equal(a, b):
+                    raise SystemExit(f"{nb} B={B} check_every={every}: step_trace and the step + summaries loop gave different samples")
+                plain()
+                paths = {"step_trace": traced, "step_summaries_loop": looped, "plain_step": plain}
+                times = {name: [] for name in paths}
+                for _ in range(args.repeats):
+                    for name, fn in paths.items():
+                        times[name].append(fn()[:2])
+                    # (b) again for its event time alone
+                    times["step_summaries_loop"][-1] = (looped(events=True)[0], times["step_summaries_loop"][-1][1])
+                row = {"neighbourhood": nb, "universes": B, "steps": args.steps, "check_every": every, "samples_per_universe": K, "samples_verified": int(a.size)}
+                for name, t in times.items():
+                    row[name] = {"event_us": statistics.median(x[0] for x in t) * 1e3, "event_us_min_max": [min(x[0] for x in t) * 1e3, max(x[0] for x in t) * 1e3],
+                                 "wall_us": statistics.median(x[1] for x in t) * 1e3, "wall_us_min_max": [min(x[1] for x in t) * 1e3, max(x[1] for x in t) * 1e3]}
+                row["loop_over_trace_wall"] = row["step_summaries_loop"]["wall_us"] / row["step_trace"]["wall_us"]
+                row["loop_over_trace_event"] = row["step_summaries_loop"]["event_us"] / row["step_trace"]["event_us"]
+                row["trace_over_plain_event"] = row["step_trace"]["event_us"] / row["plain_step"]["event_us"]
+                row["trace_over_plain_wall"] = row["step_trace"]["wall_us"] / row["plain_step"]["wall_us"]
+                # by more than the spread: the slowest traced call against the fastest loop
+                row["trace_beats_loop_beyond_spread"] = row["step_trace"]["wall_us_min_max"][1] < row["step_summaries_loop"]["wall_us_min_max"][0]
+                rows.append(row)
+                print(json.dumps(row))
+    ens.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -124,10 +215,11 @@ def main():
     ap.add_argument("--neighbourhood", choices=sorted(RULES), default="von neumann", help="of the ensemble and of the rule both paths run")
     ap.add_argument("--out", default=None, help="JSON file to write (moore: profiles/ensemble_moore_64.json)")
     ap.add_argument("--cycle", action="store_true", help="measure step_until_cycle against step_until instead (both neighbourhoods; default B = 256 1024)")
+    ap.add_argument("--trace", action="store_true", help="measure step_trace against the step + summaries loop and plain stepping instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256, 1024] if args.cycle else [1, 256, 1024, 4096]
+        args.universes = [256, 1024] if args.cycle or args.trace else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     born, survive = RULES[nb]
     if args.out is None and nb == "moore":
@@ -138,6 +230,26 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.trace:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_trace_64.json")
+        result = {
+            "what": "B universes of 64^3, random fills (density 1/2), rules B2,4/S1,3,5 (von Neumann) and B5-7/S4-6 (Moore): (a) Ensemble.step_trace(steps, check_every, "
+                    "stop mask 0) vs. (b) K - 1 rounds of ca3d_ensemble_step(check_every) + ca3d_ensemble_summarize collecting the same samples vs. (c) a plain step(steps)",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {nb_: {"step_trace": KERNELS[nb_] + "_trace", "step_summaries_loop": KERNELS[nb_], "plain_step": KERNELS[nb_]} for nb_ in sorted(KERNELS)},
+            "timing": f"one call from freshly uploaded states; hipEvent time around the launches ((b): summed over its launches) and host clock around the call; medians of "
+                      f"{args.repeats} measurements, the three paths alternating in one process, after (a) and (b) gave identical arrays",
+            "rows": trace_rows(args),
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        lost = [(r["neighbourhood"], r["universes"], r["check_every"]) for r in result["rows"] if not r["trace_beats_loop_beyond_spread"]]
+        if lost:
+            raise SystemExit(f"step_trace does not beat the step + summaries loop by more than the spread at {lost}")
+        return
     if args.cycle:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_cycle_64.json")
         result = {
