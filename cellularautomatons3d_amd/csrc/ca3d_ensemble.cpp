@@ -1,5 +1,6 @@
-// ca3d_ensemble_*: many independent 64^3 universes side by side on one device (include/ca3d.h). One workgroup of ca_ensemble_vn64 or
-// ca_ensemble_moore64 (ca_ensemble.hip; the ensemble's neighbourhood decides) steps one universe with its state in registers; a launch
+// ca3d_ensemble_*: many independent 64^3 universes side by side on one device (include/ca3d.h). One workgroup of ca_ensemble_vn64,
+// ca_ensemble_moore64 or ca_ensemble_clustered64 (ca_ensemble.hip; the ensemble's neighbourhood and `clustered` decide) steps one
+// universe with its state in registers; a launch
 // over B workgroups is B universes, each with its own rule table pair, its own step counter, its own summary record and — in
 // ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle / ca3d_ensemble_step_until_trace — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
@@ -19,6 +20,7 @@ struct ca3d_ensemble
 	hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 	uint32_t n = 0; // universes; 0: not configured
 	int neighbourhood = CA3D_ENSEMBLE_VON_NEUMANN; // of every universe: the kernel, and ensemble_rule_words() words of `rules` each
+	bool clustered = false;                        // Moore with edges and corners table pairs of their own (ca3d_ensemble_configure_clustered)
 	uint32_t *state = nullptr, *prev = nullptr, *rules = nullptr, *steps_done = nullptr, *reason = nullptr;
 	ca3d_summary *records = nullptr;
 	// ca3d_ensemble_step_until_cycle: every universe's anchor state (n x 32 KiB) and its anchor step / anchor hash / period / unused
@@ -79,6 +81,7 @@ EnsembleLaunch launch_of(const ca3d_ensemble *e)
 	l.state = e->state; l.prev = e->prev;
 	l.rules = e->rules;
 	l.neighbourhood = e->neighbourhood;
+	l.clustered = e->clustered;
 	l.records = e->records;
 	l.steps_done = e->steps_done; l.reason = e->reason;
 	l.anchor = e->anchor; l.cycle = e->cycle;
@@ -89,17 +92,32 @@ EnsembleLaunch launch_of(const ca3d_ensemble *e)
 bool moore(const ca3d_ensemble *e) { return e->neighbourhood == CA3D_ENSEMBLE_MOORE; }
 uint32_t table_bits(const ca3d_ensemble *e) { return moore(e) ? 27u : 7u; } // counts 0 .. 26 / 0 .. 6
 
-// what a universe's born / survive masks are stored as (ca_ensemble.hip reads it back: VnStep::load, MooreStep::load)
+uint32_t rule_words(const ca3d_ensemble *e) { return ensemble_rule_words(e->neighbourhood, e->clustered); }
+constexpr uint32_t kClusteredBits[3] = {27u, 13u, 9u}; // main 0 .. 26, edges 0 .. 12, corners 0 .. 8
+
+// what a universe's born / survive masks are stored as (ca_ensemble.hip reads it back: VnStep::load, MooreStep::load, ClusteredStep::load);
+// in a clustered ensemble the main pair with both side pairs silent
 void pack_rule(const ca3d_ensemble *e, uint32_t born, uint32_t survive, uint32_t *out)
 {
-	if (moore(e)) { out[0] = born; out[1] = survive; }
+	if (e->clustered) { out[0] = born; out[1] = survive; out[2] = out[3] = out[4] = out[5] = 0u; }
+	else if (moore(e)) { out[0] = born; out[1] = survive; }
 	else out[0] = survive | born << 8;
+}
+// a clustered universe's three pairs (main, edges, corners); bits no count can reach are dropped
+void pack_clustered(const uint32_t born[3], const uint32_t survive[3], uint32_t *out)
+{
+	for (int s = 0; s < 3; s++)
+	{
+		const uint32_t mask = (1u << kClusteredBits[s]) - 1u;
+		out[2 * s] = born[s] & mask;
+		out[2 * s + 1] = survive[s] & mask;
+	}
 }
 
 // `words`: ensemble_rule_words() words for each of universes [first, first + count)
 int store_rules(ca3d_ensemble *e, uint32_t first, uint32_t count, const std::vector<uint32_t> &words)
 {
-	const uint32_t per = ensemble_rule_words(e->neighbourhood);
+	const uint32_t per = rule_words(e);
 	HIP_TRY(hipSetDevice(e->device));
 	// stream-ordered behind the steps already enqueued, which keep the rules they were enqueued under; the source is consumed on return
 	HIP_TRY(hipMemcpyAsync(e->rules + (size_t)first * per, words.data(), (size_t)count * per * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
@@ -109,7 +127,7 @@ int store_rules(ca3d_ensemble *e, uint32_t first, uint32_t count, const std::vec
 	return CA3D_OK;
 }
 
-int configure_ensemble(ca3d_ensemble *e, uint32_t grid_size, uint32_t n_universes, int neighbourhood)
+int configure_ensemble(ca3d_ensemble *e, uint32_t grid_size, uint32_t n_universes, int neighbourhood, bool clustered = false)
 {
 	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
 	if (neighbourhood != CA3D_ENSEMBLE_VON_NEUMANN && neighbourhood != CA3D_ENSEMBLE_MOORE)
@@ -122,7 +140,7 @@ int configure_ensemble(ca3d_ensemble *e, uint32_t grid_size, uint32_t n_universe
 	const size_t state_bytes = (size_t)n_universes * kEnsembleWords * sizeof(uint32_t), word_bytes = (size_t)n_universes * sizeof(uint32_t);
 	hipError_t err = hipMalloc((void **)&e->state, state_bytes);
 	if (err == hipSuccess) err = hipMalloc((void **)&e->prev, state_bytes);
-	if (err == hipSuccess) err = hipMalloc((void **)&e->rules, word_bytes * ensemble_rule_words(neighbourhood));
+	if (err == hipSuccess) err = hipMalloc((void **)&e->rules, word_bytes * ensemble_rule_words(neighbourhood, clustered));
 	if (err == hipSuccess) err = hipMalloc((void **)&e->steps_done, word_bytes);
 	if (err == hipSuccess) err = hipMalloc((void **)&e->reason, word_bytes);
 	if (err == hipSuccess) err = hipMalloc((void **)&e->records, (size_t)n_universes * sizeof(ca3d_summary));
@@ -134,6 +152,7 @@ int configure_ensemble(ca3d_ensemble *e, uint32_t grid_size, uint32_t n_universe
 	}
 	e->n = n_universes;
 	e->neighbourhood = neighbourhood;
+	e->clustered = clustered;
 	e->has_rules.assign(n_universes, 0);
 	e->has_state.assign(n_universes, 0);
 	e->missing_rules = e->missing_state = n_universes;
@@ -346,6 +365,21 @@ int ca3d_ensemble_configure_neighbourhood(ca3d_ensemble_t *e, uint32_t grid_size
 }
 CA3D_API_CATCH
 
+int ca3d_ensemble_configure_clustered(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes) CA3D_API_TRY
+{
+	return configure_ensemble(e, grid_size, n_universes, CA3D_ENSEMBLE_MOORE, true);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_get_clustered(ca3d_ensemble_t *e, int *out) CA3D_API_TRY
+{
+	if (!e || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called");
+	*out = e->clustered ? 1 : 0;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
 int ca3d_ensemble_get_neighbourhood(ca3d_ensemble_t *e, int *out) CA3D_API_TRY
 {
 	if (!e || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -369,10 +403,31 @@ int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe, const int32_t
 	rc = canonicalize_rules(main_offsets, n_main, edges_offsets, n_edges, corners_offsets, n_corners, survive, born, &r, &err);
 	if (rc) return fail(rc, "%s: %s", who.c_str(), err.c_str());
 	uint32_t lut_s, lut_b;
+	const uint32_t first = all ? 0u : universe, count = all ? e->n : 1u;
+	if (e->clustered)
+	{
+		// r.fast: a side list whose count matters IS the standard one; a side table whose count does not matter is a constant over the
+		// counts its own list can reach (slot 0 is always one of them), and is stored as that constant over the standard list's counts
+		if (r.main != MAIN_MOORE || !r.fast)
+			return fail(CA3D_ERR_UNSUPPORTED, "%s: this ensemble is clustered and takes rules whose main list is Moore and whose edges / corners lists are the standard ones",
+			            who.c_str());
+		uint32_t b3[3] = {r.onset_born[0], 0u, 0u}, s3[3] = {r.onset_survive[0], 0u, 0u};
+		for (int s = 1; s < 3; s++)
+		{
+			b3[s] = r.need[s] ? r.onset_born[s] : 0u - (r.onset_born[s] & 1u);
+			s3[s] = r.need[s] ? r.onset_survive[s] : 0u - (r.onset_survive[s] & 1u);
+		}
+		uint32_t one[6];
+		pack_clustered(b3, s3, one);
+		std::vector<uint32_t> words((size_t)count * 6u);
+		for (size_t k = 0; k < words.size(); k++) words[k] = one[k % 6u];
+		return store_rules(e, first, count, words);
+	}
 	if (moore(e))
 	{
 		if (r.main != MAIN_MOORE || !side_tables_silent(r))
-			return fail(CA3D_ERR_UNSUPPORTED, "%s: this ensemble is Moore and takes rules that reduce to a Moore table pair (main list Moore, edges / corners tables that cannot fire)",
+			return fail(CA3D_ERR_UNSUPPORTED, "%s: this ensemble is Moore and takes rules that reduce to a Moore table pair (main list Moore, edges / corners tables that cannot fire; "
+			                                  "tables that fire want a clustered ensemble, ca3d_ensemble_configure_clustered)",
 			            who.c_str());
 		lut_s = r.onset_survive[0];
 		lut_b = r.onset_born[0];
@@ -384,10 +439,9 @@ int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe, const int32_t
 			            who.c_str());
 		vn_tables(r, &lut_s, &lut_b);
 	}
-	const uint32_t mask = (1u << table_bits(e)) - 1u, per = ensemble_rule_words(e->neighbourhood);
+	const uint32_t mask = (1u << table_bits(e)) - 1u, per = rule_words(e);
 	uint32_t one[2];
 	pack_rule(e, lut_b & mask, lut_s & mask, one);
-	const uint32_t first = all ? 0u : universe, count = all ? e->n : 1u;
 	std::vector<uint32_t> words((size_t)count * per);
 	for (size_t k = 0; k < words.size(); k++) words[k] = one[k % per];
 	return store_rules(e, first, count, words);
@@ -464,7 +518,7 @@ int ca3d_ensemble_set_rule_tables(ca3d_ensemble_t *e, uint32_t first, uint32_t c
 	int rc = check_range(e, first, count);
 	if (rc) return rc;
 	if (n_masks != 1u && n_masks != count) return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes take 1 or %u mask pairs (got %u)", count, count, n_masks);
-	const uint32_t bits = table_bits(e), per = ensemble_rule_words(e->neighbourhood);
+	const uint32_t bits = table_bits(e), per = rule_words(e);
 	std::vector<uint32_t> words((size_t)count * per);
 	for (uint32_t k = 0; k < count; k++)
 	{
@@ -473,6 +527,30 @@ int ca3d_ensemble_set_rule_tables(ca3d_ensemble_t *e, uint32_t first, uint32_t c
 			return fail(CA3D_ERR_INVALID_ARGUMENT, "universe %u: born mask %#x / survive mask %#x — a %s count is 0 .. %u, bits %u and above mean nothing", first + k, b, s,
 			            moore(e) ? "Moore" : "von Neumann", bits - 1u, bits);
 		pack_rule(e, b, s, &words[(size_t)k * per]); // what ca3d_ensemble_set_rules stores
+	}
+	return store_rules(e, first, count, words);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_set_rule_tables_clustered(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *born_masks, const uint32_t *survive_masks,
+                                            uint32_t n_rules) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!born_masks || !survive_masks) return fail(CA3D_ERR_INVALID_ARGUMENT, "a mask array is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if (!e->clustered) return fail(CA3D_ERR_UNSUPPORTED, "this ensemble is not clustered (ca3d_ensemble_configure_clustered): a universe has one table pair, ca3d_ensemble_set_rule_tables sets it");
+	if (n_rules != 1u && n_rules != count) return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes take 1 or %u rules (got %u)", count, count, n_rules);
+	static const char *names[3] = {"main", "edges", "corners"};
+	std::vector<uint32_t> words((size_t)count * 6u);
+	for (uint32_t k = 0; k < count; k++)
+	{
+		const uint32_t *b = born_masks + (n_rules == 1u ? 0u : 3u * (size_t)k), *s = survive_masks + (n_rules == 1u ? 0u : 3u * (size_t)k);
+		for (int i = 0; i < 3; i++)
+			if ((b[i] | s[i]) >> kClusteredBits[i])
+				return fail(CA3D_ERR_INVALID_ARGUMENT, "universe %u: %s born mask %#x / survive mask %#x — the count is 0 .. %u, bits %u and above mean nothing", first + k,
+				            names[i], b[i], s[i], kClusteredBits[i] - 1u, kClusteredBits[i]);
+		pack_clustered(b, s, &words[(size_t)k * 6u]); // what ca3d_ensemble_set_rules stores
 	}
 	return store_rules(e, first, count, words);
 }

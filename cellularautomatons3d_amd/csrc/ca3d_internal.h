@@ -202,8 +202,10 @@ constexpr uint32_t kEnsembleMaxSteps = 65536;  // steps of one launch at most: a
 struct EnsembleLaunch
 {
 	uint32_t *state, *prev;   // [B][8192] current state / the state one step earlier
-	const uint32_t *rules;    // von Neumann: [B] lut_s | lut_b << 8 (7 bits each, vn_tables); Moore: [B][2] born, survive (27 bits each)
+	const uint32_t *rules;    // von Neumann: [B] lut_s | lut_b << 8 (7 bits each, vn_tables); Moore: [B][2] born, survive (27 bits each);
+	                          // clustered: [B][6] born, survive of the main (27 bits), edges (13) and corners (9) rule-sets
 	int neighbourhood;        // CA3D_ENSEMBLE_VON_NEUMANN / CA3D_ENSEMBLE_MOORE: which kernel, and how `rules` reads
+	bool clustered;           // Moore only: three table pairs a universe (ca_ensemble_clustered64)
 	ca3d_summary *records;    // [B] what the last launch left of each universe
 	uint32_t *steps_done;     // [B] steps taken in the current step-until call (written when stop_mask != 0)
 	uint32_t *reason;         // [B] stop bits that fired in the current call; a universe whose word is set leaves at once
@@ -219,8 +221,11 @@ struct EnsembleLaunch
 	bool reset;               // after an upload: records are rebuilt with step 0 and no previous state (steps == 0)
 };
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream);
-int ensemble_workgroups_per_cu(int neighbourhood); // what the runtime says of that neighbourhood's kernel (0: it cannot tell)
-constexpr uint32_t ensemble_rule_words(int neighbourhood) { return neighbourhood == CA3D_ENSEMBLE_MOORE ? 2u : 1u; } // per universe
+int ensemble_workgroups_per_cu(int neighbourhood, bool clustered = false); // what the runtime says of that kind's kernel (0: it cannot tell)
+constexpr uint32_t ensemble_rule_words(int neighbourhood, bool clustered = false) // per universe
+{
+	return clustered ? 6u : neighbourhood == CA3D_ENSEMBLE_MOORE ? 2u : 1u;
+}
 // ca_seed.hip: the counter-based fill of ca3d_seed (include/ca3d.h) written where the state lives. One launch covers the whole arrays of
 // both ping-pong buffers: array plane a is global plane z0 - ghost + a; the `ghost` planes below and above the owned ones are zeroed.
 struct SeedLaunch

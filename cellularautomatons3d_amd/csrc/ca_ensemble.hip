@@ -19,9 +19,10 @@
 //     universe whose condition holds writes its state and record and leaves; the CU takes the next workgroup.
 // There are no waits on other workgroups, no spins, and nothing but vector stores.
 //
-// Two kernels share everything but the step: ca_ensemble_vn64 (above) and ca_ensemble_moore64, whose rule is a Moore table pair (27 + 27
-// bits, two words per universe). The body — entry check from the stored record, check points, record reduction, write-back — is
-// ensemble_run<Step, Cycle, Trace>; a Step policy (VnStep, MooreStep) owns the rule's registers, the size of the LDS exchange and one step.
+// Three kernels share everything but the step: ca_ensemble_vn64 (above), ca_ensemble_moore64, whose rule is a Moore table pair (27 + 27
+// bits, two words per universe), and ca_ensemble_clustered64, whose rule is three pairs — main (Moore), edges, corners — ORed (six words).
+// The body — entry check from the stored record, check points, record reduction, write-back — is ensemble_run<Step, Cycle, Trace>; a Step
+// policy (VnStep, MooreStep, ClusteredStep) owns the rule's registers, the size of the LDS exchange and one step.
 // The *_cycle kernels watch CA3D_STOP_PERIODIC as well; the *_trace kernels leave a sample (population, births, deaths) per check point.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -274,6 +275,127 @@ struct MooreStep
 			if (!wave) below = Sum4{{0u, 0u, 0u, 0u}}; // z == -1 is dead
 			o[0][h] = rule(s[0][h], below, get(wave, 0u, h), q[0][h]);
 			o[kPT - 1][h] = rule(s[kPT - 1][h], q[kPT - 3][h], get(wave, 1u, h), get((wave + 1u) & (kWaves - 1u), 0u, h)); // z == 64 is plane 0
+		}
+	}
+};
+
+// ---- clustered: six words per universe, born | survive of the main (Moore, counts 0 .. 26), edges (0 .. 12) and corners (0 .. 8) rule-sets
+// A cell is alive afterwards if ANY of the three lookups says so (oracle/ca_oracle.c, lit_next). A Moore total does not separate the
+// classes, so a word of a plane is summarised as seven bit planes that do: `c`, the word itself; D = left + right + c(y - 1) + c(y + 1),
+// the four in-plane face neighbours (0 .. 4); As = the left and right neighbours of rows y - 1 and y + 1, the four in-plane diagonals
+// (0 .. 4). With b, m, a for the planes z - 1, z, z + 1:
+//     faces   F = D(m) + c(b) + c(a)        edges   E = As(m) + D(b) + D(a)        corners   C = As(b) + As(a)        T = F + E + C
+// Every axis applies its own boundary to what the axis before it produced (x: alignbit, y: DPP, z: the exchange), as in MooreStep.
+// The RAW words of a wave's first and last plane go through the von Neumann exchange (32 KiB); a thread then slides a window of three
+// planes' sets over the six planes it sees, one word of a row at a time: 21 registers of sets alive, not 6 x 7 x 2.
+struct ClusteredStep
+{
+	static constexpr u32 kXchWords = VnStep::kXchWords;
+	// all-zeros / all-ones per table bit: the born leaves in vector registers, the survive leaves in scalar ones (a select reads ONE scalar)
+	u32 bornM[27], survM[27], bornE[13], survE[13], bornC[9], survC[9];
+
+	template <int N>
+	static __device__ __forceinline__ void expand(u32 b, u32 sv, u32 (&born)[N], u32 (&surv)[N])
+	{
+#pragma unroll
+		for (int c = 0; c < N; c++)
+		{
+			born[c] = 0u - ((b >> c) & 1u);
+			surv[c] = 0u - ((sv >> c) & 1u);
+			asm volatile("" : "+v"(born[c]));
+			asm volatile("" : "+s"(surv[c]));
+		}
+	}
+	__device__ __forceinline__ void load(const u32 *rules, u32 u)
+	{
+		const u32 *r = rules + 6u * u;
+		expand<27>(r[0], r[1], bornM, survM);
+		expand<13>(r[2], r[3], bornE, survE);
+		expand<9>(r[4], r[5], bornC, survC);
+	}
+	struct Set { u32 c, d[3], as[3]; };
+
+	// x and y of one word
+	static __device__ __forceinline__ Set plane_set(u32 w, u32 other, u32 h)
+	{
+		const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
+		const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
+		Set q;
+		q.c = w;
+		// row y - 1 (zero into row 0), row y + 1 (row 0 into row 63)
+		sum4(l, r, dpp_mov<kDppWaveShr1>(w), dpp_mov<kDppWaveRol1>(w), q.d);
+		sum4(dpp_mov<kDppWaveShr1>(l), dpp_mov<kDppWaveShr1>(r), dpp_mov<kDppWaveRol1>(l), dpp_mov<kDppWaveRol1>(r), q.as);
+		return q;
+	}
+	// a multiplexer tree over N leaves (counts 0 .. N - 1) and the count's bit planes p[0] ..; a node without a partner moves up as it is
+	template <int N>
+	static __device__ __forceinline__ u32 tree(u32 w, const u32 (&born)[N], const u32 (&surv)[N], const u32 *p)
+	{
+		u32 t[N];
+#pragma unroll
+		for (int i = 0; i < N; i++) t[i] = mux(w, surv[i], born[i]);
+		int n = N;
+#pragma unroll
+		for (int level = 0; level < 5; level++)
+		{
+			if (n > 1)
+			{
+#pragma unroll
+				for (int i = 0; i < N / 2; i++)
+					if (2 * i + 1 < n) t[i] = mux(p[level], t[2 * i + 1], t[2 * i]);
+				if (n & 1) t[n / 2] = t[n - 1];
+				n = (n + 1) / 2;
+			}
+		}
+		return t[0];
+	}
+	// z and the rule: three planes' sets -> F, E, C, T -> three multiplexers, ORed
+	__device__ __forceinline__ u32 rule(const Set &b, const Set &m, const Set &a) const
+	{
+		u32 F[3], E[4], C[4], T[5], k1, k2, k3, k4, k5, x, y;
+		fa(m.d[0], b.c, a.c, F[0], k1);
+		ha(m.d[1], k1, F[1], k2);
+		F[2] = m.d[2] | k2; // D == 4 leaves no carry below it
+		fa(m.as[0], b.d[0], a.d[0], E[0], k1);
+		fa(m.as[1], b.d[1], a.d[1], x, k2);
+		ha(x, k1, E[1], k3);
+		fa(m.as[2], b.d[2], a.d[2], y, k4);
+		fa(y, k2, k3, E[2], k5);
+		E[3] = k4 | k5; // E <= 12: one carry into plane 3 at most
+		ha(b.as[0], a.as[0], C[0], k1);
+		fa(b.as[1], a.as[1], k1, C[1], k2);
+		fa(b.as[2], a.as[2], k2, C[2], C[3]);
+		sum_moore(F, E, C, T);
+		const u32 w = m.c;
+		return bitop3<(TA | TB | TC)>(tree<27>(w, bornM, survM, T), tree<13>(w, bornE, survE, E), tree<9>(w, bornC, survC, C));
+	}
+
+	__device__ __forceinline__ void step(const u32 (&s)[kPT][2], u32 (&o)[kPT][2], u32 *xch, u32 buf, u32 wave, u32 row) const
+	{
+		xch[VnStep::slot(buf, wave, 0u, 0u, row)] = s[0][0];
+		xch[VnStep::slot(buf, wave, 0u, 1u, row)] = s[0][1];
+		xch[VnStep::slot(buf, wave, 1u, 0u, row)] = s[kPT - 1][0];
+		xch[VnStep::slot(buf, wave, 1u, 1u, row)] = s[kPT - 1][1];
+		__syncthreads();
+		u32 below[2], above[2];
+#pragma unroll
+		for (u32 h = 0; h < 2u; h++)
+		{
+			below[h] = wave ? xch[VnStep::slot(buf, wave - 1u, 1u, h, row)] : 0u;       // z == -1 is dead
+			above[h] = xch[VnStep::slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)]; // z == 64 is plane 0
+		}
+#pragma unroll
+		for (u32 h = 0; h < 2u; h++)
+		{
+			Set lo = plane_set(below[h], below[h ^ 1u], h), mid = plane_set(s[0][h], s[0][h ^ 1u], h);
+#pragma unroll
+			for (u32 p = 0; p < kPT; p++)
+			{
+				const Set hi = p + 1u < kPT ? plane_set(s[p + 1u][h], s[p + 1u][h ^ 1u], h) : plane_set(above[h], above[h ^ 1u], h);
+				o[p][h] = rule(lo, mid, hi);
+				lo = mid;
+				mid = hi;
+			}
 		}
 	}
 };
@@ -622,10 +744,14 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64_cycle(EnsembleAr
 __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_cycle(EnsembleArgs a) { ensemble_run<MooreStep, true, false>(a); }
 __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64_trace(EnsembleArgs a) { ensemble_run<VnStep, false, true>(a); }
 __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_trace(EnsembleArgs a) { ensemble_run<MooreStep, false, true>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_clustered64(EnsembleArgs a) { ensemble_run<ClusteredStep, false, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_clustered64_cycle(EnsembleArgs a) { ensemble_run<ClusteredStep, true, false>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_clustered64_trace(EnsembleArgs a) { ensemble_run<ClusteredStep, false, true>(a); }
 
-// the one place that maps an ensemble's neighbourhood (and whether CA3D_STOP_PERIODIC is watched, or samples are recorded) to its kernel
-auto kernel_of(int neighbourhood, bool cycle, bool trace) -> void (*)(EnsembleArgs)
+// the one place that maps an ensemble's kind (and whether CA3D_STOP_PERIODIC is watched, or samples are recorded) to its kernel
+auto kernel_of(int neighbourhood, bool clustered, bool cycle, bool trace) -> void (*)(EnsembleArgs)
 {
+	if (clustered) return trace ? ca_ensemble_clustered64_trace : cycle ? ca_ensemble_clustered64_cycle : ca_ensemble_clustered64;
 	if (trace) return neighbourhood == CA3D_ENSEMBLE_MOORE ? ca_ensemble_moore64_trace : ca_ensemble_vn64_trace; // (never with cycle: launch_ensemble)
 	if (neighbourhood == CA3D_ENSEMBLE_MOORE) return cycle ? ca_ensemble_moore64_cycle : ca_ensemble_moore64;
 	return cycle ? ca_ensemble_vn64_cycle : ca_ensemble_vn64;
@@ -637,7 +763,7 @@ hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 {
 	const bool cycle = (l.stop_mask & (uint32_t)CA3D_STOP_PERIODIC) != 0u, trace = l.samples != nullptr;
 	const bool checks = l.stop_mask || trace; // the launch has check points
-	if (l.count == 0 || l.steps > kEnsembleMaxSteps || (checks && l.check_every == 0)) return hipErrorInvalidValue;
+	if (l.count == 0 || (l.clustered && l.neighbourhood != CA3D_ENSEMBLE_MOORE) || l.steps > kEnsembleMaxSteps || (checks && l.check_every == 0)) return hipErrorInvalidValue;
 	if (cycle && (!l.anchor || !l.cycle || trace)) return hipErrorInvalidValue;
 	// the last sample a universe can write is number ceil((base + steps) / check_every): inside its sample_stride slots, or no launch
 	if (trace && ((uint64_t)l.base + l.steps + l.check_every - 1u) / l.check_every >= l.sample_stride) return hipErrorInvalidValue;
@@ -658,14 +784,14 @@ hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 	a.next_check = l.stop_mask ? l.base / l.check_every + (into ? 1u : 0u) : 0u; // launches are cut ON check points: one that ends a launch and opens the next counts once
 	a.samples = l.samples;
 	a.sample_stride = l.sample_stride;
-	hipLaunchKernelGGL(kernel_of(l.neighbourhood, cycle, trace), dim3(l.count), dim3(kThreads), 0, stream, a);
+	hipLaunchKernelGGL(kernel_of(l.neighbourhood, l.clustered, cycle, trace), dim3(l.count), dim3(kThreads), 0, stream, a);
 	return hipGetLastError();
 }
 
-int ensemble_workgroups_per_cu(int neighbourhood)
+int ensemble_workgroups_per_cu(int neighbourhood, bool clustered)
 {
 	int per_cu = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel_of(neighbourhood, false, false), (int)kThreads, 0) != hipSuccess)
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel_of(neighbourhood, clustered, false, false), (int)kThreads, 0) != hipSuccess)
 	{
 		(void)hipGetLastError();
 		return 0;

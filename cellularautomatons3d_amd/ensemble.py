@@ -1,6 +1,6 @@
 """`Ensemble`: many independent 64^3 universes stepped side by side by one kernel launch (`ca3d_ensemble_*`, include/ca3d.h).
 
-Every universe has its own rule (a table pair of the ensemble's neighbourhood, von Neumann or Moore), its own step counter, its own summary record and — in `step_until` — its own moment
+Every universe has its own rule (a table pair of the ensemble's neighbourhood, von Neumann or Moore, or — clustered — three pairs: main, edges, corners), its own step counter, its own summary record and — in `step_until` — its own moment
 to stop. No reference counterpart: its UI runs one grid.
 """
 from __future__ import annotations
@@ -49,11 +49,17 @@ class Ensemble:
     def __exit__(self, *exc):
         self.close()
 
-    def configure(self, n: int, grid_size: int = 64, neighbourhood: str = "von neumann") -> None:
-        """`neighbourhood`: "von neumann" or "moore" — of every universe; the rules set afterwards must be of that kind."""
+    def configure(self, n: int, grid_size: int = 64, neighbourhood: str = "von neumann", clustered: bool = False) -> None:
+        """`neighbourhood`: "von neumann" or "moore" — of every universe; the rules set afterwards must be of that kind.
+        `clustered` (Moore only): every universe carries edges and corners table pairs beside its main one, the reference's clustered rule."""
         if neighbourhood not in NEIGHBOURHOODS:
             raise ValueError(f"unknown ensemble neighbourhood {neighbourhood!r}: one of {NEIGHBOURHOODS}")
-        _capi.check(self._lib.ca3d_ensemble_configure_neighbourhood(self._h, grid_size, n, NEIGHBOURHOODS.index(neighbourhood)))
+        if clustered and neighbourhood != "moore":
+            raise ValueError(f"a clustered ensemble's main list is Moore (got neighbourhood {neighbourhood!r})")
+        if clustered:
+            _capi.check(self._lib.ca3d_ensemble_configure_clustered(self._h, grid_size, n))
+        else:
+            _capi.check(self._lib.ca3d_ensemble_configure_neighbourhood(self._h, grid_size, n, NEIGHBOURHOODS.index(neighbourhood)))
         self.n, self.grid_size = n, grid_size
 
     @property
@@ -62,6 +68,13 @@ class Ensemble:
         nb = C.c_int()
         _capi.check(self._lib.ca3d_ensemble_get_neighbourhood(self._h, C.byref(nb)))
         return NEIGHBOURHOODS[nb.value]
+
+    @property
+    def clustered(self) -> bool:
+        """Whether the ensemble was configured clustered (`Ca3dError` -2 before `configure`)."""
+        out = C.c_int()
+        _capi.check(self._lib.ca3d_ensemble_get_clustered(self._h, C.byref(out)))
+        return bool(out.value)
 
     def set_rules(self, u: int, main_offsets, edges_offsets, corners_offsets, survive, born) -> None:
         """The payload of `Engine.set_rules` for universe `u` (`ensemble.ALL`: every universe)."""
@@ -117,6 +130,20 @@ class Ensemble:
                 raise ValueError("count does not match the per-universe arrays")
             b, s, count = np.ascontiguousarray(np.broadcast_to(b, n)), np.ascontiguousarray(np.broadcast_to(s, n)), n
         _capi.check(self._lib.ca3d_ensemble_set_rule_tables(self._h, first, count, b.ctypes.data_as(_u32p), s.ctypes.data_as(_u32p), b.size))
+
+    def set_clustered_tables(self, first: int, born_masks, survive_masks, count: Optional[int] = None) -> None:
+        """`ca3d_ensemble_set_rule_tables_clustered`: a rule is three masks — main (bits 0..26), edges (0..12), corners (0..8). `[n, 3]`
+        arrays: one rule per universe from `first`; two length-3 rows: that rule for `count` universes (default: all from `first`)."""
+        b, s = np.ascontiguousarray(_as_u32(born_masks)), np.ascontiguousarray(_as_u32(survive_masks))
+        if b.shape != s.shape or b.ndim not in (1, 2) or b.shape[-1] != 3:
+            raise ValueError("born_masks / survive_masks: two [n, 3] arrays or two length-3 rows (main, edges, corners)")
+        if b.ndim == 1:
+            count, n_rules = (self.n - first if count is None else count), 1
+        else:
+            if count is not None and count != b.shape[0]:
+                raise ValueError("count does not match the per-universe arrays")
+            count = n_rules = b.shape[0]
+        _capi.check(self._lib.ca3d_ensemble_set_rule_tables_clustered(self._h, first, count, b.ctypes.data_as(_u32p), s.ctypes.data_as(_u32p), n_rules))
 
     def read_state(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         count = self.n - first if count is None else count

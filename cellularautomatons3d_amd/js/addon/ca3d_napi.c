@@ -1054,6 +1054,59 @@ static napi_value js_ensemble_neighbourhood(napi_env env, napi_callback_info inf
 	return v;
 }
 
+/* ensembleConfigureClustered(handle, gridSize, n): Moore main list, three table pairs a universe (ca3d_ensemble_configure_clustered) */
+static napi_value js_ensemble_configure_clustered(napi_env env, napi_callback_info info)
+{
+	napi_value argv[3];
+	if (!get_args(env, info, 3, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t grid, n;
+	if (!e || !get_u32(env, argv[1], &grid) || !get_u32(env, argv[2], &n)) return NULL;
+	int rc = ca3d_ensemble_configure_clustered(e, grid, n);
+	if (rc) return throw_ca3d(env, rc);
+	void *p = NULL;
+	napi_get_value_external(env, argv[0], &p);
+	((EnsembleSlot *)p)->n = n;
+	return undefined(env);
+}
+
+/* ensembleClustered(handle) -> 0 | 1 */
+static napi_value js_ensemble_clustered(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	if (!e) return NULL;
+	int c = 0;
+	int rc = ca3d_ensemble_get_clustered(e, &c);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_int32(env, c, &v);
+	return v;
+}
+
+/* ensembleSetClusteredTables(handle, first, count, Uint32Array born masks, Uint32Array survive masks) — 3 words (main, edges, corners) a
+ * rule, 1 or count rules each */
+static napi_value js_ensemble_set_clustered_tables(napi_env env, napi_callback_info info)
+{
+	napi_value argv[5];
+	if (!get_args(env, info, 5, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, count;
+	void *b, *s;
+	size_t nb, ns;
+	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count) || !get_typed(env, argv[3], napi_uint32_array, 0, &b, &nb) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 0, &s, &ns))
+		return NULL;
+	if (nb != ns || nb == 0 || nb % 3u)
+	{
+		napi_throw_range_error(env, NULL, "born and survive masks must hold the same number of rules, three words (main, edges, corners) each");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_set_rule_tables_clustered(e, first, count, (const uint32_t *)b, (const uint32_t *)s, (uint32_t)(nb / 3u));
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
 /* ensembleSetRules(handle, universe | 0xFFFFFFFF, main, edges, corners, survive, born) */
 static napi_value js_ensemble_set_rules(napi_env env, napi_callback_info info)
 {
@@ -1376,7 +1429,9 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleSynchronize", js_ensemble_synchronize}, {"ensembleStats", js_ensemble_stats},
 	    {"seedState", js_seed_state}, {"groupSeedState", js_group_seed_state}, {"ensembleSeedState", js_ensemble_seed_state},
 	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables},
-	    {"ensembleConfigureNeighbourhood", js_ensemble_configure_neighbourhood}, {"ensembleNeighbourhood", js_ensemble_neighbourhood}};
+	    {"ensembleConfigureNeighbourhood", js_ensemble_configure_neighbourhood}, {"ensembleNeighbourhood", js_ensemble_neighbourhood},
+	    {"ensembleConfigureClustered", js_ensemble_configure_clustered}, {"ensembleClustered", js_ensemble_clustered},
+	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

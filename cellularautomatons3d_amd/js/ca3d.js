@@ -416,7 +416,7 @@ class EngineGroup
 }
 
 // ca3d_ensemble_*: `n` independent 64^3 universes (8192 packed words each) stepped side by side by one kernel launch, each with its
-// own rule (a table pair of the ensemble's neighbourhood, von Neumann or Moore), step counter, summary record and — in stepUntil — its
+// own rule (a table pair of the ensemble's neighbourhood, von Neumann or Moore — or, clustered, three pairs), step counter, summary record and — in stepUntil — its
 // own moment to stop (include/ca3d.h). Synchronous.
 const ENSEMBLE_ALL = 0xFFFFFFFF, ENSEMBLE_WORDS = 8192;
 const ENSEMBLE_NEIGHBOURHOODS = ["von neumann", "moore"]; // index = enum ca3d_ensemble_neighbourhood
@@ -429,16 +429,21 @@ class Ensemble
 		this.n = 0;
 	}
 	close() { if (this._e) { this._a.ensembleDestroy(this._e); this._e = null; } }
-	/** neighbourhood: "von neumann" (default) or "moore" — of every universe; the rules set afterwards must be of that kind */
-	configure(n, gridSize, neighbourhood)
+	/** neighbourhood: "von neumann" (default) or "moore" — of every universe; the rules set afterwards must be of that kind.
+	 *  clustered (Moore only): every universe carries edges and corners table pairs beside its main one */
+	configure(n, gridSize, neighbourhood, clustered = false)
 	{
 		const nb = ENSEMBLE_NEIGHBOURHOODS.indexOf(neighbourhood === undefined ? "von neumann" : neighbourhood);
 		if (nb < 0) throw new Error(`unknown ensemble neighbourhood ${JSON.stringify(neighbourhood)}: "von neumann" or "moore"`);
-		this._a.ensembleConfigureNeighbourhood(this._e, gridSize === undefined ? 64 : gridSize, n, nb);
+		if (clustered && ENSEMBLE_NEIGHBOURHOODS[nb] !== "moore") throw new Error(`a clustered ensemble's main list is Moore (got neighbourhood ${JSON.stringify(neighbourhood)})`);
+		if (clustered) this._a.ensembleConfigureClustered(this._e, gridSize === undefined ? 64 : gridSize, n);
+		else this._a.ensembleConfigureNeighbourhood(this._e, gridSize === undefined ? 64 : gridSize, n, nb);
 		this.n = n;
 	}
 	/** the configured neighbourhood as its string (throws before configure) */
 	get neighbourhood() { return ENSEMBLE_NEIGHBOURHOODS[this._a.ensembleNeighbourhood(this._e)]; }
+	/** whether the ensemble was configured clustered (throws before configure) */
+	get clustered() { return this._a.ensembleClustered(this._e) !== 0; }
 	/** universe: an index, or ENSEMBLE_ALL */
 	setRules(universe, mainOffsets, edgesOffsets, cornersOffsets, survive, born) { this._a.ensembleSetRules(this._e, universe, mainOffsets, edgesOffsets, cornersOffsets, survive, born); }
 	setRuleStrings(universe, rules)
@@ -466,6 +471,15 @@ class Ensemble
 		const scalar = typeof bornMasks === "number";
 		const b = Uint32Array.from(scalar ? [bornMasks] : bornMasks), s = Uint32Array.from(scalar ? [surviveMasks] : surviveMasks);
 		this._a.ensembleSetRuleTables(this._e, first, scalar ? (count === undefined ? this.n - first : count) : b.length, b, s);
+	}
+	/** ca3d_ensemble_set_rule_tables_clustered: a rule is three masks [main (bits 0..26), edges (0..12), corners (0..8)]; arrays of such
+	 *  triples: one rule per universe from `first`; two plain triples: that rule for `count` universes (default: all from `first`) */
+	setClusteredTables(first, bornMasks, surviveMasks, count)
+	{
+		const one = typeof bornMasks[0] === "number";
+		const flat = (m) => Uint32Array.from(one ? m : [].concat(...m.map((r) => Array.from(r))));
+		const b = flat(bornMasks), s = flat(surviveMasks);
+		this._a.ensembleSetClusteredTables(this._e, first, one ? (count === undefined ? this.n - first : count) : b.length / 3, b, s);
 	}
 	readState(first, count)
 	{

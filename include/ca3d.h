@@ -389,6 +389,28 @@ enum ca3d_ensemble_neighbourhood
 };
 int ca3d_ensemble_configure_neighbourhood(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes, int neighbourhood);
 int ca3d_ensemble_get_neighbourhood(ca3d_ensemble_t *e, int *out);
+/* A CLUSTERED ensemble: every universe is 64^3, its main list is Moore, and it carries the reference's three rule-sets as data — a born /
+ * survive table pair each for the 26 Moore neighbours (counts 0 .. 26, the cell itself not counted), the 12 edge neighbours (0 .. 12)
+ * and the 8 corner neighbours (0 .. 8). A cell is alive afterwards if ANY of the three lookups says so:
+ *   next = (alive ? sM[T] : bM[T]) | (alive ? sE[E] : bE[E]) | (alive ? sC[C] : bC[C])
+ * (kernels ca_ensemble_clustered64 / _cycle / _trace). "Clustered" is a property beside the neighbourhood, not a third neighbourhood:
+ * ca3d_ensemble_get_neighbourhood answers CA3D_ENSEMBLE_MOORE for such an ensemble and ca3d_ensemble_get_clustered 1 (0 for every other
+ * configure; CA3D_ERR_NOT_CONFIGURED before any). The checks are ca3d_ensemble_configure_neighbourhood's.
+ *   ca3d_ensemble_set_rules  accepts every payload that canonicalises to main list Moore with the standard edges and corners lists, silent
+ *                            side tables included (a plain Moore rule is a clustered rule); the rest — von Neumann or 2D main lists,
+ *                            generic lists — is CA3D_ERR_UNSUPPORTED naming the universe. Table bits no count can reach are dropped.
+ *   ca3d_ensemble_set_rule_tables  sets the main pair and silences both side pairs.
+ *   ca3d_ensemble_set_rule_tables_clustered  three words a rule — main, edges, corners — in born_masks and in survive_masks; n_rules == 1
+ *                            (that rule for all `count` universes) or == count. A bit at position 27 / 13 / 9 or above in the respective
+ *                            word: CA3D_ERR_INVALID_ARGUMENT naming the universe. Stores what ca3d_ensemble_set_rules stores for the same
+ *                            rule and waits for the stream as ca3d_ensemble_set_rule_tables does. In an ensemble that is not clustered:
+ *                            CA3D_ERR_UNSUPPORTED.
+ * Everything else — upload, seed, read, step, step_until, step_until_cycle, step_until_trace, summarize, get_stats — means what it means
+ * in any other ensemble. */
+int ca3d_ensemble_configure_clustered(ca3d_ensemble_t *e, uint32_t grid_size, uint32_t n_universes);
+int ca3d_ensemble_get_clustered(ca3d_ensemble_t *e, int *out);
+int ca3d_ensemble_set_rule_tables_clustered(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *born_masks,
+                                            const uint32_t *survive_masks, uint32_t n_rules);
 int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe,
                             const int32_t *main_offsets, uint32_t n_main,
                             const int32_t *edges_offsets, uint32_t n_edges,

@@ -13,6 +13,11 @@ through one engine would pay on top.
 for a Moore rule at 64^3 is one launch per step of the kernel compiled for the rule; same protocol, written to
 profiles/ensemble_moore_64.json unless --out says otherwise.
 
+--neighbourhood clustered measures a clustered ensemble (ca_ensemble_clustered64, three table pairs a universe, bench.py's `clustered` rule:
+Moore B5-7 / S4-7, edges B4 / S3-5, corners B3 / S2-4) against the same universes one after another through one Engine, which steps that
+rule at 64^3 with the class kernel compiled for it; same protocol, written to profiles/ensemble_clustered_64.json unless --out says
+otherwise.
+
 --cycle measures what watching CA3D_STOP_PERIODIC costs, for both neighbourhoods: Ensemble.step_until_cycle (stop mask 7, the *_cycle
 kernels) against Ensemble.step_until (stop mask 3, the kernels above) on the same universes — B = 256 and 1024, 256 steps, check_every 1
 and 8, density-1/2 fills on which nothing stops within the call, so every check is paid. Before timing, both calls must have left the same
@@ -51,6 +56,8 @@ from cellularautomatons3d_amd import Engine, Ensemble, _capi, host  # noqa: E402
 G, W, CELLS = 64, 8192, 64 ** 3
 RULES = {"von neumann": ("2,4", "1,3,5"), "moore": ("5-7", "4-6")}  # born, survive
 KERNELS = {"von neumann": "ca_ensemble_vn64", "moore": "ca_ensemble_moore64"}
+# bench.py's `clustered` rule: the keyword arguments of set_rule_strings
+CLUSTERED = dict(neighbourhood="moore", born="5-7", survive="4-7", born_edges="4", survive_edges="3-5", born_corners="3", survive_corners="2-4")
 
 
 def fills(B):
@@ -212,7 +219,8 @@ def main():
     ap.add_argument("--steps", type=int, default=256, help="steps per launch")
     ap.add_argument("--repeats", type=int, default=5, help="alternating measurements per path; the median is reported")
     ap.add_argument("--min-seconds", type=float, default=0.25, help="work per measurement")
-    ap.add_argument("--neighbourhood", choices=sorted(RULES), default="von neumann", help="of the ensemble and of the rule both paths run")
+    ap.add_argument("--neighbourhood", choices=sorted(RULES) + ["clustered"], default="von neumann",
+                    help="of the ensemble and of the rule both paths run; clustered: a clustered ensemble and bench.py's clustered rule")
     ap.add_argument("--out", default=None, help="JSON file to write (moore: profiles/ensemble_moore_64.json)")
     ap.add_argument("--cycle", action="store_true", help="measure step_until_cycle against step_until instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--trace", action="store_true", help="measure step_trace against the step + summaries loop and plain stepping instead (both neighbourhoods; default B = 256 1024)")
@@ -221,9 +229,14 @@ def main():
     if args.universes is None:
         args.universes = [256, 1024] if args.cycle or args.trace else [1, 256, 1024, 4096]
     nb = args.neighbourhood
-    born, survive = RULES[nb]
-    if args.out is None and nb == "moore":
-        args.out = os.path.join(ROOT, "profiles", "ensemble_moore_64.json")
+    clustered = nb == "clustered"
+    if clustered:
+        nb, rule = "moore", CLUSTERED
+    else:
+        rule = dict(neighbourhood=nb, born=RULES[nb][0], survive=RULES[nb][1])
+    born, survive = rule["born"], rule["survive"]
+    if args.out is None and (clustered or nb == "moore"):
+        args.out = os.path.join(ROOT, "profiles", "ensemble_clustered_64.json" if clustered else "ensemble_moore_64.json")
     commit = args.commit
     if commit is None:
         try:
@@ -269,13 +282,13 @@ def main():
 
     eng, ens = Engine(0), Ensemble(0)
     eng.configure(G)
-    eng.set_rule_strings(neighbourhood=nb, born=born, survive=survive)
+    eng.set_rule_strings(**rule)
     eng.set_option("stats", 0)  # no event pair per call: the baseline at its best
     rows = []
     for B in args.universes:
         words = fills(B)
-        ens.configure(B, neighbourhood=nb)
-        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood=nb, born=born, survive=survive)
+        ens.configure(B, neighbourhood=nb, clustered=clustered)
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, **rule)
         sample = range(B) if B <= 256 else sorted(set(range(0, B, max(1, B // 64))) | {255, 256, B - 1})
         verify(ens, eng, words, args.steps, sample)
         eng.upload_state(words[0])
@@ -310,9 +323,10 @@ def main():
     kernel = eng.info().kernel_name.decode()
     eng.close(); ens.close()
     result = {
-        "what": f"B universes of 64^3, {'Moore ' if nb == 'moore' else ''}rule B{born}/S{survive}, random fills (density 1/2): one Ensemble.step(steps) launch vs. B Engine.step(steps) calls",
+        "what": f"B universes of 64^3, {'clustered rule Moore ' if clustered else 'Moore ' if nb == 'moore' else ''}rule B{born}/S{survive}"
+                f"{', edges B%s/S%s, corners B%s/S%s' % tuple(rule[k] for k in ('born_edges', 'survive_edges', 'born_corners', 'survive_corners')) if clustered else ''}, random fills (density 1/2): one Ensemble.step(steps) launch vs. B Engine.step(steps) calls",
         "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
-        "ensemble_kernel": f"{KERNELS[nb]} (rule as data)", "baseline_kernel": kernel,
+        "ensemble_kernel": f"{'ca_ensemble_clustered64' if clustered else KERNELS[nb]} (rule as data)", "baseline_kernel": kernel,
         "timing": f"host clock around >= {args.min_seconds} s of calls ending in a synchronise; median of {args.repeats} alternating measurements",
         "rows": rows,
     }
