@@ -62,6 +62,7 @@ class SeedStruct(C.Structure):
 
 STOP_EXTINCT, STOP_STILL = 1, 2
 STOP_PERIODIC = 4  # ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle only
+STOP_MOVING = 8  # ca3d_ensemble_step_until_moving only
 ENSEMBLE_ALL = 0xFFFFFFFF
 ENSEMBLE_WORDS = 8192  # words of one 64^3 universe
 
@@ -150,6 +151,7 @@ SYMBOLS = [
     ("ca3d_ensemble_step", C.c_int, [_H, C.c_uint32]),
     ("ca3d_ensemble_step_until", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
     ("ca3d_ensemble_step_until_cycle", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p]),
+    ("ca3d_ensemble_step_until_moving", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _i32p]),
     ("ca3d_ensemble_step_until_trace", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, _u32p]),
     ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),

@@ -2,7 +2,7 @@
 // ca_ensemble_moore64 or ca_ensemble_clustered64 (ca_ensemble.hip; the ensemble's neighbourhood and `clustered` decide) steps one
 // universe with its state in registers; a launch
 // over B workgroups is B universes, each with its own rule table pair, its own step counter, its own summary record and — in
-// ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle / ca3d_ensemble_step_until_trace — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
+// ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle / ca3d_ensemble_step_until_moving / ca3d_ensemble_step_until_trace — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
 #include <cstring>
 #include <new>
@@ -26,6 +26,9 @@ struct ca3d_ensemble
 	// ca3d_ensemble_step_until_cycle: every universe's anchor state (n x 32 KiB) and its anchor step / anchor hash / period / unused
 	// (n x 4 words), allocated at the first call that watches CA3D_STOP_PERIODIC, gone with the other arrays at a configure
 	uint32_t *anchor = nullptr, *cycle = nullptr;
+	// ca3d_ensemble_step_until_moving: the same record with the found shift and the anchor's population and box behind it (n x 8 words:
+	// what the *_moving kernels take for `cycle`), allocated at the first call that watches CA3D_STOP_MOVING; the anchors are shared
+	uint32_t *moving = nullptr;
 	// ca3d_ensemble_step_until_trace: the samples of the call under way, [n][K][3] words; grown when a call needs more than
 	// trace_words, gone with the other arrays at a configure
 	uint32_t *trace = nullptr;
@@ -47,9 +50,9 @@ namespace
 
 void free_arrays(ca3d_ensemble *e)
 {
-	for (void *p : {(void *)e->state, (void *)e->prev, (void *)e->rules, (void *)e->steps_done, (void *)e->reason, (void *)e->records, (void *)e->anchor, (void *)e->cycle, (void *)e->trace})
+	for (void *p : {(void *)e->state, (void *)e->prev, (void *)e->rules, (void *)e->steps_done, (void *)e->reason, (void *)e->records, (void *)e->anchor, (void *)e->cycle, (void *)e->moving, (void *)e->trace})
 		if (p) hipFree(p);
-	e->state = e->prev = e->rules = e->steps_done = e->reason = e->anchor = e->cycle = e->trace = nullptr;
+	e->state = e->prev = e->rules = e->steps_done = e->reason = e->anchor = e->cycle = e->moving = e->trace = nullptr;
 	e->trace_words = 0;
 	e->records = nullptr;
 	if (e->seed_dev) hipFree(e->seed_dev);
@@ -181,6 +184,7 @@ int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_ma
 		l.base = base;
 		l.check_every = check_every;
 		l.stop_mask = stop_mask;
+		if (stop_mask & CA3D_STOP_MOVING) l.cycle = e->moving; // the *_moving kernels' wider record
 		l.final = base + n == total;
 		if (samples_per_universe) { l.samples = e->trace; l.sample_stride = samples_per_universe; }
 		HIP_TRY(launch_ensemble(l, e->stream));
@@ -195,6 +199,7 @@ int run(ca3d_ensemble *e, uint32_t total, uint32_t check_every, uint32_t stop_ma
 
 // ca3d_ensemble_step_until (known: EXTINCT | STILL, period null) and ca3d_ensemble_step_until_cycle (known: + PERIODIC). Without
 // CA3D_STOP_PERIODIC in the mask the launches are the first call's whatever the entry point: the *_cycle kernels run only when asked for.
+// ca3d_ensemble_step_until_moving (known: + MOVING, shift): the *_moving kernels run only with CA3D_STOP_MOVING in the mask.
 // ca3d_ensemble_step_until_trace passes `trace` (known: EXTINCT | STILL): the *_trace kernels run whatever the mask, 0 included.
 struct TraceOut
 {
@@ -204,7 +209,7 @@ struct TraceOut
 uint64_t trace_capacity(uint32_t max_steps, uint32_t check_every) { return ((uint64_t)max_steps + check_every - 1u) / check_every + 1u; }
 
 int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t known, uint32_t *steps_done, uint32_t *reason,
-               uint32_t *period, const TraceOut *trace = nullptr)
+               uint32_t *period, const TraceOut *trace = nullptr, int32_t *shift = nullptr)
 {
 	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
 	if (check_every == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "check_every must be at least 1");
@@ -218,7 +223,10 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 		            max_steps, check_every, (unsigned long long)K);
 	HIP_TRY(hipSetDevice(e->device));
 	const size_t word_bytes = (size_t)e->n * sizeof(uint32_t);
-	const bool cycle = (stop_mask & CA3D_STOP_PERIODIC) != 0u;
+	const bool moving = (stop_mask & CA3D_STOP_MOVING) != 0u;   // the *_moving kernels: their record is e->moving, eight words a universe
+	const bool cycle = (stop_mask & CA3D_STOP_PERIODIC) != 0u && !moving; // the *_cycle kernels: e->cycle, four words
+	const uint32_t rec_words = moving ? 8u : 4u;
+	uint32_t *&rec = moving ? e->moving : e->cycle;
 	const size_t sample_words = (size_t)e->n * (size_t)K * 3u;
 	if (trace && sample_words > e->trace_words)
 	{
@@ -239,19 +247,20 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 		e->trace = grown;
 		e->trace_words = sample_words;
 	}
-	if (cycle && !e->anchor)
+	if ((cycle || moving) && (!e->anchor || !rec))
 	{
-		hipError_t err = hipMalloc((void **)&e->anchor, (size_t)e->n * kEnsembleWords * sizeof(uint32_t));
-		if (err == hipSuccess && !e->cycle) err = hipMalloc((void **)&e->cycle, 4u * word_bytes);
+		const bool had_anchor = e->anchor != nullptr;
+		hipError_t err = had_anchor ? hipSuccess : hipMalloc((void **)&e->anchor, (size_t)e->n * kEnsembleWords * sizeof(uint32_t));
+		if (err == hipSuccess && !rec) err = hipMalloc((void **)&rec, rec_words * word_bytes);
 		if (err != hipSuccess)
 		{
-			if (e->anchor) hipFree(e->anchor);
-			e->anchor = nullptr;
+			if (!had_anchor && e->anchor) hipFree(e->anchor);
+			if (!had_anchor) e->anchor = nullptr;
 			(void)hipGetLastError();
 			return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating the anchors of %u universes: %s", e->n, hipGetErrorString(err));
 		}
 	}
-	std::vector<uint32_t> done(e->n, stop_mask ? 0u : max_steps), fired(e->n, 0u), cyc(cycle ? 4u * (size_t)e->n : 0u, 0u);
+	std::vector<uint32_t> done(e->n, stop_mask ? 0u : max_steps), fired(e->n, 0u), cyc(cycle || moving ? rec_words * (size_t)e->n : 0u, 0u);
 	std::vector<uint32_t> got(sample_words); // [n][K][3]: staged, so that a failure below leaves the caller's array as it was
 	e->last_launches = 0;
 	e->timed = false;
@@ -263,7 +272,7 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 			HIP_TRY(hipMemsetAsync(e->steps_done, 0, word_bytes, e->stream));
 			HIP_TRY(hipMemsetAsync(e->reason, 0, word_bytes, e->stream));
 		}
-		if (cycle) HIP_TRY(hipMemsetAsync(e->cycle, 0, 4u * word_bytes, e->stream)); // no anchor survives a call
+		if (cycle || moving) HIP_TRY(hipMemsetAsync(rec, 0, rec_words * word_bytes, e->stream)); // no anchor survives a call
 		if (trace) HIP_TRY(hipMemsetAsync(e->trace, 0, sample_words * sizeof(uint32_t), e->stream)); // slots no check point reaches stay zero
 		rc = run(e, max_steps, check_every, stop_mask, trace ? (uint32_t)K : 0u); // max_steps == 0: one launch that only checks
 		if (rc) return rc;
@@ -272,7 +281,7 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 			HIP_TRY(hipMemcpyAsync(done.data(), e->steps_done, word_bytes, hipMemcpyDeviceToHost, e->stream));
 			HIP_TRY(hipMemcpyAsync(fired.data(), e->reason, word_bytes, hipMemcpyDeviceToHost, e->stream));
 		}
-		if (cycle) HIP_TRY(hipMemcpyAsync(cyc.data(), e->cycle, 4u * word_bytes, hipMemcpyDeviceToHost, e->stream));
+		if (cycle || moving) HIP_TRY(hipMemcpyAsync(cyc.data(), rec, rec_words * word_bytes, hipMemcpyDeviceToHost, e->stream));
 		if (trace) HIP_TRY(hipMemcpyAsync(got.data(), e->trace, sample_words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
 	}
 	else if (max_steps)
@@ -288,7 +297,14 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 	if (steps_done) memcpy(steps_done, done.data(), word_bytes);
 	if (reason) memcpy(reason, fired.data(), word_bytes);
 	if (period)
-		for (uint32_t u = 0; u < e->n; u++) period[u] = cycle ? cyc[4u * (size_t)u + 2u] : 0u;
+		for (uint32_t u = 0; u < e->n; u++) period[u] = cycle || moving ? cyc[rec_words * (size_t)u + 2u] : 0u;
+	if (shift)
+		for (uint32_t u = 0; u < e->n; u++)
+		{
+			// word 3 of a universe's record: dx, dy, dz as signed bytes, zero unless CA3D_STOP_MOVING fired
+			const uint32_t packed = moving ? cyc[8u * (size_t)u + 3u] : 0u;
+			for (int i = 0; i < 3; i++) shift[3u * (size_t)u + i] = (int32_t)(int8_t)(uint8_t)(packed >> (8 * i));
+		}
 	if (trace)
 	{
 		const size_t per = (size_t)trace->samples_per_universe * 3u, mine = (size_t)K * 3u;
@@ -598,6 +614,14 @@ int ca3d_ensemble_step_until_cycle(ca3d_ensemble_t *e, uint32_t max_steps, uint3
                                    uint32_t *reason, uint32_t *period) CA3D_API_TRY
 {
 	return step_until(e, max_steps, check_every, stop_mask, CA3D_STOP_EXTINCT | CA3D_STOP_STILL | CA3D_STOP_PERIODIC, steps_done, reason, period);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_step_until_moving(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                                    uint32_t *reason, uint32_t *period, int32_t *shift) CA3D_API_TRY
+{
+	return step_until(e, max_steps, check_every, stop_mask, CA3D_STOP_EXTINCT | CA3D_STOP_STILL | CA3D_STOP_PERIODIC | CA3D_STOP_MOVING, steps_done, reason, period,
+	                  nullptr, shift);
 }
 CA3D_API_CATCH
 

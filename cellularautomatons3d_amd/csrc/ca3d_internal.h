@@ -210,7 +210,9 @@ struct EnsembleLaunch
 	uint32_t *steps_done;     // [B] steps taken in the current step-until call (written when stop_mask != 0)
 	uint32_t *reason;         // [B] stop bits that fired in the current call; a universe whose word is set leaves at once
 	uint32_t *anchor;         // [B][8192] the state at each universe's anchor check point; [B][4] anchor step, anchor hash, period, unused —
-	uint32_t *cycle;          // both only when stop_mask holds CA3D_STOP_PERIODIC (the *_cycle kernels), else unused and may be null
+	uint32_t *cycle;          // both only when stop_mask holds CA3D_STOP_PERIODIC (the *_cycle kernels), else unused and may be null.
+	                          // stop_mask holds CA3D_STOP_MOVING (the *_moving kernels): both as well, `cycle` then [B][8] — anchor step, anchor
+	                          // hash, period, shift (dx, dy, dz as signed bytes), the anchor's population, packed box_min, packed box_max, unused
 	uint32_t *samples;        // [B][sample_stride][3] population, births, deaths per check point of the call (the *_trace kernels); null: no trace.
 	uint32_t sample_stride;   // Every check point is then reached whatever stop_mask holds, CA3D_STOP_PERIODIC is refused
 	uint32_t first, count;

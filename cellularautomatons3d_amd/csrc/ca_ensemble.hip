@@ -23,7 +23,8 @@
 // bits, two words per universe), and ca_ensemble_clustered64, whose rule is three pairs — main (Moore), edges, corners — ORed (six words).
 // The body — entry check from the stored record, check points, record reduction, write-back — is ensemble_run<Step, Cycle, Trace>; a Step
 // policy (VnStep, MooreStep, ClusteredStep) owns the rule's registers, the size of the LDS exchange and one step.
-// The *_cycle kernels watch CA3D_STOP_PERIODIC as well; the *_trace kernels leave a sample (population, births, deaths) per check point.
+// The *_cycle kernels watch CA3D_STOP_PERIODIC as well, the *_moving kernels CA3D_STOP_MOVING on top of that; the *_trace kernels leave a
+// sample (population, births, deaths) per check point.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,7 +52,8 @@ struct EnsembleArgs
 	u32 final, reset;
 	// the *_cycle kernels only (ca3d_ensemble_step_until_cycle); appended, so that the kernels above read what they always read
 	u32 *anchor;    // [B][8192]: the state at the universe's anchor check point
-	u32 *cycle;     // [B][4]: anchor step, anchor hash, period, unused — next to steps_done / reason
+	u32 *cycle;     // [B][4]: anchor step, anchor hash, period, unused — next to steps_done / reason. The *_moving kernels: [B][8], + packed
+	                // shift, + the anchor's population, packed box_min, packed box_max (kMeta* below)
 	u32 next_check; // number j of the call's next regular check point (the one first_check steps into this launch)
 	// the *_trace kernels only (ca3d_ensemble_step_until_trace); appended likewise
 	u32 *samples;      // [B][sample_stride][3]: population, births, deaths at check point j of the call
@@ -99,6 +101,38 @@ __device__ __forceinline__ u32 wave_sum_uniform(u32 v)
 	return (u32)__builtin_amdgcn_readlane((int)v, 0) + (u32)__builtin_amdgcn_readlane((int)v, 16) + (u32)__builtin_amdgcn_readlane((int)v, 32) +
 	       (u32)__builtin_amdgcn_readlane((int)v, 48);
 }
+
+// The same for an OR (the *_moving kernels' x-occupancy words).
+__device__ __forceinline__ u32 row16_or(u32 v)
+{
+	v |= dpp_mov<1 | (0 << 2) | (3 << 4) | (2 << 6)>(v); // quad_perm:[1,0,3,2]
+	v |= dpp_mov<2 | (3 << 2) | (0 << 4) | (1 << 6)>(v); // quad_perm:[2,3,0,1]
+	v |= dpp_mov<0x141>(v);                              // row_half_mirror
+	v |= dpp_mov<0x140>(v);                              // row_mirror
+	return v;
+}
+__device__ __forceinline__ u32 wave_or_uniform(u32 v)
+{
+	v = row16_or(v);
+	return (u32)__builtin_amdgcn_readlane((int)v, 0) | (u32)__builtin_amdgcn_readlane((int)v, 16) | (u32)__builtin_amdgcn_readlane((int)v, 32) |
+	       (u32)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// The *_moving kernels (CA3D_STOP_MOVING): a bounding box travels as two words, x | y << 8 | z << 16 of box_min and of box_max. Inside
+// means clear of every face: a pattern on a - face sees the dead boundary, one on a + face wraps.
+__device__ __forceinline__ bool box_inside(u32 mn, u32 mx)
+{
+	bool ok = true;
+#pragma unroll
+	for (u32 i = 0; i < 3u; i++) ok = ok && ((mn >> (8u * i)) & 0xFFu) >= 1u && ((mx >> (8u * i)) & 0xFFu) <= 62u;
+	return ok;
+}
+// the *_moving kernels' chk, in words: the four per-wave words of the *_cycle kernels (flags, hash, "differs from the anchor", "differs
+// from the shifted anchor"), the per-wave partials of a check point (8 words a wave: population, x-occupancy words 0 and 1, y ballot low
+// and high, z bits low and high — the wave's four planes in place —, unused), the anchor's record (8 words, one copy per wave)
+constexpr u32 kMovDiff = 3u * kWaves, kMovPart = 4u * kWaves, kMovCyc = 12u * kWaves, kMovWords = 20u * kWaves;
+// the anchor's record, in chk and in EnsembleArgs::cycle
+constexpr u32 kMetaStep = 0, kMetaHash = 1, kMetaPeriod = 2, kMetaShift = 3, kMetaPop = 4, kMetaMin = 5, kMetaMax = 6;
 
 // ---- von Neumann: the table pair in one word, lut_s | lut_b << 8 (7 bits each)
 struct VnStep
@@ -411,7 +445,14 @@ struct ClusteredStep
 // are reduced over the wave, ride the chk exchange and its barrier as the hash does, and thread 0 sums the 16 partials and stores the
 // three words. Births and deaths travel as ONE word, births | deaths << 16: a wave's 512 words hold 16 384 of each at most. The number j
 // is worked out at the check point from base, t and check_every (read from the kernel's arguments there and then).
-template <typename Step, bool Cycle, bool Trace>
+// Moving (with Cycle): CA3D_STOP_MOVING is watched as well (include/ca3d.h, ca3d_ensemble_step_until_moving). look() also reduces the
+// population and the bounding box of the state — per-wave partials in chk behind the check's own barrier, joined by every wave for
+// itself, wave-uniform — and the anchor's population and box are kept beside its step and hash. Equal populations, equal box extents,
+// both boxes clear of the faces and a displacement d != 0 of box_min start the comparison with the anchor SHIFTED by d: a thread loads
+// the anchor's row (y - dy, z - dz) for each of its four planes (a row outside the universe is zero and is not loaded), shifts the 64
+// bits by dx and compares with its own two words. As both boxes are clear of the faces no live bit is shifted out: the comparison is
+// exact, and only it declares MOVING.
+template <typename Step, bool Cycle, bool Trace, bool Moving = false>
 __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 {
 	__shared__ __attribute__((aligned(16))) u32 xch[Step::kXchWords];
@@ -420,8 +461,9 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 	// Cycle, behind those (one array, so that nothing moves in the kernels without it): the anchor's step and hash and the period found,
 	// one copy PER WAVE (written by its lane 0, read by the wave itself: LDS order within a wave, no barrier) — in LDS, because the
 	// Moore step has no scalar registers to spare across the steps either
-	__shared__ __attribute__((aligned(16))) u32 chk[Cycle ? 7u * kWaves : Trace ? 3u * kWaves : kWaves];
-	u32(*cyc)[4] = reinterpret_cast<u32(*)[4]>(chk + (Cycle ? 3u * kWaves : 0u));
+	// Moving: laid out as kMovDiff .. kMovWords say
+	__shared__ __attribute__((aligned(16))) u32 chk[Moving ? kMovWords : Cycle ? 7u * kWaves : Trace ? 3u * kWaves : kWaves];
+	u32(*cyc)[Moving ? 8 : 4] = reinterpret_cast<u32(*)[Moving ? 8 : 4]>(chk + (Moving ? kMovCyc : Cycle ? 3u * kWaves : 0u));
 	__shared__ u64 red64[kWaves][2];
 	__shared__ u32 red32[kWaves][6];
 	const u32 u = a.first + blockIdx.x;
@@ -463,9 +505,15 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 		if (row == 0u)
 		{
 			// the anchor the launch before left (the call's first launch sets it on entry)
-			cyc[wave][0] = a.base ? a.cycle[4u * u] : 0u;
-			cyc[wave][1] = a.base ? a.cycle[4u * u + 1u] : 0u;
+			cyc[wave][0] = a.base ? a.cycle[(Moving ? 8u : 4u) * u] : 0u;
+			cyc[wave][1] = a.base ? a.cycle[(Moving ? 8u : 4u) * u + 1u] : 0u;
 			cyc[wave][2] = 0u;
+			if (Moving)
+			{
+				cyc[wave][kMetaShift] = 0u;
+#pragma unroll
+				for (u32 i = kMetaPop; i <= kMetaMax; i++) cyc[wave][i] = a.base ? a.cycle[8u * u + i] : 0u;
+			}
 		}
 	}
 	// One round of the loop: the check that is due on the state in `s` (previous state in `o`), then one step from `s` into `o`.
@@ -475,6 +523,7 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 		{
 			bool alive, changed, has_prev;
 			u32 hash = 0; // Cycle: of the state in `s`
+			u32 cpop = 0, cmin = 0, cmax = 0; // Moving: its population and packed box (box_inside)
 			// the workgroup's two bits (and hash) of the state in `s` against `o`
 			auto look = [&]() __attribute__((always_inline)) -> u32 {
 				u32 al = 0, ch = 0, hs = 0;
@@ -511,7 +560,52 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 					bd = wave_sum_uniform(bd);
 					if (row == 0u) { chk[kWaves + wave] = pop; chk[2u * kWaves + wave] = bd; }
 				}
+				if (Moving)
+				{
+					u32 pop = 0, x0 = 0, x1 = 0, zb = 0;
+#pragma unroll
+					for (u32 p = 0; p < kPT; p++)
+					{
+						pop += (u32)__popc(s[p][0]) + (u32)__popc(s[p][1]);
+						x0 |= s[p][0];
+						x1 |= s[p][1];
+						if (__ballot((s[p][0] | s[p][1]) != 0u)) zb |= 1u << p;
+					}
+					const u64 ym = __ballot((x0 | x1) != 0u); // bit y: row y of one of the wave's planes holds a live cell
+					pop = wave_sum_uniform(pop);
+					x0 = wave_or_uniform(x0);
+					x1 = wave_or_uniform(x1);
+					if (row == 0u)
+					{
+						u32 w = wave;
+						asm volatile("" : "+s"(w)); // (worked out here, not held across the steps: see own())
+						const u64 zm = (u64)zb << (w * kPT);
+						uint4 *part = reinterpret_cast<uint4 *>(chk + kMovPart) + 2u * w;
+						part[0] = make_uint4(pop, x0, x1, (u32)ym);
+						part[1] = make_uint4((u32)(ym >> 32), (u32)zm, (u32)(zm >> 32), 0u);
+					}
+				}
 				__syncthreads();
+				if (Moving)
+				{
+					// every wave joins the 16 partials for itself: lanes 0 .. 15 of every row of 16 take one wave's each, four DPP steps
+					// leave the row's lanes with the whole, lane 0 is read
+					u32 r = row;
+					asm volatile("" : "+v"(r));
+					const uint4 *part = reinterpret_cast<const uint4 *>(chk + kMovPart) + 2u * (r & 15u);
+					const uint4 pa = part[0], pb = part[1];
+					auto first = [](u32 v) { return (u32)__builtin_amdgcn_readlane((int)v, 0); };
+					cpop = first(row16_sum(pa.x));
+					const u32 x0 = first(row16_or(pa.y)), x1 = first(row16_or(pa.z));
+					const u64 ym = (u64)first(row16_or(pb.x)) << 32 | first(row16_or(pa.w));
+					const u64 zm = (u64)first(row16_or(pb.z)) << 32 | first(row16_or(pb.y));
+					if (cpop)
+					{
+						cmin = (x0 ? (u32)__builtin_ctz(x0) : 32u + (u32)__builtin_ctz(x1)) | (u32)__builtin_ctzll(ym) << 8 | (u32)__builtin_ctzll(zm) << 16;
+						cmax = (x1 ? 63u - (u32)__builtin_clz(x1) : 31u - (u32)__builtin_clz(x0)) | (63u - (u32)__builtin_clzll(ym)) << 8 |
+						       (63u - (u32)__builtin_clzll(zm)) << 16;
+					}
+				}
 				const uint4 *c4 = reinterpret_cast<const uint4 *>(chk);
 				uint4 m = c4[0];
 #pragma unroll
@@ -607,6 +701,52 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 						if (row == 0u) cyc[wave][2] = k - astep;
 					}
 				}
+				if (Moving)
+				{
+					const uint4 am = *reinterpret_cast<const uint4 *>(cyc[wave] + kMetaPop);
+					const u32 apop = (u32)__builtin_amdgcn_readfirstlane((int)am.x), amin = (u32)__builtin_amdgcn_readfirstlane((int)am.y),
+					          amax = (u32)__builtin_amdgcn_readfirstlane((int)am.z);
+					// the filter: nothing below runs unless the two states could be translates of each other, clear of the faces, d != 0
+					if (j != 0u && k != astep && (a.stop_mask & (u32)CA3D_STOP_MOVING) && cpop != 0u && cpop == apop && cmin != amin && cmax - cmin == amax - amin &&
+					    box_inside(cmin, cmax) && box_inside(amin, amax))
+					{
+						const int dx = (int)(cmin & 0xFFu) - (int)(amin & 0xFFu), dy = (int)((cmin >> 8) & 0xFFu) - (int)((amin >> 8) & 0xFFu),
+						          dz = (int)(cmin >> 16) - (int)(amin >> 16);
+						u32 r = row, w = wave;
+						asm volatile("" : "+v"(r), "+s"(w));
+						const u32 *anchor = ka->anchor + (size_t)u * kEnsembleWords;
+						const u32 sy = r - (u32)dy; // the anchor's row that lands on this one; outside 0 .. 63: nothing does
+						u32 diff = 0;
+#pragma unroll
+						for (u32 p = 0; p < kPT; p++)
+						{
+							const u32 sz = w * kPT + p - (u32)dz;
+							uint2 v = make_uint2(0u, 0u);
+							if (sy < 64u && sz < 64u) v = *reinterpret_cast<const uint2 *>(anchor + (sz * 64u + sy) * 2u); // inside the universe's 8192 words
+							u64 from = (u64)v.y << 32 | v.x;
+							from = dx >= 0 ? from << dx : from >> -dx; // |dx| <= 61
+							diff |= ((u32)from ^ s[p][0]) | ((u32)(from >> 32) ^ s[p][1]);
+						}
+						// every lane votes: the ballot is taken BEFORE the branch that leaves lane 0 alone
+						const u32 differs = __ballot(diff != 0u) ? 1u : 0u;
+						// (a part of chk written here only: a step's barrier, or the record's, lies before the next time)
+						if (row == 0u) chk[kMovDiff + wave] = differs;
+						__syncthreads();
+						const uint4 *d4 = reinterpret_cast<const uint4 *>(chk) + kMovDiff / 4u;
+						uint4 m = d4[0];
+#pragma unroll
+						for (int i = 1; i < (int)kWaves / 4; i++) { const uint4 n = d4[i]; m.x |= n.x; m.y |= n.y; m.z |= n.z; m.w |= n.w; }
+						if (__builtin_amdgcn_readfirstlane((int)(m.x | m.y | m.z | m.w)) == 0)
+						{
+							fired |= (u32)CA3D_STOP_MOVING;
+							if (row == 0u)
+							{
+								cyc[wave][kMetaPeriod] = k - astep;
+								cyc[wave][kMetaShift] = ((u32)dx & 0xFFu) | ((u32)dy & 0xFFu) << 8 | ((u32)dz & 0xFFu) << 16; // signed bytes
+							}
+						}
+					}
+				}
 			}
 			if (fired) return true;
 			if (Cycle && (j & (j - 1u)) == 0u) // check points 0, 1, 2, 4, 8 ...: the anchor moves here, AFTER the comparison
@@ -615,6 +755,7 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 #pragma unroll
 				for (u32 p = 0; p < kPT; p++) *reinterpret_cast<uint2 *>(anchor + p * 128u) = make_uint2(s[p][0], s[p][1]);
 				if (row == 0u) *reinterpret_cast<uint2 *>(cyc[wave]) = make_uint2(ka->base + t, hash);
+				if (Moving && row == 0u) *reinterpret_cast<uint4 *>(cyc[wave] + kMetaPop) = make_uint4(cpop, cmin, cmax, 0u);
 			}
 			until = a.check_every;
 		}
@@ -644,10 +785,15 @@ __device__ __forceinline__ void ensemble_run(const EnsembleArgs &a)
 		a.reason[u] = fired;
 		if (Cycle)
 		{
-			u32 *out = ka->cycle + 4u * u; // (thread 0 reads what it wrote itself)
+			u32 *out = ka->cycle + (Moving ? 8u : 4u) * u; // (thread 0 reads what it wrote itself)
 			out[0] = cyc[0][0];
 			out[1] = cyc[0][1];
 			out[2] = cyc[0][2];
+			if (Moving)
+			{
+#pragma unroll
+				for (u32 i = kMetaShift; i <= kMetaMax; i++) out[i] = cyc[0][i];
+			}
 		}
 	}
 	if (t == 0u && !a.reset) return; // nothing moved: state and record stand
@@ -747,10 +893,16 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_trace(Ensembl
 __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_clustered64(EnsembleArgs a) { ensemble_run<ClusteredStep, false, false>(a); }
 __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_clustered64_cycle(EnsembleArgs a) { ensemble_run<ClusteredStep, true, false>(a); }
 __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_clustered64_trace(EnsembleArgs a) { ensemble_run<ClusteredStep, false, true>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_vn64_moving(EnsembleArgs a) { ensemble_run<VnStep, true, false, true>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_moore64_moving(EnsembleArgs a) { ensemble_run<MooreStep, true, false, true>(a); }
+__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_clustered64_moving(EnsembleArgs a) { ensemble_run<ClusteredStep, true, false, true>(a); }
 
-// the one place that maps an ensemble's kind (and whether CA3D_STOP_PERIODIC is watched, or samples are recorded) to its kernel
-auto kernel_of(int neighbourhood, bool clustered, bool cycle, bool trace) -> void (*)(EnsembleArgs)
+// the one place that maps an ensemble's kind (and whether CA3D_STOP_PERIODIC or CA3D_STOP_MOVING is watched, or samples are recorded) to
+// its kernel
+auto kernel_of(int neighbourhood, bool clustered, bool cycle, bool trace, bool moving = false) -> void (*)(EnsembleArgs)
 {
+	if (moving) // (never with trace: launch_ensemble)
+		return clustered ? ca_ensemble_clustered64_moving : neighbourhood == CA3D_ENSEMBLE_MOORE ? ca_ensemble_moore64_moving : ca_ensemble_vn64_moving;
 	if (clustered) return trace ? ca_ensemble_clustered64_trace : cycle ? ca_ensemble_clustered64_cycle : ca_ensemble_clustered64;
 	if (trace) return neighbourhood == CA3D_ENSEMBLE_MOORE ? ca_ensemble_moore64_trace : ca_ensemble_vn64_trace; // (never with cycle: launch_ensemble)
 	if (neighbourhood == CA3D_ENSEMBLE_MOORE) return cycle ? ca_ensemble_moore64_cycle : ca_ensemble_moore64;
@@ -761,7 +913,9 @@ auto kernel_of(int neighbourhood, bool clustered, bool cycle, bool trace) -> voi
 
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 {
-	const bool cycle = (l.stop_mask & (uint32_t)CA3D_STOP_PERIODIC) != 0u, trace = l.samples != nullptr;
+	// the *_moving kernels watch CA3D_STOP_PERIODIC too when the mask holds it: they are *_cycle kernels with one more condition
+	const bool moving = (l.stop_mask & (uint32_t)CA3D_STOP_MOVING) != 0u;
+	const bool cycle = moving || (l.stop_mask & (uint32_t)CA3D_STOP_PERIODIC) != 0u, trace = l.samples != nullptr;
 	const bool checks = l.stop_mask || trace; // the launch has check points
 	if (l.count == 0 || (l.clustered && l.neighbourhood != CA3D_ENSEMBLE_MOORE) || l.steps > kEnsembleMaxSteps || (checks && l.check_every == 0)) return hipErrorInvalidValue;
 	if (cycle && (!l.anchor || !l.cycle || trace)) return hipErrorInvalidValue;
@@ -784,7 +938,7 @@ hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream)
 	a.next_check = l.stop_mask ? l.base / l.check_every + (into ? 1u : 0u) : 0u; // launches are cut ON check points: one that ends a launch and opens the next counts once
 	a.samples = l.samples;
 	a.sample_stride = l.sample_stride;
-	hipLaunchKernelGGL(kernel_of(l.neighbourhood, l.clustered, cycle, trace), dim3(l.count), dim3(kThreads), 0, stream, a);
+	hipLaunchKernelGGL(kernel_of(l.neighbourhood, l.clustered, cycle, trace, moving), dim3(l.count), dim3(kThreads), 0, stream, a);
 	return hipGetLastError();
 }
 

@@ -46,6 +46,7 @@ def _summary(s: "_capi.SummaryStruct", planes: Optional[np.ndarray]) -> Summary:
 
 
 STOP_EXTINCT, STOP_STILL, STOP_PERIODIC = _capi.STOP_EXTINCT, _capi.STOP_STILL, _capi.STOP_PERIODIC
+STOP_MOVING = _capi.STOP_MOVING  # Ensemble.step_until_moving only
 
 
 def _seed_spec(grid_size: int, seed: int, and_rounds: int = 0, box=None) -> "_capi.SeedStruct":

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi, host
 from ._capi import ENSEMBLE_ALL, ENSEMBLE_WORDS, Stats
-from .engine import STOP_EXTINCT, STOP_PERIODIC, STOP_STILL, Summary, _as_i32, _as_u32, _seed_spec, _summary
+from .engine import STOP_EXTINCT, STOP_MOVING, STOP_PERIODIC, STOP_STILL, Summary, _as_i32, _as_u32, _seed_spec, _summary
 
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
@@ -169,6 +169,19 @@ class Ensemble:
         _capi.check(self._lib.ca3d_ensemble_step_until_cycle(self._h, max_steps, check_every, stop_mask, done.ctypes.data_as(_u32p),
                                                              reason.ctypes.data_as(_u32p), period.ctypes.data_as(_u32p)))
         return done, reason, period
+
+    def step_until_moving(self, max_steps: int, check_every: int = 8,
+                          stop_mask: int = STOP_EXTINCT | STOP_STILL | STOP_PERIODIC | STOP_MOVING) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """`step_until_cycle` that also stops a universe whose state at a check point is its anchor state translated by a vector
+        d != 0, both clear of the faces (`ca3d_ensemble_step_until_moving`, STOP_MOVING): a glider or spaceship, decided inside the kernel
+        and exact -> (steps_done u32[n], reason u32[n], period u32[n], shift i32[n, 3]). `period` is a multiple of the ship's period,
+        `shift[u]` = (dx, dy, dz) its displacement over `period`, zero unless STOP_MOVING is in `reason[u]`."""
+        done, reason, period = (np.empty(self.n, dtype=np.uint32) for _ in range(3))
+        shift = np.empty((self.n, 3), dtype=np.int32)
+        _capi.check(self._lib.ca3d_ensemble_step_until_moving(self._h, max_steps, check_every, stop_mask, done.ctypes.data_as(_u32p),
+                                                              reason.ctypes.data_as(_u32p), period.ctypes.data_as(_u32p),
+                                                              shift.ctypes.data_as(_i32p)))
+        return done, reason, period, shift
 
     def step_trace(self, max_steps: int, check_every: int = 8,
                    stop_mask: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:

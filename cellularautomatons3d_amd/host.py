@@ -372,6 +372,31 @@ def state_summary(grid_size: int, words, prev_words=None, layout: int = 0, z0: i
     return out
 
 
+def moved_by(grid_size: int, a_words, b_words) -> Optional[Tuple[int, int, int]]:
+    """The predicate behind CA3D_STOP_MOVING (include/ca3d.h, ca3d_ensemble_step_until_moving) on the CPU: (dx, dy, dz) when the packed
+    state `b_words` is the packed state `a_words` translated by that vector, both non-empty, both bounding boxes strictly inside the grid
+    (box_min >= 1, box_max <= G - 2 on every axis) and the vector not zero; None otherwise — equal states included. For following a
+    candidate up on the host: `moved_by(64, state_then, state_now)`."""
+    G = int(grid_size)
+    sa, sb = state_summary(G, a_words), state_summary(G, b_words)
+    if sa["population"] == 0 or sa["population"] != sb["population"]:
+        return None
+    for s in (sa, sb):
+        if min(s["box_min"]) < 1 or max(s["box_max"]) > G - 2:
+            return None
+    d = tuple(int(q - p) for p, q in zip(sa["box_min"], sb["box_min"]))
+    if d == (0, 0, 0) or tuple(int(q - p) for p, q in zip(sa["box_max"], sb["box_max"])) != d:
+        return None
+
+    def box(words, s):
+        cells = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").ravel().view(np.uint8), bitorder="little").reshape(G, G, G)  # [z, y, x]
+        (x0, y0, z0), (x1, y1, z1) = s["box_min"], s["box_max"]
+        return cells[z0:z1 + 1, y0:y1 + 1, x0:x1 + 1]
+
+    # (nothing lives outside either box: equal boxes' contents are equal states up to the shift)
+    return d if np.array_equal(box(a_words, sa), box(b_words, sb)) else None
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

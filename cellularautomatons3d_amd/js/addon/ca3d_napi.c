@@ -1211,6 +1211,31 @@ static napi_value js_ensemble_step_until_cycle(napi_env env, napi_callback_info 
 	return rc ? throw_ca3d(env, rc) : undefined(env);
 }
 
+/* ensembleStepUntilMoving(handle, maxSteps, checkEvery, stopMask, Uint32Array(n) stepsDone, Uint32Array(n) reason, Uint32Array(n) period,
+ *                         Int32Array(3 n) shift) */
+static napi_value js_ensemble_step_until_moving(napi_env env, napi_callback_info info)
+{
+	napi_value argv[8];
+	if (!get_args(env, info, 8, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t max_steps, every, mask;
+	void *done, *reason, *period, *shift;
+	size_t nd, nr, np, ns;
+	if (!e || !get_u32(env, argv[1], &max_steps) || !get_u32(env, argv[2], &every) || !get_u32(env, argv[3], &mask) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 0, &done, &nd) || !get_typed(env, argv[5], napi_uint32_array, 0, &reason, &nr) ||
+	    !get_typed(env, argv[6], napi_uint32_array, 0, &period, &np) || !get_typed(env, argv[7], napi_int32_array, 0, &shift, &ns))
+		return NULL;
+	void *p = NULL;
+	napi_get_value_external(env, argv[0], &p);
+	if (nd != ((EnsembleSlot *)p)->n || nr != nd || np != nd || ns != 3u * nd)
+	{
+		napi_throw_range_error(env, NULL, "stepsDone, reason and period must hold one entry per universe, shift three");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_step_until_moving(e, max_steps, every, mask, (uint32_t *)done, (uint32_t *)reason, (uint32_t *)period, (int32_t *)shift);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
 /* ensembleStepUntilTrace(handle, maxSteps, checkEvery, stopMask, Uint32Array(n) stepsDone, Uint32Array(n) reason,
  *                        Uint32Array(n * samplesPerUniverse * 3) samples, samplesPerUniverse, Uint32Array(n) nSamples) */
 static napi_value js_ensemble_step_until_trace(napi_env env, napi_callback_info info)
@@ -1425,7 +1450,7 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"summary", js_summary}, {"groupSummary", js_group_summary}, {"stepUntilAsync", js_step_until_async}, {"stepUntilCycleAsync", js_step_until_cycle_async},
 	    {"ensembleCreate", js_ensemble_create}, {"ensembleDestroy", js_ensemble_destroy}, {"ensembleConfigure", js_ensemble_configure},
 	    {"ensembleSetRules", js_ensemble_set_rules}, {"ensembleUploadState", js_ensemble_upload_state}, {"ensembleReadState", js_ensemble_read_state},
-	    {"ensembleStep", js_ensemble_step}, {"ensembleStepUntil", js_ensemble_step_until}, {"ensembleStepUntilCycle", js_ensemble_step_until_cycle}, {"ensembleStepUntilTrace", js_ensemble_step_until_trace}, {"ensembleSummaries", js_ensemble_summaries},
+	    {"ensembleStep", js_ensemble_step}, {"ensembleStepUntil", js_ensemble_step_until}, {"ensembleStepUntilCycle", js_ensemble_step_until_cycle}, {"ensembleStepUntilMoving", js_ensemble_step_until_moving}, {"ensembleStepUntilTrace", js_ensemble_step_until_trace}, {"ensembleSummaries", js_ensemble_summaries},
 	    {"ensembleSynchronize", js_ensemble_synchronize}, {"ensembleStats", js_ensemble_stats},
 	    {"seedState", js_seed_state}, {"groupSeedState", js_group_seed_state}, {"ensembleSeedState", js_ensemble_seed_state},
 	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables},

@@ -227,6 +227,7 @@ function loadAddon()
 
 const STOP_EXTINCT = 1, STOP_STILL = 2; // ca3d_step_until: bits of `reason`
 const STOP_PERIODIC = 4; // ... and of ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle, which alone take it
+const STOP_MOVING = 8; // ... and of ca3d_ensemble_step_until_moving (Ensemble.stepUntilMoving), which alone takes it
 
 class Engine
 {
@@ -505,6 +506,17 @@ class Ensemble
 		this._a.ensembleStepUntilCycle(this._e, maxSteps, o.checkEvery, o.stopMask, stepsDone, reason, period);
 		return { stepsDone, reason, period };
 	}
+	/** stepUntilCycle that also stops a universe whose state at a check point is its anchor state translated by a vector d != 0, both clear
+	 *  of the faces (ca3d_ensemble_step_until_moving): a glider or spaceship, decided inside the kernel and exact
+	 *  -> {stepsDone, reason, period: Uint32Array(n) each, shift: Int32Array(3 n)} (reason: + STOP_MOVING; shift[3 u ..]: dx, dy, dz over
+	 *  period[u], zero unless STOP_MOVING is in reason[u]) */
+	stepUntilMoving(maxSteps, opts)
+	{
+		const o = Object.assign({ checkEvery: 8, stopMask: STOP_EXTINCT | STOP_STILL | STOP_PERIODIC | STOP_MOVING }, opts || {});
+		const stepsDone = new Uint32Array(this.n), reason = new Uint32Array(this.n), period = new Uint32Array(this.n), shift = new Int32Array(3 * this.n);
+		this._a.ensembleStepUntilMoving(this._e, maxSteps, o.checkEvery, o.stopMask, stepsDone, reason, period, shift);
+		return { stepsDone, reason, period, shift };
+	}
 	/** stepUntil that records every universe's population curve inside the kernel: one sample (population, births, deaths) per check
 	 *  point -> {samples: Uint32Array(n * samplesPerUniverse * 3), samplesPerUniverse, nSamples, stepsDone, reason}; sample j of universe u
 	 *  starts at samples[(u * samplesPerUniverse + j) * 3], slots past nSamples[u] are zero. stopMask: STOP_EXTINCT | STOP_STILL bits;
@@ -526,7 +538,7 @@ class Ensemble
 }
 
 module.exports = {
-	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
+	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, STOP_MOVING, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
 	initialState, dispatchShape, traceSamples, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
 };

@@ -303,7 +303,8 @@ enum
 {
 	CA3D_STOP_EXTINCT = 1,
 	CA3D_STOP_STILL = 2,
-	CA3D_STOP_PERIODIC = 4 /* ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle only: the two calls above it refuse the bit */
+	CA3D_STOP_PERIODIC = 4, /* ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle only: the two calls above it refuse the bit */
+	CA3D_STOP_MOVING = 8    /* ca3d_ensemble_step_until_moving only: every other call refuses the bit */
 };
 int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, ca3d_summary *out, uint32_t *steps_done,
                     uint32_t *reason);
@@ -332,7 +333,7 @@ int ca3d_step_until(ca3d_t *h, uint32_t max_steps, uint32_t check_every, uint32_
  *   - A cycle of period p entered after a transient of m steps is found at step a + lcm(p, check_every), a the first anchor step with
  *     a >= m and the next anchor move at least that lcm away: at most about 3 x max(m, lcm) steps after the start.
  *   - The state afterwards is bit for bit the state after ca3d_step(steps_done), as for the other conditions.
- *   - Patterns that translate are not cycles: nothing is compared modulo shifts.
+ *   - Patterns that translate are not cycles: nothing is compared modulo shifts (ensembles: ca3d_ensemble_step_until_moving does that).
  * stop_mask: any subset of the three bits. *steps_done, *reason, *period are nullable. The anchor is a device copy of the state,
  * allocated at the first call and freed by ca3d_configure / ca3d_destroy; the filter is the summary's digest, which every check point
  * computes anyway, and equal digests start one compare kernel over the two buffers. Stepping goes through ca3d_step as in
@@ -430,6 +431,36 @@ int ca3d_ensemble_step_until(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t ch
  * CA3D_STOP_PERIODIC. Everything else — launch cutting at 65 536 steps, stats, records, readiness errors — as ca3d_ensemble_step_until. */
 int ca3d_ensemble_step_until_cycle(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
                                    uint32_t *reason, uint32_t *period);
+/* Stop on a spaceship: ca3d_ensemble_step_until_cycle with a fourth condition, exact detection of a pattern that reproduced itself
+ * somewhere else, decided inside the kernel (ca_ensemble_vn64_moving / ca_ensemble_moore64_moving / ca_ensemble_clustered64_moving).
+ *   CA3D_STOP_MOVING  the state at a check point equals the anchor state translated by a vector d != 0, both clear of the faces
+ * It is ca3d_ensemble_step_until_cycle's definition, per universe, with the same check points and the same ONE anchor on Brent's
+ * schedule, and one more condition evaluated at every check point j > 0. With A the anchor state and C the current state, MOVING holds
+ * iff both are non-empty, both bounding boxes lie strictly inside the grid (every box_min >= 1, every box_max <= 62: a pattern on a -
+ * face sees the dead boundary and one on a + face wraps, so a match there says nothing about what follows), d = box_min(C) - box_min(A)
+ * is not the zero vector, and C equals A translated by d, cell for cell. In the executable form above the line
+ *                 | (j > 0 and inside(t[k]) and inside(t[anchor]) and d != 0 and t[k] == translate(t[anchor], d) ? MOVING : 0)
+ * joins `fired`, masked by stop_mask like the rest, and the return becomes period = fired & (PERIODIC | MOVING) ? k - anchor : 0,
+ * shift = fired & MOVING ? d : (0, 0, 0). What follows from it:
+ *   - It is EXACT. Population, box extents and hashes only filter; a stop is declared only after every word has been compared.
+ *   - PERIODIC and MOVING exclude each other (d = 0 against d != 0). Either may fire beside EXTINCT or STILL.
+ *   - period[u] is a multiple of the ship's true period: lcm(true period, check_every) at a regular check point.
+ *   - shift[u] is the displacement over that period; each component lies in -61 .. 61.
+ *   - A ship of period p entered after a transient of m steps is found about 3 x max(m, lcm) steps after the start, provided it stays
+ *     clear of the faces that long.
+ *   - The call proves that the pattern reproduced itself displaced between two check points. It does not prove that the pattern goes
+ *     on: it will reach a face.
+ *   - MOVING never fires on entry, and the anchor does not survive the call.
+ * stop_mask: any subset of the four bits. Without CA3D_STOP_MOVING the call IS ca3d_ensemble_step_until_cycle with the same mask, and
+ * without CA3D_STOP_PERIODIC as well ca3d_ensemble_step_until: the launches are those calls' kernels, the results theirs, shift all
+ * zero. The three other calls keep refusing the bit. steps_done, reason, period: B entries each; shift: [B][3] (dx, dy, dz); all four
+ * nullable. At a check point the workgroup reduces population and bounding box on the check's own barrier; the anchor's are kept beside
+ * its step and hash (B x 8 words on the device, allocated at the first call with CA3D_STOP_MOVING in stop_mask, freed by a configure;
+ * the anchors themselves are ca3d_ensemble_step_until_cycle's). Equal populations, equal box extents, both boxes inside and d != 0
+ * start the comparison of all words against the shifted anchor. A refused call leaves the caller's arrays as they were. Everything
+ * else — launch cutting at 65 536 steps, stats, records, readiness errors — as ca3d_ensemble_step_until. */
+int ca3d_ensemble_step_until_moving(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
+                                    uint32_t *reason, uint32_t *period, int32_t *shift /* [B][3]: dx, dy, dz */);
 /* ca3d_ensemble_step_until that also RECORDS each universe's population curve, written by the kernel (ca_ensemble_vn64_trace /
  * ca_ensemble_moore64_trace): one sample — population, births, deaths, meaning what they mean in ca3d_summary, births and deaths against
  * the state one step earlier — per check point and universe, with no launch, synchronisation or read-back per sample.

@@ -25,6 +25,13 @@ states with every universe still running; then the two alternate from freshly up
 the launch (Ensemble.stats) and of the host clock around the call are reported. Written to profiles/ensemble_cycle_64.json unless --out
 says otherwise.
 
+--moving measures what watching CA3D_STOP_MOVING costs on top of that, for the three kernels (von Neumann, Moore, and clustered holding the
+Moore rule with silent side tables — the rule is data, the kernel's work does not depend on it, and bench.py's clustered rule lets
+universes stop within the call): Ensemble.step_until_moving (stop mask 15, the *_moving kernels: a population and bounding-box reduction on every check's
+barrier) against Ensemble.step_until_cycle (stop mask 7, the *_cycle kernels) on the same universes, built like --cycle: B = 256 and 1024,
+256 steps, check_every 1 and 8, density-1/2 fills on which nothing stops, the same verification, medians of the hipEvent time. Written to
+profiles/ensemble_moving_64.json unless --out says otherwise.
+
 --trace measures what a population curve costs, for both neighbourhoods: (a) Ensemble.step_trace(steps, check_every, stop mask 0) — the
 *_trace kernels write one sample (population, births, deaths) per check point and universe — against (b) the path without it, K - 1
 rounds of ca3d_ensemble_step(check_every) + ca3d_ensemble_summarize collecting the same three numbers from the records (through the C
@@ -132,6 +139,50 @@ def cycle_rows(args):
     return rows
 
 
+def moving_rows(args):
+    """step_until_moving (mask 15) against step_until_cycle (mask 7): one row per (kernel, B, check_every)."""
+    ens = Ensemble(0)
+    rows = []
+    for kind in ("von neumann", "moore", "clustered"):
+        clustered = kind == "clustered"
+        nb = "moore" if clustered else kind
+        rule = dict(neighbourhood=nb, born=RULES[nb][0], survive=RULES[nb][1])  # clustered: the Moore rule, both side tables silent
+        for B in args.universes:
+            words = fills(B)
+            ens.configure(B, neighbourhood=nb, clustered=clustered)
+            ens.set_rule_strings(_capi.ENSEMBLE_ALL, **rule)
+            for every in (1, 8):
+                def call(moving):
+                    """One call from the uploaded fills -> (event ms, wall ms, steps_done, reason)."""
+                    ens.upload_state(0, words)
+                    t0 = time.perf_counter()
+                    out = ens.step_until_moving(args.steps, check_every=every, stop_mask=15) if moving else ens.step_until_cycle(args.steps, check_every=every, stop_mask=7)
+                    wall = (time.perf_counter() - t0) * 1e3
+                    return ens.stats().gpu_ms, wall, out[0], out[1]
+
+                _, _, done, reason = call(True)
+                with_moving = ens.read_state()
+                _, _, done0, reason0 = call(False)
+                if not np.array_equal(with_moving, ens.read_state()):
+                    raise SystemExit(f"{kind} B={B} check_every={every}: step_until_moving and step_until_cycle left different states")
+                if reason.any() or reason0.any() or (done != args.steps).any() or (done0 != args.steps).any():
+                    raise SystemExit(f"{kind} B={B} check_every={every}: a universe stopped within {args.steps} steps — not every check would be paid")
+                tm, tc = [], []
+                for _ in range(args.repeats):
+                    tm.append(call(True)[:2])
+                    tc.append(call(False)[:2])
+                ev_m, ev_c = statistics.median(t[0] for t in tm), statistics.median(t[0] for t in tc)
+                wall_m, wall_c = statistics.median(t[1] for t in tm), statistics.median(t[1] for t in tc)
+                row = {"kernel": kind, "universes": B, "steps": args.steps, "check_every": every,
+                       "step_until_moving": {"event_us": ev_m * 1e3, "event_us_min_max": [min(t[0] for t in tm) * 1e3, max(t[0] for t in tm) * 1e3], "wall_us": wall_m * 1e3},
+                       "step_until_cycle": {"event_us": ev_c * 1e3, "event_us_min_max": [min(t[0] for t in tc) * 1e3, max(t[0] for t in tc) * 1e3], "wall_us": wall_c * 1e3},
+                       "moving_over_cycle_event": ev_m / ev_c, "moving_over_cycle_wall": wall_m / wall_c, "states_verified": B}
+                rows.append(row)
+                print(json.dumps(row))
+    ens.close()
+    return rows
+
+
 def trace_rows(args):
     """step_trace against the step + summaries loop and against plain stepping: one row per (neighbourhood, B, check_every)."""
     import ctypes as C
@@ -223,11 +274,12 @@ def main():
                     help="of the ensemble and of the rule both paths run; clustered: a clustered ensemble and bench.py's clustered rule")
     ap.add_argument("--out", default=None, help="JSON file to write (moore: profiles/ensemble_moore_64.json)")
     ap.add_argument("--cycle", action="store_true", help="measure step_until_cycle against step_until instead (both neighbourhoods; default B = 256 1024)")
+    ap.add_argument("--moving", action="store_true", help="measure step_until_moving against step_until_cycle instead (von Neumann, Moore, clustered; default B = 256 1024)")
     ap.add_argument("--trace", action="store_true", help="measure step_trace against the step + summaries loop and plain stepping instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256, 1024] if args.cycle or args.trace else [1, 256, 1024, 4096]
+        args.universes = [256, 1024] if args.cycle or args.trace or args.moving else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -262,6 +314,23 @@ def main():
         lost = [(r["neighbourhood"], r["universes"], r["check_every"]) for r in result["rows"] if not r["trace_beats_loop_beyond_spread"]]
         if lost:
             raise SystemExit(f"step_trace does not beat the step + summaries loop by more than the spread at {lost}")
+        return
+    if args.moving:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_moving_64.json")
+        names = {"von neumann": "ca_ensemble_vn64", "moore": "ca_ensemble_moore64", "clustered": "ca_ensemble_clustered64"}
+        result = {
+            "what": "B universes of 64^3, random fills (density 1/2), rules B2,4/S1,3,5 (von Neumann), B5-7/S4-6 (Moore; the same, side tables silent, in the clustered ensemble): "
+                    "Ensemble.step_until_moving(steps, stop mask 15) vs. Ensemble.step_until_cycle(steps, stop mask 7); nothing stops, every check is paid",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {k: [v + "_moving", v + "_cycle"] for k, v in names.items()},
+            "timing": f"one call from freshly uploaded states; hipEvent time around the launch and host clock around the call; medians of {args.repeats} alternating measurements",
+            "rows": moving_rows(args),
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
         return
     if args.cycle:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_cycle_64.json")
