@@ -156,6 +156,9 @@ SYMBOLS = [
     ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
+    ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ca3d_ensemble_get_sheet_stats", C.c_int, [_H, C.POINTER(RenderStats)]),
     ("ca3d_render_target", C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     ("ca3d_synchronize", C.c_int, [_H]),
     ("ca3d_recovered_launches", C.c_int, [_H, C.POINTER(C.c_uint32)]),

@@ -4,6 +4,7 @@
 // over B workgroups is B universes, each with its own rule table pair, its own step counter, its own summary record and — in
 // ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle / ca3d_ensemble_step_until_moving / ca3d_ensemble_step_until_trace — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
+// ca3d_ensemble_render_sheet draws a range of universes as the tiles of one contact sheet (render_sheet.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -43,6 +44,16 @@ struct ca3d_ensemble
 	bool timed = false;
 	uint64_t last_steps = 0, last_launches = 0;
 	double last_cell_steps = 0;
+	// ca3d_ensemble_render_sheet: the sheet's three device targets (presentation RGBA8, light RGBA16F, depth RG16F), grown when a sheet
+	// has more than sheet_px pixels, gone with the other arrays at a configure; its three counters, its event pair (created at the first
+	// sheet) and what ca3d_ensemble_get_sheet_stats says of the last one
+	uint32_t *sheet_present = nullptr, *sheet_depth = nullptr;
+	uint2 *sheet_light = nullptr;
+	size_t sheet_px = 0;
+	unsigned long long *sheet_counters = nullptr;
+	hipEvent_t ev_sheet_start = nullptr, ev_sheet_stop = nullptr;
+	bool sheet_drawn = false;
+	uint64_t sheet_primary_rays = 0;
 };
 
 namespace
@@ -58,6 +69,13 @@ void free_arrays(ca3d_ensemble *e)
 	if (e->seed_dev) hipFree(e->seed_dev);
 	if (e->seed_host) hipHostFree(e->seed_host);
 	e->seed_dev = e->seed_host = nullptr;
+	for (void *p : {(void *)e->sheet_present, (void *)e->sheet_light, (void *)e->sheet_depth, (void *)e->sheet_counters})
+		if (p) hipFree(p);
+	e->sheet_present = e->sheet_depth = nullptr;
+	e->sheet_light = nullptr;
+	e->sheet_counters = nullptr;
+	e->sheet_px = 0;
+	e->sheet_drawn = false;
 	e->n = 0;
 	e->timed = false;
 }
@@ -319,6 +337,35 @@ int step_until(ca3d_ensemble *e, uint32_t max_steps, uint32_t check_every, uint3
 	return CA3D_OK;
 }
 
+// room for a sheet of `px` pixels in the three targets, and the counters; a failure leaves the handle with what it had
+int size_sheet_targets(ca3d_ensemble *e, size_t px)
+{
+	if (!e->sheet_counters) HIP_TRY(hipMalloc((void **)&e->sheet_counters, 3u * sizeof(unsigned long long)));
+	if (!e->ev_sheet_start) HIP_TRY(hipEventCreate(&e->ev_sheet_start));
+	if (!e->ev_sheet_stop) HIP_TRY(hipEventCreate(&e->ev_sheet_stop));
+	if (px <= e->sheet_px) return CA3D_OK;
+	uint32_t *present = nullptr, *depth = nullptr;
+	uint2 *light = nullptr;
+	hipError_t err = hipMalloc((void **)&present, px * 4u);
+	if (err == hipSuccess) err = hipMalloc((void **)&light, px * 8u);
+	if (err == hipSuccess) err = hipMalloc((void **)&depth, px * 4u);
+	if (err != hipSuccess)
+	{
+		for (void *p : {(void *)present, (void *)light, (void *)depth})
+			if (p) hipFree(p);
+		(void)hipGetLastError();
+		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating a sheet of %zu pixels: %s", px, hipGetErrorString(err));
+	}
+	if (e->sheet_px)
+	{
+		HIP_TRY(hipStreamSynchronize(e->stream)); // a sheet that was only enqueued may still be drawing into the old targets
+		for (void *p : {(void *)e->sheet_present, (void *)e->sheet_light, (void *)e->sheet_depth}) hipFree(p);
+	}
+	e->sheet_present = present; e->sheet_light = light; e->sheet_depth = depth;
+	e->sheet_px = px;
+	return CA3D_OK;
+}
+
 } // namespace
 
 extern "C"
@@ -363,6 +410,8 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	if (e->ev_start) hipEventDestroy(e->ev_start);
 	if (e->ev_stop) hipEventDestroy(e->ev_stop);
 	if (e->ev_seed) hipEventDestroy(e->ev_seed);
+	if (e->ev_sheet_start) hipEventDestroy(e->ev_sheet_start);
+	if (e->ev_sheet_stop) hipEventDestroy(e->ev_sheet_stop);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
 	return CA3D_OK;
@@ -673,6 +722,69 @@ int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, ca3d_stats *out) CA3D_API_TRY
 		HIP_TRY(hipEventElapsedTime(&ms, e->ev_start, e->ev_stop));
 		out->gpu_ms = ms;
 	}
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_render_sheet(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const float uniforms[128], uint32_t tile_w, uint32_t tile_h,
+                               uint32_t columns, uint32_t spp, uint8_t *presentation_rgba8, uint16_t *light_rgba16f, uint16_t *depth_rg16f) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!uniforms) return fail(CA3D_ERR_INVALID_ARGUMENT, "uniforms is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if (columns == 0) return fail(CA3D_ERR_INVALID_ARGUMENT, "a sheet has at least one column of tiles");
+	for (uint32_t t : {tile_w, tile_h})
+		if (t < 16u || t > 1024u || t % 16u)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "bad tile size %ux%u: width and height are multiples of 16 from 16 to 1024", tile_w, tile_h);
+	if (spp != 1 && spp != 4) return fail(CA3D_ERR_INVALID_ARGUMENT, "spp must be 1 or 4");
+	const uint64_t rows = ((uint64_t)count + columns - 1u) / columns, W = (uint64_t)columns * tile_w, H = rows * tile_h;
+	if (W * H > (1ull << 26)) // (columns < 2^32, tile_w <= 2^10, H <= 2^30: no overflow)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "a sheet of %llu x %llu pixels: at most 2^26 pixels", (unsigned long long)W, (unsigned long long)H);
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t px = (size_t)(W * H);
+	if ((rc = size_sheet_targets(e, px))) return rc;
+	SheetLaunch l{};
+	l.state = e->state;
+	l.first = first; l.count = count;
+	l.tile_w = tile_w; l.tile_h = tile_h; l.columns = columns; l.spp = spp;
+	l.uniforms = uniforms;
+	l.presentation = e->sheet_present; l.light = e->sheet_light; l.depth = e->sheet_depth;
+	l.counters = e->sheet_counters;
+	e->sheet_drawn = false;
+	HIP_TRY(hipMemsetAsync(e->sheet_counters, 0, 3u * sizeof(unsigned long long), e->stream));
+	HIP_TRY(hipEventRecord(e->ev_sheet_start, e->stream));
+	HIP_TRY(launch_render_sheet(l, e->stream));
+	HIP_TRY(hipEventRecord(e->ev_sheet_stop, e->stream));
+	e->sheet_drawn = true;
+	e->sheet_primary_rays = (uint64_t)count * tile_w * tile_h * spp;
+	if (presentation_rgba8) HIP_TRY(hipMemcpyAsync(presentation_rgba8, e->sheet_present, px * 4u, hipMemcpyDeviceToHost, e->stream));
+	if (light_rgba16f) HIP_TRY(hipMemcpyAsync(light_rgba16f, e->sheet_light, px * 8u, hipMemcpyDeviceToHost, e->stream));
+	if (depth_rg16f) HIP_TRY(hipMemcpyAsync(depth_rg16f, e->sheet_depth, px * 4u, hipMemcpyDeviceToHost, e->stream));
+	if (presentation_rgba8 || light_rgba16f || depth_rg16f) HIP_TRY(hipStreamSynchronize(e->stream));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_get_sheet_stats(ca3d_ensemble_t *e, ca3d_render_stats *out) CA3D_API_TRY
+{
+	if (!e || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	if (!e->sheet_drawn) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_render_sheet has not been called yet");
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(hipEventSynchronize(e->ev_sheet_stop));
+	float ms = 0.f;
+	HIP_TRY(hipEventElapsedTime(&ms, e->ev_sheet_start, e->ev_sheet_stop));
+	unsigned long long c[3] = {0, 0, 0};
+	HIP_TRY(hipMemcpyAsync(c, e->sheet_counters, sizeof c, hipMemcpyDeviceToHost, e->stream)); // behind the sheet; a sheet enqueued later has zeroed them
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	*out = ca3d_render_stats{};
+	out->gpu_ms = ms;
+	out->primary_rays = e->sheet_primary_rays;
+	out->shadow_rays = c[0];
+	out->primary_cell_visits = c[1];
+	out->shadow_cell_visits = c[2];
 	return CA3D_OK;
 }
 CA3D_API_CATCH

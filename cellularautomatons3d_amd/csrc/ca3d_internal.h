@@ -228,6 +228,23 @@ constexpr uint32_t ensemble_rule_words(int neighbourhood, bool clustered = false
 {
 	return clustered ? 6u : neighbourhood == CA3D_ENSEMBLE_MOORE ? 2u : 1u;
 }
+// render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
+// ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
+// slots past `count` are zeroed in front of it. The caller has checked every size.
+struct SheetLaunch
+{
+	const uint32_t *state;  // [B][8192], the ensemble's current states
+	uint32_t first, count;
+	uint32_t tile_w, tile_h, columns, spp;
+	const float *uniforms;  // host pointer, >= 84 floats; windowSize as given
+	uint32_t *presentation; // device RGBA8 sheet or null
+	void *light;            // device RGBA16F sheet or null
+	uint32_t *depth;        // device RG16F sheet or null
+	unsigned long long *counters; // device, 3 counters (zeroed by the caller), or null
+};
+hipError_t launch_render_sheet(const SheetLaunch &l, hipStream_t stream);
+// workgroups a universe's 16 x 16-pixel blocks are dealt to, for `count` universes of `blocks` blocks each on a chip with room for `slots` workgroups
+uint32_t sheet_shares(uint32_t count, uint32_t blocks, uint32_t slots);
 // ca_seed.hip: the counter-based fill of ca3d_seed (include/ca3d.h) written where the state lives. One launch covers the whole arrays of
 // both ping-pong buffers: array plane a is global plane z0 - ghost + a; the `ghost` planes below and above the owned ones are zeroed.
 struct SeedLaunch

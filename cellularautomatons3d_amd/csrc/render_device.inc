@@ -1,5 +1,5 @@
 // Device code shared by the renderer's translation units (render.hip: plain / in-wave scheduled / literal-frame kernels;
-// render_stream.hip: the ray-stream pipeline): vector helpers, the launch parameters, the reference's slab test / sdBox /
+// render_stream.hip: the ray-stream pipeline; render_sheet.hip: the ensemble's contact sheet): vector helpers, the launch parameters, the reference's slab test / sdBox /
 // face normal / Cook-Torrance BRDF (shaders/pathtraced_fragment_clustered.wgsl:182-254, 537-633), occupancy helpers, the exact
 // cell walk, and shade_sample — the ONE statement of a sample's arithmetic that every kernel instantiates.
 // Included inside `namespace ca3d { namespace {`; built with -ffp-contract=off (the parity target is a plain-float CPU restatement).
@@ -308,11 +308,18 @@ __device__ __forceinline__ bool live_box_clip(const RenderParams &P, v3 start, v
 	return true;
 }
 
+// Where a walk gets the packed word `key` of the volume from: the state in global memory ...
+struct GlobalWords
+{
+	__device__ __forceinline__ u32 operator()(const RenderParams &P, int key) const { return P.cells[key]; }
+};
+
 // Exact cell walk (Amanatides-Woo) from `start` along unit `dir` over (t0, tmax). SHADOW selects the visit test.
-// Returns true on a hit; `tnear_out` is the slab entry of the hit cube (primary only).
-template <bool SHADOW, bool SKIP>
-__device__ bool walk(const RenderParams &P, v3 start, v3 dir, float t0, float tmax, v3 half, int sx0, int sy0, int sz0,
-                     float &tnear_out, u32 &visits)
+// Returns true on a hit; `tnear_out` is the slab entry of the hit cube (primary only). `fetch` reads a packed word (GlobalWords, or a
+// copy of the volume somewhere closer: render_sheet.hip) — the ONE walk body whatever the words come from.
+template <bool SHADOW, bool SKIP, class Fetch>
+__device__ __forceinline__ bool walk_from(const RenderParams &P, v3 start, v3 dir, float t0, float tmax, v3 half, int sx0, int sy0, int sz0,
+                                          float &tnear_out, u32 &visits, const Fetch &fetch)
 {
 	const int G = (int)P.G;
 	const float cs = 1.0f / (float)P.G;
@@ -364,7 +371,7 @@ __device__ bool walk(const RenderParams &P, v3 start, v3 dir, float t0, float tm
 		else
 		{
 			const int key = (ix >> 5) + (iy + iz * G) * (int)P.cols;
-			if (key != wkey) { word = P.cells[key]; wkey = key; }
+			if (key != wkey) { word = fetch(P, key); wkey = key; }
 			alive = (word >> (ix & 31)) & 1u;
 		}
 		if (alive)
@@ -393,6 +400,13 @@ __device__ bool walk(const RenderParams &P, v3 start, v3 dir, float t0, float tm
 		if ((u32)ix >= (u32)G || (u32)iy >= (u32)G || (u32)iz >= (u32)G) return false;
 	}
 	return false;
+}
+
+template <bool SHADOW, bool SKIP>
+__device__ bool walk(const RenderParams &P, v3 start, v3 dir, float t0, float tmax, v3 half, int sx0, int sy0, int sz0,
+                     float &tnear_out, u32 &visits)
+{
+	return walk_from<SHADOW, SKIP>(P, start, dir, t0, tmax, half, sx0, sy0, sz0, tnear_out, visits, GlobalWords{});
 }
 
 struct Sample

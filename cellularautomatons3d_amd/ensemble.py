@@ -11,7 +11,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _capi, host
-from ._capi import ENSEMBLE_ALL, ENSEMBLE_WORDS, Stats
+from ._capi import ENSEMBLE_ALL, ENSEMBLE_WORDS, RenderStats, Stats
 from .engine import STOP_EXTINCT, STOP_MOVING, STOP_PERIODIC, STOP_STILL, Summary, _as_i32, _as_u32, _seed_spec, _summary
 
 _u32p = C.POINTER(C.c_uint32)
@@ -205,6 +205,45 @@ class Ensemble:
         recs = (_capi.SummaryStruct * count)()
         _capi.check(self._lib.ca3d_ensemble_summarize(self._h, first, count, recs))
         return [_summary(r, None) for r in recs]
+
+    def render_sheet(self, uniforms, tile_w: int, tile_h: int, columns: Optional[int] = None, spp: int = 1, first: int = 0,
+                     count: Optional[int] = None, light: bool = False, depth: bool = False):
+        """`ca3d_ensemble_render_sheet`: universes first .. first + count - 1 (default: all from `first`) as the tiles of one contact
+        sheet, one launch; tile k is the frame `Engine.render(uniforms, tile_w, tile_h, spp)` draws of universe first + k at 64^3 with
+        "render_skip" 0, bit for bit (`host.sheet_tile` cuts it out). `columns`: tiles per row (default ceil(sqrt(count))); the sheet
+        is `host.sheet_shape(count, tile_w, tile_h, columns)`. Returns the presentation sheet u8[H, W, 4]; with `light` / `depth` a
+        tuple (presentation, light f16[H, W, 4], depth f16[H, W, 2]) of the ones asked for. Fill `uniforms` with
+        `host.uniform_block(tile_w, tile_h, ...)`: one block serves every tile."""
+        u = np.ascontiguousarray(uniforms, dtype=np.float32)
+        if u.size != 128:
+            raise ValueError("the common uniform block holds 128 floats")
+        count = self.n - first if count is None else count
+        if columns is None:
+            columns = max(1, int(np.ceil(np.sqrt(max(count, 1)))))
+
+        def call(*out):
+            _capi.check(self._lib.ca3d_ensemble_render_sheet(self._h, first, count, u.ctypes.data_as(C.POINTER(C.c_float)), tile_w, tile_h,
+                                                             columns, spp, *out))
+
+        sizable = count >= 1 and columns >= 1 and tile_w >= 1 and tile_h >= 1
+        h, w = host.sheet_shape(count, tile_w, tile_h, columns) if sizable else (0, 0)
+        if not sizable or h * w > 1 << 26:
+            call(None, None, None)  # no sheet to size arrays for: the library refuses the call and names the reason
+            raise ValueError("a sheet has at least one tile, one column and one pixel a tile, and at most 2^26 pixels")
+        pres = np.empty((h, w, 4), dtype=np.uint8)
+        lt = np.empty((h, w, 4), dtype=np.float16) if light else None
+        dp = np.empty((h, w, 2), dtype=np.float16) if depth else None
+        call(pres.ctypes.data, lt.ctypes.data if light else None, dp.ctypes.data if depth else None)
+        if not (light or depth):
+            return pres
+        return (pres,) + ((lt,) if light else ()) + ((dp,) if depth else ())
+
+    def sheet_stats(self) -> RenderStats:
+        """The last sheet (`ca3d_ensemble_get_sheet_stats`): gpu_ms, primary_rays = count * tile_w * tile_h * spp, shadow rays and
+        both cell-visit counts summed over its tiles. Waits for the sheet."""
+        s = RenderStats()
+        _capi.check(self._lib.ca3d_ensemble_get_sheet_stats(self._h, C.byref(s)))
+        return s
 
     def synchronize(self) -> None:
         _capi.check(self._lib.ca3d_ensemble_synchronize(self._h))

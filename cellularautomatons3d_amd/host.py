@@ -138,6 +138,21 @@ def trace_samples(max_steps: int, check_every: int) -> int:
     return -(-max_steps // check_every) + 1
 
 
+def sheet_shape(count: int, tile_w: int, tile_h: int, columns: int) -> Tuple[int, int]:
+    """(H, W) of `ca3d_ensemble_render_sheet`'s sheet (include/ca3d.h): `columns` tiles a row, ceil(count / columns) rows."""
+    if count < 1 or columns < 1 or tile_w < 1 or tile_h < 1:
+        raise ValueError("a sheet has at least one tile, one column and one pixel a tile")
+    return -(-count // columns) * tile_h, columns * tile_w
+
+
+def sheet_tile(sheet: np.ndarray, k: int, tile_w: int, tile_h: int, columns: int) -> np.ndarray:
+    """Tile k of a sheet `[H, W, ...]` as a view: column k % columns, row k // columns."""
+    row, col = divmod(k, columns)
+    if k < 0 or (row + 1) * tile_h > sheet.shape[0] or columns * tile_w != sheet.shape[1]:
+        raise ValueError(f"tile {k} of {columns} columns of {tile_w} x {tile_h} tiles is not in a sheet of shape {sheet.shape}")
+    return sheet[row * tile_h:(row + 1) * tile_h, col * tile_w:(col + 1) * tile_w]
+
+
 def get_cluster_idx_from_grid_coordinates(grid_size: int, x: int, y: int, z: int) -> int:
     """`_getClusterIdxFromGridCoordinates` (main_pathtraced.js:1170-1178)."""
     cols = grid_size // 32

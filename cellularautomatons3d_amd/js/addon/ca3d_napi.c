@@ -1310,6 +1310,51 @@ static napi_value js_ensemble_stats(napi_env env, napi_callback_info info)
 	return o;
 }
 
+/* ensembleRenderSheet(handle, first, count, Float32Array(128) uniforms, tileW, tileH, columns, spp, Uint8Array(W * H * 4) presentation):
+ * the contact sheet of universes [first, first + count), W = columns * tileW, H = ceil(count / columns) * tileH (ca3d_ensemble_render_sheet) */
+static napi_value js_ensemble_render_sheet(napi_env env, napi_callback_info info)
+{
+	napi_value argv[9];
+	if (!get_args(env, info, 9, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, count, tw, th, columns, spp;
+	void *u, *pres;
+	size_t nu, npres;
+	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count) || !get_typed(env, argv[3], napi_float32_array, 0, &u, &nu) ||
+	    !get_u32(env, argv[4], &tw) || !get_u32(env, argv[5], &th) || !get_u32(env, argv[6], &columns) || !get_u32(env, argv[7], &spp) ||
+	    !get_typed(env, argv[8], napi_uint8_array, 0, &pres, &npres))
+		return NULL;
+	/* sizes the library refuses anyway leave no sheet to check the array against: it names the reason */
+	const int sizable = count && columns && tw && tw <= 1024u && th && th <= 1024u;
+	const uint64_t px = sizable ? (uint64_t)columns * tw * (((uint64_t)count + columns - 1u) / columns) * th : 0u;
+	if (nu != 128 || (sizable && px <= (1ull << 26) && npres != px * 4u))
+	{
+		napi_throw_range_error(env, NULL, "uniforms must be Float32Array(128); presentation must hold columns*tileW x ceil(count/columns)*tileH x 4 bytes");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_render_sheet(e, first, count, (const float *)u, tw, th, columns, spp, (uint8_t *)pres, NULL, NULL);
+	return rc ? throw_ca3d(env, rc) : undefined(env);
+}
+
+static napi_value js_ensemble_sheet_stats(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	if (!e) return NULL;
+	ca3d_render_stats st;
+	int rc = ca3d_ensemble_get_sheet_stats(e, &st);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value o;
+	napi_create_object(env, &o);
+	set_num(env, o, "gpuMs", st.gpu_ms);
+	set_num(env, o, "primaryRays", (double)st.primary_rays);
+	set_num(env, o, "shadowRays", (double)st.shadow_rays);
+	set_num(env, o, "primaryCellVisits", (double)st.primary_cell_visits);
+	set_num(env, o, "shadowCellVisits", (double)st.shadow_cell_visits);
+	return o;
+}
+
 /*
  * ca3d_seed_state and its kin: a spec crosses as eight u32 in ca3d_seed's own order — seed, andRounds, boxMin x y z, boxMax x y z
  * (js/ca3d.js builds them: seedSpec).
@@ -1456,7 +1501,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables},
 	    {"ensembleConfigureNeighbourhood", js_ensemble_configure_neighbourhood}, {"ensembleNeighbourhood", js_ensemble_neighbourhood},
 	    {"ensembleConfigureClustered", js_ensemble_configure_clustered}, {"ensembleClustered", js_ensemble_clustered},
-	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables}};
+	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables},
+	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

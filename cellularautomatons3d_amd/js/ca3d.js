@@ -533,6 +533,24 @@ class Ensemble
 	}
 	/** the universes' records, as Engine.summary() objects without planePopulation */
 	summaries(first, count) { first = first || 0; return this._a.ensembleSummaries(this._e, first, count === undefined ? this.n - first : count); }
+	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
+	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at
+	 *  64^3 with "render_skip" 0, bit for bit. `uniforms`: Float32Array(128) filled for a tileW x tileH window, one block for every tile;
+	 *  columns: tiles per row (default ceil(sqrt(count))); spp 1 or 4 -> {width, height, presentation: Uint8Array(width * height * 4)} */
+	renderSheet(opts)
+	{
+		const o = Object.assign({ spp: 1, first: 0 }, opts || {});
+		const count = o.count === undefined ? this.n - o.first : o.count;
+		const columns = o.columns === undefined ? Math.max(1, Math.ceil(Math.sqrt(count))) : o.columns;
+		const width = columns * o.tileW, height = columns ? Math.ceil(count / columns) * o.tileH : 0;
+		// (a size the library refuses — nothing to draw, more than 2^26 pixels — gets no array: it names the reason)
+		const bytes = width * height * 4;
+		const presentation = new Uint8Array(bytes > 0 && bytes <= 4 * 2 ** 26 ? bytes : 0);
+		this._a.ensembleRenderSheet(this._e, o.first, count, o.uniforms, o.tileW, o.tileH, columns, o.spp, presentation);
+		return { width, height, presentation };
+	}
+	/** the last sheet: {gpuMs, primaryRays, shadowRays, primaryCellVisits, shadowCellVisits}; waits for it */
+	sheetStats() { return this._a.ensembleSheetStats(this._e); }
 	synchronize() { this._a.ensembleSynchronize(this._e); }
 	stats() { return this._a.ensembleStats(this._e); }
 }

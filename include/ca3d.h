@@ -661,6 +661,40 @@ typedef struct ca3d_render_stats
 } ca3d_render_stats;
 int ca3d_get_render_stats(ca3d_t *h, ca3d_render_stats *out);
 
+/*
+ * The ensemble's contact sheet (no reference counterpart: its UI shows one grid): universes first .. first + count - 1 of a
+ * configured ensemble, each rendered as one tile of a sheet, in ONE launch (kernel ca_render_sheet64, csrc/render_sheet.hip: a
+ * workgroup copies its universe's 32 KiB into LDS and walks every view and shadow ray of its pixels there).
+ *
+ * The definition has no arithmetic of its own. Tile k is, bit for bit and in all three targets, the converged frame that
+ *   ca3d_render(uniforms, tile_w, tile_h, spp)
+ * draws on an engine configured at 64^3, CA3D_LAYOUT_PACKED32, holding universe first + k's current state, with "render_skip" 0 (the
+ * cell-by-cell walk; the skipping walk is only within tolerance of it) and "render_indirect" 0. ONE uniform block serves every tile;
+ * its windowSize is taken as given, exactly as ca3d_render takes it. Light gizmo, depth overlay, gamma and material colour are part of
+ * the frame and therefore of every tile. spp is 1 or 4 as in ca3d_render.
+ *
+ * Layout: the sheet is W = columns * tile_w pixels wide and H = ceil(count / columns) * tile_h high, row-major, top row first; tile k
+ * sits at column k % columns, row k / columns. Tile slots past `count` in the last row are zero in every byte of every target.
+ * Outputs, each nullable, sized as ca3d_render's for a W x H target:
+ *   presentation_rgba8  W*H*4 bytes    light_rgba16f  W*H*4 halfs    depth_rg16f  W*H*2 halfs
+ * The call runs on the ensemble's stream, behind whatever steps are queued, and draws the states those steps leave. With a pointer
+ * given it returns when that sheet is on the host; with all three NULL it draws into device targets the ensemble owns (grown on
+ * demand, freed by a configure and by destroy) and does not wait. Rules are not needed: a configured ensemble with a state in every
+ * universe of the range is enough.
+ *
+ * Errors: NULL handle or NULL uniforms — CA3D_ERR_INVALID_ARGUMENT without touching a device; not configured —
+ * CA3D_ERR_NOT_CONFIGURED; count == 0 or first + count > n, columns == 0, tile_w or tile_h not a multiple of 16 in [16, 1024], spp
+ * not 1 or 4, W * H > 2^26 pixels — CA3D_ERR_INVALID_ARGUMENT; a universe of the range without a state — CA3D_ERR_NOT_CONFIGURED,
+ * the message names the first such universe.
+ *
+ * ca3d_ensemble_get_sheet_stats describes the last sheet and waits for it: gpu_ms the hipEvent time around its launch, primary_rays =
+ * count * tile_w * tile_h * spp, shadow rays and both visit counts summed over the tiles — the sums of ca3d_get_render_stats over the
+ * frames that define the tiles. Before any sheet (or after a configure): CA3D_ERR_NOT_CONFIGURED.
+ */
+int ca3d_ensemble_render_sheet(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const float uniforms[128], uint32_t tile_w, uint32_t tile_h,
+                               uint32_t columns, uint32_t spp, uint8_t *presentation_rgba8, uint16_t *light_rgba16f, uint16_t *depth_rg16f);
+int ca3d_ensemble_get_sheet_stats(ca3d_ensemble_t *e, ca3d_render_stats *out);
+
 /* How many converged frames the engine keeps in flight (option "render_pipeline" below): the number of internal streams — on pairwise
  * different hardware queues, probed when the first pipelined frame is drawn — that such frames alternate between; 0 before that frame,
  * with the option off, or when the runtime gave the engine no two streams that run side by side. Does not wait for the GPU. */

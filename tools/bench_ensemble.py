@@ -42,6 +42,14 @@ launches, in a run of its own) and of the host clock around the call are reporte
 its synchronisations. Written to profiles/ensemble_trace_64.json unless --out says otherwise; the tool fails when (a) does not beat
 (b) by the host clock by more than the spread, after the file is written.
 
+--sheet measures the contact sheet (ca3d_ensemble_render_sheet, kernel ca_render_sheet64: every universe drawn as a tile, one launch)
+against the loop it replaces: one Engine at 64^3 and, per universe, upload_state from a host array plus ca3d_render with a host
+presentation pointer (the engine's default options). B = 256 and 1024 universes seeded with and_rounds 4 (a different seed each),
+camera host.orbit_camera(), tiles 64 x 64 and 128 x 128 at 1 and 4 samples. Before timing, sampled tiles must equal the engine's
+"render_skip" 0 frames byte for byte. Reported: medians of --repeats measurements of the sheet's hipEvent time (Ensemble.sheet_stats)
+and of the host clock around a call that reads the presentation sheet back, and of the host clock around the loop. No ratio is
+required. Written to profiles/ensemble_sheet_64.json unless --out says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -264,6 +272,60 @@ def trace_rows(args):
     return rows
 
 
+def sheet_rows(args):
+    """render_sheet against the upload + render loop: one row per (B, tile, spp)."""
+    import ctypes as C
+
+    ens, eng = Ensemble(0), Engine(0)
+    eng.configure(G)
+    fp = C.POINTER(C.c_float)
+    rows = []
+    for B in args.universes:
+        ens.configure(B)
+        ens.seed_states(0, np.arange(1, B + 1), 4)
+        words = ens.read_state()
+        columns = int(np.ceil(np.sqrt(B)))
+        for tile in (64, 128):
+            u = host.uniform_block(tile, tile, host.orbit_camera())
+            frame = np.empty((tile, tile, 4), dtype=np.uint8)
+
+            def loop(universes, spp):
+                for k in universes:
+                    eng.upload_state(words[k])
+                    _capi.check(eng._lib.ca3d_render(eng._h, u.ctypes.data_as(fp), tile, tile, spp, frame.ctypes.data, None, None))
+
+            for spp in (1, 4):
+                sheet = ens.render_sheet(u, tile, tile, columns, spp)
+                eng.set_option("render_skip", 0)
+                for k in sorted({0, 1, columns, B // 2, B - 1}):
+                    loop([k], spp)
+                    if not np.array_equal(host.sheet_tile(sheet, k, tile, tile, columns), frame):
+                        raise SystemExit(f"B {B}, tile {tile}, spp {spp}: tile {k} is not the engine's frame of universe {k}")
+                eng.set_option("render_skip", 1)  # the default: the loop as its users run it
+                gpu, wall_sheet, wall_loop = [], [], []
+                for _ in range(args.repeats):
+                    t0 = time.perf_counter()
+                    ens.render_sheet(u, tile, tile, columns, spp)
+                    wall_sheet.append((time.perf_counter() - t0) * 1e3)
+                    gpu.append(ens.sheet_stats().gpu_ms)
+                    t0 = time.perf_counter()
+                    loop(range(B), spp)
+                    wall_loop.append((time.perf_counter() - t0) * 1e3)
+                st = ens.sheet_stats()
+                row = {"universes": B, "tile": tile, "spp": spp, "columns": columns, "sheet": list(host.sheet_shape(B, tile, tile, columns))[::-1],
+                       "sheet_gpu_ms": statistics.median(gpu), "sheet_gpu_ms_all": gpu,
+                       "sheet_wall_ms": statistics.median(wall_sheet), "sheet_wall_ms_all": wall_sheet,
+                       "loop_wall_ms": statistics.median(wall_loop), "loop_wall_ms_all": wall_loop,
+                       "loop_over_sheet_wall": statistics.median(wall_loop) / statistics.median(wall_sheet),
+                       "primary_rays": int(st.primary_rays), "shadow_rays": int(st.shadow_rays),
+                       "cell_visits": int(st.primary_cell_visits + st.shadow_cell_visits), "tiles_verified": 5}
+                rows.append(row)
+                print(json.dumps(row))
+    ens.close()
+    eng.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -276,10 +338,11 @@ def main():
     ap.add_argument("--cycle", action="store_true", help="measure step_until_cycle against step_until instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--moving", action="store_true", help="measure step_until_moving against step_until_cycle instead (von Neumann, Moore, clustered; default B = 256 1024)")
     ap.add_argument("--trace", action="store_true", help="measure step_trace against the step + summaries loop and plain stepping instead (both neighbourhoods; default B = 256 1024)")
+    ap.add_argument("--sheet", action="store_true", help="measure render_sheet against the upload + render loop instead (B = 256 1024)")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256, 1024] if args.cycle or args.trace or args.moving else [1, 256, 1024, 4096]
+        args.universes = [256, 1024] if args.cycle or args.trace or args.moving or args.sheet else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -295,6 +358,24 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.sheet:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_sheet_64.json")
+        result = {
+            "what": "B universes of 64^3 seeded with and_rounds 4 (seeds 1 .. B), camera host.orbit_camera(), square tiles, ceil(sqrt(B)) columns: Ensemble.render_sheet "
+                    "(presentation read back) vs. the loop it replaces — one Engine at 64^3, per universe upload_state from a host array + ca3d_render with a host "
+                    "presentation pointer, default engine options",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"render_sheet": "ca_render_sheet64", "loop": "ca3d_render's default launches at 64^3"},
+            "timing": f"sheet_gpu_ms: hipEvent time around the sheet's launch; *_wall_ms: host clock around the call(s), presentation on the host; medians of "
+                      f"{args.repeats} alternating measurements after sampled tiles equalled the engine's render_skip 0 frames",
+            "rows": sheet_rows(args),
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.trace:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_trace_64.json")
         result = {
