@@ -55,6 +55,14 @@ class SummaryStruct(C.Structure):
     ]
 
 
+class ComponentStruct(C.Structure):
+    """ca3d_component (include/ca3d.h): one connected object of `ca3d_ensemble_census`, 32 bytes (`host.COMPONENT_DTYPE`)."""
+    _fields_ = [
+        ("population", C.c_uint32), ("first_cell", C.c_uint32), ("box_min", C.c_uint32), ("box_max", C.c_uint32), ("digest", C.c_uint64),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 class SeedStruct(C.Structure):
     """ca3d_seed (include/ca3d.h)."""
     _fields_ = [("seed", C.c_uint32), ("and_rounds", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
@@ -154,6 +162,7 @@ SYMBOLS = [
     ("ca3d_ensemble_step_until_moving", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _i32p]),
     ("ca3d_ensemble_step_until_trace", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, _u32p]),
     ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),
+    ("ca3d_ensemble_census", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ComponentStruct), _u32p, _u32p, C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

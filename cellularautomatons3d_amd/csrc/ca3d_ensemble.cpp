@@ -5,6 +5,7 @@
 // ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle / ca3d_ensemble_step_until_moving / ca3d_ensemble_step_until_trace — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
 // ca3d_ensemble_render_sheet draws a range of universes as the tiles of one contact sheet (render_sheet.hip).
+// ca3d_ensemble_census lists the connected objects of a range of universes (ca_census.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -54,6 +55,12 @@ struct ca3d_ensemble
 	hipEvent_t ev_sheet_start = nullptr, ev_sheet_stop = nullptr;
 	bool sheet_drawn = false;
 	uint64_t sheet_primary_rays = 0;
+	// ca3d_ensemble_census: the result of the call under way — [count][max_components] records, then n_components[count], then
+	// remaining[count] — in one device array of census_bytes bytes, grown when a call needs more, gone with the other arrays at a
+	// configure; its event pair (created at the first census)
+	uint8_t *census = nullptr;
+	size_t census_bytes = 0;
+	hipEvent_t ev_census_start = nullptr, ev_census_stop = nullptr;
 };
 
 namespace
@@ -76,6 +83,9 @@ void free_arrays(ca3d_ensemble *e)
 	e->sheet_counters = nullptr;
 	e->sheet_px = 0;
 	e->sheet_drawn = false;
+	if (e->census) hipFree(e->census);
+	e->census = nullptr;
+	e->census_bytes = 0;
 	e->n = 0;
 	e->timed = false;
 }
@@ -366,6 +376,30 @@ int size_sheet_targets(ca3d_ensemble *e, size_t px)
 	return CA3D_OK;
 }
 
+// room for a census result of `bytes` bytes; a failure leaves the handle with what it had
+int size_census(ca3d_ensemble *e, size_t bytes)
+{
+	if (!e->ev_census_start) HIP_TRY(hipEventCreate(&e->ev_census_start));
+	if (!e->ev_census_stop) HIP_TRY(hipEventCreate(&e->ev_census_stop));
+	if (bytes <= e->census_bytes) return CA3D_OK;
+	// the new array first: a failure leaves the handle as it was
+	uint8_t *grown = nullptr;
+	hipError_t err = hipMalloc((void **)&grown, bytes);
+	if (err != hipSuccess)
+	{
+		(void)hipGetLastError();
+		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating a census of %zu bytes: %s", bytes, hipGetErrorString(err));
+	}
+	if (e->census)
+	{
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		hipFree(e->census);
+	}
+	e->census = grown;
+	e->census_bytes = bytes;
+	return CA3D_OK;
+}
+
 } // namespace
 
 extern "C"
@@ -412,6 +446,8 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	if (e->ev_seed) hipEventDestroy(e->ev_seed);
 	if (e->ev_sheet_start) hipEventDestroy(e->ev_sheet_start);
 	if (e->ev_sheet_stop) hipEventDestroy(e->ev_sheet_stop);
+	if (e->ev_census_start) hipEventDestroy(e->ev_census_start);
+	if (e->ev_census_stop) hipEventDestroy(e->ev_census_stop);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
 	return CA3D_OK;
@@ -785,6 +821,39 @@ int ca3d_ensemble_get_sheet_stats(ca3d_ensemble_t *e, ca3d_render_stats *out) CA
 	out->shadow_rays = c[0];
 	out->primary_cell_visits = c[1];
 	out->shadow_cell_visits = c[2];
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_census(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t max_components, ca3d_component *out, uint32_t *n_components,
+                         uint32_t *remaining, float *gpu_ms) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!out || !n_components || !remaining) return fail(CA3D_ERR_INVALID_ARGUMENT, "out, n_components or remaining is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if (max_components == 0 || max_components > kCensusMaxComponents)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "max_components %u: a census lists 1 to %u components a universe", max_components, kCensusMaxComponents);
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t rec_bytes = (size_t)count * max_components * sizeof(ca3d_component), word_bytes = (size_t)count * sizeof(uint32_t);
+	if ((rc = size_census(e, rec_bytes + 2u * word_bytes))) return rc;
+	CensusLaunch l{};
+	l.state = e->state;
+	l.first = first; l.count = count;
+	l.max_components = max_components;
+	l.out = reinterpret_cast<ca3d_component *>(e->census);
+	l.n_components = reinterpret_cast<uint32_t *>(e->census + rec_bytes);
+	l.remaining = l.n_components + count;
+	HIP_TRY(hipEventRecord(e->ev_census_start, e->stream));
+	HIP_TRY(launch_census(l, e->stream));
+	HIP_TRY(hipEventRecord(e->ev_census_stop, e->stream));
+	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipMemcpyAsync(n_components, l.n_components, word_bytes, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipMemcpyAsync(remaining, l.remaining, word_bytes, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->ev_census_start, e->ev_census_stop));
 	return CA3D_OK;
 }
 CA3D_API_CATCH

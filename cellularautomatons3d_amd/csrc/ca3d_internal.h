@@ -228,6 +228,18 @@ constexpr uint32_t ensemble_rule_words(int neighbourhood, bool clustered = false
 {
 	return clustered ? 6u : neighbourhood == CA3D_ENSEMBLE_MOORE ? 2u : 1u;
 }
+// ca_census.hip: the connected components of universes [first, first + count) of an ensemble's state array (ca3d_ensemble_census), one
+// workgroup of ca_ensemble_census64 each; out, n_components and remaining are indexed by universe - first. The caller has checked the range.
+constexpr uint32_t kCensusMaxComponents = 1024;
+struct CensusLaunch
+{
+	const uint32_t *state; // [B][8192], the ensemble's current states
+	uint32_t first, count;
+	uint32_t max_components; // 1 .. kCensusMaxComponents
+	ca3d_component *out;     // device, [count][max_components]: every slot is written
+	uint32_t *n_components, *remaining; // device, [count]
+};
+hipError_t launch_census(const CensusLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

@@ -206,6 +206,26 @@ class Ensemble:
         _capi.check(self._lib.ca3d_ensemble_summarize(self._h, first, count, recs))
         return [_summary(r, None) for r in recs]
 
+    def census(self, first: int = 0, count: Optional[int] = None, max_components: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`ca3d_ensemble_census`: the connected objects (26-neighbourhood inside the closed cube) of universes first .. first + count - 1
+        (default: all from `first`), found on the device in one launch behind the queued steps
+        -> (components [count, max_components] of `host.COMPONENT_DTYPE`, n_components u32[count], remaining u32[count]).
+        Components come in the order of their first cells; slots past n_components[u] are zero; remaining[u] counts the live cells in no
+        listed component (0: the list is complete). `host.census` is the same on the CPU, `host.unpack_box` opens box_min / box_max.
+        The call only reads; `census_gpu_ms()` tells what the launch took."""
+        count = self.n - first if count is None else count
+        comps = np.zeros((max(count, 0), max(max_components, 0)), dtype=host.COMPONENT_DTYPE)
+        n, rest = (np.zeros(max(count, 0), dtype=np.uint32) for _ in range(2))
+        ms = C.c_float(0.0)
+        _capi.check(self._lib.ca3d_ensemble_census(self._h, first, count, max_components, comps.ctypes.data_as(C.POINTER(_capi.ComponentStruct)),
+                                                   n.ctypes.data_as(_u32p), rest.ctypes.data_as(_u32p), C.byref(ms)))
+        self._census_ms = float(ms.value)
+        return comps, n, rest
+
+    def census_gpu_ms(self) -> float:
+        """hipEvent time of the last `census` launch of this object, in milliseconds (None before the first)."""
+        return getattr(self, "_census_ms", None)
+
     def render_sheet(self, uniforms, tile_w: int, tile_h: int, columns: Optional[int] = None, spp: int = 1, first: int = 0,
                      count: Optional[int] = None, light: bool = False, depth: bool = False):
         """`ca3d_ensemble_render_sheet`: universes first .. first + count - 1 (default: all from `first`) as the tiles of one contact

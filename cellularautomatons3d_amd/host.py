@@ -412,6 +412,83 @@ def moved_by(grid_size: int, a_words, b_words) -> Optional[Tuple[int, int, int]]
     return d if np.array_equal(box(a_words, sa), box(b_words, sb)) else None
 
 
+# ------------------------------------------------------------------------------------------------- census
+# The definition of ca3d_ensemble_census (include/ca3d.h) in executable form: the connected objects of one 64^3 universe.
+
+#: ca3d_component (include/ca3d.h), 32 bytes
+COMPONENT_DTYPE = np.dtype([("population", "<u4"), ("first_cell", "<u4"), ("box_min", "<u4"), ("box_max", "<u4"), ("digest", "<u8"),
+                            ("reserved", "<u4", (2,))])
+
+
+def unpack_box(word: int) -> Tuple[int, int, int]:
+    """(x, y, z) of a packed box corner x | y << 8 | z << 16 (`ca3d_component.box_min` / `box_max`)."""
+    word = int(word)
+    return word & 0xFF, (word >> 8) & 0xFF, (word >> 16) & 0xFF
+
+
+def _dilate_closed(f: np.ndarray) -> np.ndarray:
+    """The 3 x 3 x 3 dilation of a boolean cube [z, y, x] inside the cube: nothing crosses a face."""
+    for axis in range(3):
+        g = f.copy()
+        lo = [slice(None)] * 3
+        hi = [slice(None)] * 3
+        lo[axis], hi[axis] = slice(0, -1), slice(1, None)
+        g[tuple(hi)] |= f[tuple(lo)]
+        g[tuple(lo)] |= f[tuple(hi)]
+        f = g
+    return f
+
+
+def census(words, max_components: int = 64) -> Tuple[np.ndarray, int, int]:
+    """`ca3d_ensemble_census` for ONE packed 64^3 universe, in plain numpy: the connected components of its live cells under the
+    26-neighbourhood inside the closed cube (no face wraps), ordered by their first cells (smallest x + 64 y + 4096 z)
+    -> (components [max_components] of COMPONENT_DTYPE, n_components, remaining). The first min(C, max_components) components are
+    listed, the slots behind them are zero, `remaining` is the number of live cells in no listed component. A component's digest is
+    `state_summary(64, translated)["digest"]` of the state that holds only it, translated by -box_min."""
+    G = 64
+    if not 1 <= int(max_components) <= 1024:
+        raise ValueError("max_components is 1 .. 1024")
+    w = np.ascontiguousarray(words, dtype="<u4").ravel()
+    if w.size != words_per_buffer(G):
+        raise ValueError("a universe holds 8192 words")
+    rest = np.unpackbits(w.view(np.uint8), bitorder="little").reshape(G, G, G).astype(bool)  # [z, y, x]: the flat index is x + 64 y + 4096 z
+    out = np.zeros(int(max_components), dtype=COMPONENT_DTYPE)
+    n = 0
+    while n < max_components:
+        live = np.flatnonzero(rest.ravel())
+        if live.size == 0:
+            break
+        first = int(live[0])
+        z, y, x = first >> 12, (first >> 6) & 63, first & 63
+        z0, z1, y0, y1, x0, x1 = z, z + 1, y, y + 1, x, x + 1  # the fill works in a window that grows with the component
+        f = np.zeros((G, G, G), dtype=bool)
+        f[z, y, x] = True
+        size = 1
+        while True:
+            z0, y0, x0 = max(z0 - 1, 0), max(y0 - 1, 0), max(x0 - 1, 0)
+            z1, y1, x1 = min(z1 + 1, G), min(y1 + 1, G), min(x1 + 1, G)
+            win = (slice(z0, z1), slice(y0, y1), slice(x0, x1))
+            f[win] = _dilate_closed(f[win]) & rest[win]
+            grown = int(np.count_nonzero(f[win]))
+            if grown == size:
+                break
+            size = grown
+        zs, ys, xs = np.nonzero(f)
+        bz, by, bx = int(zs.min()), int(ys.min()), int(xs.min())
+        moved = np.zeros((G, G, G), dtype=np.uint8)
+        moved[zs - bz, ys - by, xs - bx] = 1
+        translated = np.packbits(moved.ravel(), bitorder="little").view("<u4")
+        rec = out[n]
+        rec["population"] = zs.size
+        rec["first_cell"] = first
+        rec["box_min"] = bx | by << 8 | bz << 16
+        rec["box_max"] = int(xs.max()) | int(ys.max()) << 8 | int(zs.max()) << 16
+        rec["digest"] = state_summary(G, translated)["digest"]
+        rest &= ~f
+        n += 1
+    return out, n, int(np.count_nonzero(rest))
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

@@ -1281,6 +1281,37 @@ static napi_value js_ensemble_summaries(napi_env env, napi_callback_info info)
 	return out;
 }
 
+/* ensembleCensus(handle, first, count, maxComponents, Uint32Array(count * maxComponents * 8) records, Uint32Array(count) nComponents,
+ *                Uint32Array(count) remaining) -> gpuMs: the connected objects of universes [first, first + count) (ca3d_ensemble_census);
+ * a record is ca3d_component's eight words: population, firstCell, boxMin, boxMax, digest low, digest high, 0, 0 (js/ca3d.js opens them) */
+static napi_value js_ensemble_census(napi_env env, napi_callback_info info)
+{
+	napi_value argv[7];
+	if (!get_args(env, info, 7, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, count, max_components;
+	void *recs, *n, *rest;
+	size_t nrecs, nn, nrest;
+	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count) || !get_u32(env, argv[3], &max_components) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 0, &recs, &nrecs) || !get_typed(env, argv[5], napi_uint32_array, 0, &n, &nn) ||
+	    !get_typed(env, argv[6], napi_uint32_array, 0, &rest, &nrest))
+		return NULL;
+	/* sizes the library refuses anyway leave nothing to check the arrays against: it names the reason */
+	const int sizable = count && max_components && max_components <= 1024u;
+	if (sizable && (nrecs != (size_t)count * max_components * 8u || nn != count || nrest != count))
+	{
+		napi_throw_range_error(env, NULL, "records must hold count * maxComponents * 8 words, nComponents and remaining one entry per universe");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_component) == 32, "a record crosses as eight words");
+	float ms = 0.f;
+	int rc = ca3d_ensemble_census(e, first, count, max_components, (ca3d_component *)recs, (uint32_t *)n, (uint32_t *)rest, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1502,7 +1533,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleConfigureNeighbourhood", js_ensemble_configure_neighbourhood}, {"ensembleNeighbourhood", js_ensemble_neighbourhood},
 	    {"ensembleConfigureClustered", js_ensemble_configure_clustered}, {"ensembleClustered", js_ensemble_clustered},
 	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables},
-	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats}};
+	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats},
+	    {"ensembleCensus", js_ensemble_census}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

@@ -533,6 +533,36 @@ class Ensemble
 	}
 	/** the universes' records, as Engine.summary() objects without planePopulation */
 	summaries(first, count) { first = first || 0; return this._a.ensembleSummaries(this._e, first, count === undefined ? this.n - first : count); }
+	/** The census (ca3d_ensemble_census): the connected objects — 26-neighbourhood inside the closed cube, no face wraps — of universes
+	 *  first .. first + count - 1 (default: all from `first`), found on the device in one launch behind the queued steps
+	 *  -> {components, nComponents: Uint32Array(count), remaining: Uint32Array(count), gpuMs}. components[k] lists universe first + k's
+	 *  first min(C, maxComponents) objects in the order of their first cells, each {population, firstCell (x + 64 y + 4096 z), boxMin
+	 *  [x, y, z], boxMax, digest (BigInt: the state digest of the object translated to the origin)}; remaining[k]: live cells in no
+	 *  listed object, 0 when the list is complete. maxComponents: 1 .. 1024, default 64. The call only reads. */
+	census(first, count, maxComponents)
+	{
+		first = first || 0;
+		count = count === undefined ? this.n - first : count;
+		maxComponents = maxComponents === undefined ? 64 : maxComponents;
+		// (a size the library refuses gets no arrays: it names the reason)
+		const sizable = count > 0 && maxComponents >= 1 && maxComponents <= 1024;
+		const words = new Uint32Array(sizable ? count * maxComponents * 8 : 0);
+		const nComponents = new Uint32Array(sizable ? count : 0), remaining = new Uint32Array(sizable ? count : 0);
+		const gpuMs = this._a.ensembleCensus(this._e, first, count, maxComponents, words, nComponents, remaining);
+		const box = (w) => [w & 0xFF, (w >>> 8) & 0xFF, (w >>> 16) & 0xFF];
+		const components = [];
+		for (let k = 0; k < count; k++)
+		{
+			const list = [];
+			for (let i = 0; i < nComponents[k]; i++)
+			{
+				const r = words.subarray((k * maxComponents + i) * 8, (k * maxComponents + i) * 8 + 8);
+				list.push({ population: r[0], firstCell: r[1], boxMin: box(r[2]), boxMax: box(r[3]), digest: BigInt(r[5]) << 32n | BigInt(r[4]) });
+			}
+			components.push(list);
+		}
+		return { components, nComponents, remaining, gpuMs };
+	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at
 	 *  64^3 with "render_skip" 0, bit for bit. `uniforms`: Float32Array(128) filled for a tileW x tileH window, one block for every tile;

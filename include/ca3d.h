@@ -483,6 +483,47 @@ int ca3d_ensemble_step_until_moving(ca3d_ensemble_t *e, uint32_t max_steps, uint
 int ca3d_ensemble_step_until_trace(ca3d_ensemble_t *e, uint32_t max_steps, uint32_t check_every, uint32_t stop_mask, uint32_t *steps_done,
                                    uint32_t *reason, uint32_t *samples, uint32_t samples_per_universe, uint32_t *n_samples);
 int ca3d_ensemble_summarize(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_summary *out);
+/*
+ * The census (no reference counterpart): the connected OBJECTS of universes first .. first + count - 1, one by one — a soup's ash as a
+ * list — found by one launch of ca_ensemble_census64 (csrc/ca_census.hip, one workgroup a universe, bit-parallel flood fills in
+ * registers) behind whatever is queued on the ensemble's stream. Nothing state-sized leaves the device. host.census restates it.
+ *
+ * The definition.
+ *   Cells and adjacency: the cells are the live bits of the universe's current state. Two live cells are adjacent when they differ by
+ *     at most 1 on every axis (the 26-neighbourhood) INSIDE THE CUBE. The census treats the universe as a CLOSED BOX: no face wraps, on
+ *     any axis. (The dynamics' + faces wrap and their - faces are dead; that relation is not symmetric and cannot define objects.)
+ *   Components and order: a component is a maximal set of cells connected through adjacent cells. A component's first cell is its
+ *     cell with the smallest x + 64 y + 4096 z (the bit order of the packed state); components are ordered by their first cells.
+ *   With C the number of components: n_components[u] = min(C, max_components); out[u][0 .. n_components[u]) holds the first
+ *     components in that order and every slot behind them is zero in every byte; remaining[u] is the number of live cells in no
+ *     listed component — 0 exactly when the list is complete. max_components is 1 .. 1024.
+ *   The record: population (cells), first_cell (x + 64 y + 4096 z), box_min and box_max (the bounding box, inclusive, each packed
+ *     x | y << 8 | z << 16), digest, reserved (zero).
+ *   The digest is the `digest` of ca3d_summary for the 64^3 state that holds only this component translated by -box_min
+ *     (host.state_summary(64, translated)["digest"]): equal shapes have equal digests wherever they lie. It is not invariant under
+ *     rotation, reflection or an oscillator's phase.
+ *
+ * The call only reads: states, records, step counters, anchors and steps_done are unchanged, and a later step call behaves as if the
+ * census had not happened. It needs no rules. It waits for its own result, as ca3d_ensemble_summarize does. gpu_ms (nullable) receives
+ * the hipEvent time around the launch. The result is staged in device arrays on the handle (count x max_components records and 2 x
+ * count words, grown when a call needs more — the new array is allocated before the old one is freed, so CA3D_ERR_OUT_OF_MEMORY leaves
+ * the handle as it was — freed by a configure and by destroy).
+ *
+ * Errors: NULL handle, out, n_components or remaining — CA3D_ERR_INVALID_ARGUMENT without touching a device; not configured —
+ * CA3D_ERR_NOT_CONFIGURED; count == 0, first + count > n, max_components outside 1 .. 1024 — CA3D_ERR_INVALID_ARGUMENT; a universe
+ * of the range without a state — CA3D_ERR_NOT_CONFIGURED, the message names the first such universe. A refused call touches none of
+ * the caller's arrays.
+ */
+typedef struct ca3d_component
+{
+	uint32_t population;
+	uint32_t first_cell;       /* x + 64 y + 4096 z of the component's lowest cell */
+	uint32_t box_min, box_max; /* x | y << 8 | z << 16, inclusive */
+	uint64_t digest;           /* of the component translated by -box_min */
+	uint32_t reserved[2];      /* zero */
+} ca3d_component;              /* 32 bytes */
+int ca3d_ensemble_census(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t max_components, ca3d_component *out /* [count][max_components] */,
+                         uint32_t *n_components /* [count] */, uint32_t *remaining /* [count] */, float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

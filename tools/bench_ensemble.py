@@ -50,6 +50,17 @@ camera host.orbit_camera(), tiles 64 x 64 and 128 x 128 at 1 and 4 samples. Befo
 and of the host clock around a call that reads the presentation sheet back, and of the host clock around the loop. No ratio is
 required. Written to profiles/ensemble_sheet_64.json unless --out says otherwise.
 
+--census measures the census (ca3d_ensemble_census, kernel ca_ensemble_census64: every universe's connected objects listed in one
+launch) against the path that exists without it: read_state of the same universes plus labelling on the CPU (scipy.ndimage.label with a
+full 3 x 3 x 3 structure when scipy can be imported, else host.census; the profile says which). B = 256 and 1024 universes of ash —
+seed_states (seeds 1 .. B), then step_until_cycle(512) under Moore B5-7 / S4-6 (and_rounds 2) and under Moore B6 / S5-7 (and_rounds 1),
+what a soup search would census — and of two synthetic states in every universe: host.seeded_state(64, 0xCA3D0009, 8) (509 objects of
+518 cells) and host.seeded_state(64, 77, 2, box 20 .. 43) (190 objects, one of 1 306 cells); max_components 1024. Before timing, the
+census must equal the CPU path's components (population, first cell, box, order) in every universe and host.census byte for byte,
+digests included, in sampled ones. Reported: medians of --repeats measurements of the census' hipEvent time and of the host clock around
+the call, of read_state alone, and of read_state + labelling. No ratio is required. Written to profiles/ensemble_census_64.json unless
+--out says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -326,6 +337,99 @@ def sheet_rows(args):
     return rows
 
 
+CENSUS_ASH = {"ash B5-7/S4-6": ("5-7", "4-6", 2), "ash B6/S5-7": ("6", "5-7", 1)}  # born, survive, and_rounds of the seed
+CENSUS_SYNTHETIC = {"sparse (509 objects, 518 cells)": (G, 0xCA3D0009, 8), "giant (190 objects, one of 1306 cells)": (G, 77, 2, ((20, 20, 20), (43, 43, 43)))}
+
+
+def census_rows(args):
+    """census against read_state + labelling on the CPU: one row per (workload, B). -> (rows, the labeller's name)"""
+    try:
+        from scipy import ndimage
+        labeller = "scipy.ndimage.label, full 3 x 3 x 3 structure"
+    except ImportError:
+        ndimage, labeller = None, "host.census"
+    full = np.ones((3, 3, 3), dtype=int)
+    M = 1024
+
+    def cells_of(words):
+        return np.unpackbits(words.view(np.uint8), bitorder="little").reshape(G, G, G)
+
+    def label_only(states):
+        for w in states:
+            if ndimage is not None:
+                ndimage.label(cells_of(w), structure=full)
+            else:
+                host.census(w, M)
+
+    def by_label(w):
+        """(first_cell, population, box_min, box_max) of every component, in the census' order."""
+        if ndimage is None:
+            c, n, _ = host.census(w, M)
+            return [(int(r["first_cell"]), int(r["population"]), int(r["box_min"]), int(r["box_max"])) for r in c[:n]]
+        lab, n = ndimage.label(cells_of(w), structure=full)
+        flat = lab.ravel()
+        live = np.flatnonzero(flat)
+        firsts = np.full(n + 1, 1 << 30, dtype=np.int64)
+        np.minimum.at(firsts, flat[live], live)
+        pops = np.bincount(flat, minlength=n + 1)
+        out = []
+        for k, sl in enumerate(ndimage.find_objects(lab), start=1):
+            out.append((int(firsts[k]), int(pops[k]), sl[2].start | sl[1].start << 8 | sl[0].start << 16,
+                        (sl[2].stop - 1) | (sl[1].stop - 1) << 8 | (sl[0].stop - 1) << 16))
+        return sorted(out)
+
+    ens = Ensemble(0)
+    rows = []
+    for B in args.universes:
+        for name in list(CENSUS_ASH) + list(CENSUS_SYNTHETIC):
+            ens.configure(B, neighbourhood="moore")
+            steps = None
+            if name in CENSUS_ASH:
+                born, survive, rounds = CENSUS_ASH[name]
+                ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+                ens.seed_states(0, np.arange(1, B + 1), rounds)
+                done, reason, _ = ens.step_until_cycle(512)
+                steps = {"max_steps": 512, "stopped": int(np.count_nonzero(reason)), "median_steps_done": float(np.median(done))}
+            else:
+                ens.upload_state(0, np.broadcast_to(host.seeded_state(*CENSUS_SYNTHETIC[name]), (B, W)))
+            states = ens.read_state()
+            comps, n, rest = ens.census(max_components=M)
+            for u in range(B):
+                want = by_label(states[u])
+                got = [(int(r["first_cell"]), int(r["population"]), int(r["box_min"]), int(r["box_max"])) for r in comps[u, :n[u]]]
+                if got != want[:M] or int(rest[u]) != sum(w[1] for w in want[M:]):
+                    raise SystemExit(f"{name}, B {B}: the census of universe {u} is not the CPU labelling's")
+            sample = sorted({0, B // 2, B - 1})
+            for u in sample:
+                c, k, r = host.census(states[u], M)
+                if c.tobytes() != comps[u].tobytes() or (k, r) != (int(n[u]), int(rest[u])):
+                    raise SystemExit(f"{name}, B {B}: the census of universe {u} is not host.census'")
+            gpu, wall, read, cpu = [], [], [], []
+            for _ in range(args.repeats):
+                t0 = time.perf_counter()
+                ens.census(max_components=M)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                gpu.append(ens.census_gpu_ms())
+                t0 = time.perf_counter()
+                got = ens.read_state()
+                read.append((time.perf_counter() - t0) * 1e3)
+                label_only(got)
+                cpu.append((time.perf_counter() - t0) * 1e3)
+            row = {"workload": name, "universes": B, "max_components": M, "stepping": steps,
+                   "components_per_universe": {"min": int(n.min()), "median": float(np.median(n)), "max": int(n.max())},
+                   "live_cells_per_universe_median": float(np.median(comps["population"].sum(axis=1) + rest)),
+                   "complete_universes": int(np.count_nonzero(rest == 0)), "universes_verified": B, "digests_verified_in": sample,
+                   "census_gpu_ms": statistics.median(gpu), "census_gpu_ms_all": gpu,
+                   "census_wall_ms": statistics.median(wall), "census_wall_ms_all": wall,
+                   "read_state_wall_ms": statistics.median(read), "read_state_wall_ms_all": read,
+                   "read_state_and_label_wall_ms": statistics.median(cpu), "read_state_and_label_wall_ms_all": cpu,
+                   "cpu_path_over_census_wall": statistics.median(cpu) / statistics.median(wall)}
+            rows.append(row)
+            print(json.dumps(row))
+    ens.close()
+    return rows, labeller
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -339,10 +443,11 @@ def main():
     ap.add_argument("--moving", action="store_true", help="measure step_until_moving against step_until_cycle instead (von Neumann, Moore, clustered; default B = 256 1024)")
     ap.add_argument("--trace", action="store_true", help="measure step_trace against the step + summaries loop and plain stepping instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--sheet", action="store_true", help="measure render_sheet against the upload + render loop instead (B = 256 1024)")
+    ap.add_argument("--census", action="store_true", help="measure census against read_state + labelling on the CPU instead (B = 256 1024)")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256, 1024] if args.cycle or args.trace or args.moving or args.sheet else [1, 256, 1024, 4096]
+        args.universes = [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -358,6 +463,25 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.census:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_census_64.json")
+        rows, labeller = census_rows(args)
+        result = {
+            "what": "B universes of 64^3: Ensemble.census(max_components 1024) — one launch of ca_ensemble_census64, the records copied to the host — vs. the path "
+                    "that exists without it, read_state of the same universes + labelling their connected components on the CPU (the labelling alone: no "
+                    "populations, boxes or digests are derived in the timed loop). Ash: seed_states (seeds 1 .. B), then step_until_cycle(512)",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"census": "ca_ensemble_census64"}, "cpu_labelling": labeller,
+            "timing": f"census_gpu_ms: hipEvent time around the launch; *_wall_ms: host clock around the call(s); medians of {args.repeats} alternating measurements "
+                      "after the census equalled the CPU labelling in every universe (population, first cell, box, order) and host.census byte for byte in sampled ones",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.sheet:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_sheet_64.json")
         result = {
