@@ -63,6 +63,21 @@ class ComponentStruct(C.Structure):
     ]
 
 
+class IsolateJobStruct(C.Structure):
+    """ca3d_isolate_job (include/ca3d.h): a source universe and a cell x + 64 y + 4096 z of the object to isolate."""
+    _fields_ = [("universe", C.c_uint32), ("cell", C.c_uint32)]
+
+
+class IsolatedStruct(C.Structure):
+    """ca3d_isolated (include/ca3d.h): what `ca3d_ensemble_isolate` says of one job, 16 bytes."""
+    _fields_ = [("population", C.c_uint32), ("shift", C.c_int32 * 3)]
+
+
+#: placement of `ca3d_ensemble_isolate` (the low byte of its flags), and its one flag bit
+ISOLATE_PLACEMENTS = {"keep": 0, "centre": 1, "origin": 2}
+ISOLATE_COPY_RULES = 0x100
+
+
 class SeedStruct(C.Structure):
     """ca3d_seed (include/ca3d.h)."""
     _fields_ = [("seed", C.c_uint32), ("and_rounds", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
@@ -163,6 +178,8 @@ SYMBOLS = [
     ("ca3d_ensemble_step_until_trace", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32, _u32p]),
     ("ca3d_ensemble_summarize", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(SummaryStruct)]),
     ("ca3d_ensemble_census", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ComponentStruct), _u32p, _u32p, C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_isolate", C.c_int, [_H, C.c_uint32, _H, C.c_uint32, C.POINTER(IsolateJobStruct), C.c_uint32, C.POINTER(IsolatedStruct),
+                                        C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -6,6 +6,7 @@
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
 // ca3d_ensemble_render_sheet draws a range of universes as the tiles of one contact sheet (render_sheet.hip).
 // ca3d_ensemble_census lists the connected objects of a range of universes (ca_census.hip).
+// ca3d_ensemble_isolate makes objects a census named the only thing in universes of their own (ca_isolate.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -61,6 +62,12 @@ struct ca3d_ensemble
 	uint8_t *census = nullptr;
 	size_t census_bytes = 0;
 	hipEvent_t ev_census_start = nullptr, ev_census_stop = nullptr;
+	// ca3d_ensemble_isolate, on the DESTINATION handle: the results of the call under way, [n_jobs] of 16 bytes, then its jobs, [n_jobs]
+	// of 8 bytes, in one device array of isolate_bytes bytes, grown when a call needs more, gone with the other arrays at a configure;
+	// its event pair and the event that orders the launch behind the source's stream (created at the first call)
+	uint8_t *isolate = nullptr;
+	size_t isolate_bytes = 0;
+	hipEvent_t ev_isolate_start = nullptr, ev_isolate_stop = nullptr, ev_isolate_src = nullptr;
 };
 
 namespace
@@ -86,6 +93,9 @@ void free_arrays(ca3d_ensemble *e)
 	if (e->census) hipFree(e->census);
 	e->census = nullptr;
 	e->census_bytes = 0;
+	if (e->isolate) hipFree(e->isolate);
+	e->isolate = nullptr;
+	e->isolate_bytes = 0;
 	e->n = 0;
 	e->timed = false;
 }
@@ -400,6 +410,31 @@ int size_census(ca3d_ensemble *e, size_t bytes)
 	return CA3D_OK;
 }
 
+// room for the jobs and results of an isolate call, `bytes` bytes; a failure leaves the handle with what it had
+int size_isolate(ca3d_ensemble *e, size_t bytes)
+{
+	if (!e->ev_isolate_start) HIP_TRY(hipEventCreate(&e->ev_isolate_start));
+	if (!e->ev_isolate_stop) HIP_TRY(hipEventCreate(&e->ev_isolate_stop));
+	if (!e->ev_isolate_src) HIP_TRY(hipEventCreateWithFlags(&e->ev_isolate_src, hipEventDisableTiming));
+	if (bytes <= e->isolate_bytes) return CA3D_OK;
+	// the new array first: a failure leaves the handle as it was
+	uint8_t *grown = nullptr;
+	hipError_t err = hipMalloc((void **)&grown, bytes);
+	if (err != hipSuccess)
+	{
+		(void)hipGetLastError();
+		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating %zu bytes of isolate jobs: %s", bytes, hipGetErrorString(err));
+	}
+	if (e->isolate)
+	{
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		hipFree(e->isolate);
+	}
+	e->isolate = grown;
+	e->isolate_bytes = bytes;
+	return CA3D_OK;
+}
+
 } // namespace
 
 extern "C"
@@ -448,6 +483,9 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	if (e->ev_sheet_stop) hipEventDestroy(e->ev_sheet_stop);
 	if (e->ev_census_start) hipEventDestroy(e->ev_census_start);
 	if (e->ev_census_stop) hipEventDestroy(e->ev_census_stop);
+	if (e->ev_isolate_start) hipEventDestroy(e->ev_isolate_start);
+	if (e->ev_isolate_stop) hipEventDestroy(e->ev_isolate_stop);
+	if (e->ev_isolate_src) hipEventDestroy(e->ev_isolate_src);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
 	return CA3D_OK;
@@ -854,6 +892,74 @@ int ca3d_ensemble_census(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uin
 	HIP_TRY(hipMemcpyAsync(remaining, l.remaining, word_bytes, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->ev_census_start, e->ev_census_stop));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_isolate(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensemble_t *src, uint32_t n_jobs, const ca3d_isolate_job *jobs, uint32_t flags,
+                          ca3d_isolated *out, float *gpu_ms) CA3D_API_TRY
+{
+	if (!dst || !src) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!jobs) return fail(CA3D_ERR_INVALID_ARGUMENT, "jobs is NULL");
+	if (!dst->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called for the destination ensemble");
+	if (!src->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called for the source ensemble");
+	if (n_jobs == 0 || dst_first >= dst->n || n_jobs > dst->n - dst_first)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "%u jobs into universes [%u, %u + %u) of %u", n_jobs, dst_first, dst_first, n_jobs, dst->n);
+	const uint32_t placement = flags & 0xFFu;
+	const bool copy_rules = (flags & CA3D_ISOLATE_COPY_RULES) != 0u;
+	if (placement > CA3D_ISOLATE_ORIGIN) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown placement %u (CA3D_ISOLATE_KEEP = 0, CA3D_ISOLATE_CENTRE = 1, CA3D_ISOLATE_ORIGIN = 2)", placement);
+	if (flags & ~(0xFFu | CA3D_ISOLATE_COPY_RULES)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in flags %#x", flags);
+	if (src->device != dst->device) return fail(CA3D_ERR_INVALID_ARGUMENT, "the source ensemble is on device %d, the destination on device %d", src->device, dst->device);
+	if (copy_rules && (src->neighbourhood != dst->neighbourhood || src->clustered != dst->clustered))
+		return fail(CA3D_ERR_UNSUPPORTED, "CA3D_ISOLATE_COPY_RULES: source and destination ensemble differ in neighbourhood or in being clustered (%u and %u rule words a universe)",
+		            rule_words(src), rule_words(dst));
+	for (uint32_t k = 0; k < n_jobs; k++)
+	{
+		const uint32_t u = jobs[k].universe;
+		if (u >= src->n) return fail(CA3D_ERR_INVALID_ARGUMENT, "job %u: universe %u of %u", k, u, src->n);
+		if (jobs[k].cell >= 1u << 18) return fail(CA3D_ERR_INVALID_ARGUMENT, "job %u: cell %u — a cell is x + 64 y + 4096 z, below %u", k, jobs[k].cell, 1u << 18);
+		if (src == dst && u >= dst_first && u - dst_first < n_jobs)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "job %u: source universe %u lies among the destinations [%u, %u + %u) of the same ensemble", k, u, dst_first, dst_first, n_jobs);
+		if (!src->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "job %u: ca3d_ensemble_upload_state has not been called for source universe %u", k, u);
+		if (copy_rules && !src->has_rules[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "job %u: ca3d_ensemble_set_rules has not been called for source universe %u", k, u);
+	}
+	HIP_TRY(hipSetDevice(dst->device));
+	const size_t out_bytes = (size_t)n_jobs * sizeof(ca3d_isolated), job_bytes = (size_t)n_jobs * sizeof(ca3d_isolate_job);
+	int rc = size_isolate(dst, out_bytes + job_bytes);
+	if (rc) return rc;
+	IsolateLaunch l{};
+	l.src_state = src->state;
+	l.dst_state = dst->state; l.dst_prev = dst->prev;
+	l.src_rules = src->rules; l.dst_rules = dst->rules;
+	l.out = reinterpret_cast<ca3d_isolated *>(dst->isolate);
+	l.jobs = reinterpret_cast<const ca3d_isolate_job *>(dst->isolate + out_bytes);
+	l.dst_first = dst_first; l.n_jobs = n_jobs;
+	l.placement = placement;
+	l.rule_words = copy_rules ? rule_words(dst) : 0u;
+	if (src != dst)
+	{
+		// behind what is queued on the source's stream now
+		HIP_TRY(hipEventRecord(dst->ev_isolate_src, src->stream));
+		HIP_TRY(hipStreamWaitEvent(dst->stream, dst->ev_isolate_src, 0));
+	}
+	HIP_TRY(hipMemcpyAsync(dst->isolate + out_bytes, jobs, job_bytes, hipMemcpyHostToDevice, dst->stream));
+	HIP_TRY(hipEventRecord(dst->ev_isolate_start, dst->stream));
+	HIP_TRY(launch_isolate(l, dst->stream));
+	HIP_TRY(hipEventRecord(dst->ev_isolate_stop, dst->stream));
+	// the records of the new states: step 0, no previous state (the launch ca3d_ensemble_upload_state ends in)
+	EnsembleLaunch r = launch_of(dst);
+	r.first = dst_first; r.count = n_jobs;
+	r.reset = true;
+	r.final = true;
+	HIP_TRY(launch_ensemble(r, dst->stream));
+	if (out) HIP_TRY(hipMemcpyAsync(out, l.out, out_bytes, hipMemcpyDeviceToHost, dst->stream));
+	HIP_TRY(hipStreamSynchronize(dst->stream)); // the caller's jobs are consumed, and the source may go on
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, dst->ev_isolate_start, dst->ev_isolate_stop));
+	for (uint32_t u = dst_first; u < dst_first + n_jobs; u++)
+	{
+		if (!dst->has_state[u]) { dst->has_state[u] = 1; dst->missing_state--; }
+		if (copy_rules && !dst->has_rules[u]) { dst->has_rules[u] = 1; dst->missing_rules--; }
+	}
 	return CA3D_OK;
 }
 CA3D_API_CATCH

@@ -240,6 +240,22 @@ struct CensusLaunch
 	uint32_t *n_components, *remaining; // device, [count]
 };
 hipError_t launch_census(const CensusLaunch &l, hipStream_t stream);
+// ca_isolate.hip: job k makes the connected component of source universe jobs[k].universe that holds jobs[k].cell the only thing in
+// destination universe dst_first + k (ca3d_ensemble_isolate), translated as `placement` says, in both buffers; one workgroup of
+// ca_ensemble_isolate64 a job. The caller has checked every universe, cell and range, and that no source universe is a destination.
+struct IsolateLaunch
+{
+	const uint32_t *src_state;      // [Bs][8192], the source ensemble's current states
+	uint32_t *dst_state, *dst_prev; // [Bd][8192], the destination ensemble's two buffers
+	const uint32_t *src_rules;      // [Bs][rule_words] / [Bd][rule_words]: copied universe to universe when rule_words != 0
+	uint32_t *dst_rules;
+	const ca3d_isolate_job *jobs;   // device, [n_jobs]
+	ca3d_isolated *out;             // device, [n_jobs]: every entry is written
+	uint32_t dst_first, n_jobs;
+	uint32_t placement;             // CA3D_ISOLATE_KEEP / CENTRE / ORIGIN
+	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
+};
+hipError_t launch_isolate(const IsolateLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

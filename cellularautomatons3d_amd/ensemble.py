@@ -226,6 +226,33 @@ class Ensemble:
         """hipEvent time of the last `census` launch of this object, in milliseconds (None before the first)."""
         return getattr(self, "_census_ms", None)
 
+    def isolate(self, jobs, dst_first: int = 0, src: Optional["Ensemble"] = None, placement: str = "centre",
+                copy_rules: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """`ca3d_ensemble_isolate`: universe dst_first + k of THIS ensemble becomes the connected object of universe jobs[k][0] of `src`
+        (default: this ensemble) that holds the cell jobs[k][1] (x + 64 y + 4096 z, any cell of the object — a census' first_cell
+        will do), alone, translated as `placement` says ("keep", "centre", "origin"), at step 0, found and written on the device in
+        one launch -> (population u32[n], shift i32[n, 3]). `copy_rules`: the destination universe takes its source universe's rule
+        (both ensembles of one kind). `jobs`: [n, 2]. `host.isolate` is the same on the CPU for one universe; `isolate_gpu_ms()`
+        tells what the launch took."""
+        if placement not in _capi.ISOLATE_PLACEMENTS:
+            raise ValueError(f"unknown placement {placement!r}: one of {tuple(_capi.ISOLATE_PLACEMENTS)}")
+        j = np.ascontiguousarray(_as_u32(jobs))
+        if j.ndim != 2 or j.shape[1] != 2:
+            raise ValueError("jobs is an [n, 2] array of (universe, cell)")
+        n = j.shape[0]
+        out = np.zeros((n, 4), dtype=np.int32)
+        ms = C.c_float(0.0)
+        flags = _capi.ISOLATE_PLACEMENTS[placement] | (_capi.ISOLATE_COPY_RULES if copy_rules else 0)
+        _capi.check(self._lib.ca3d_ensemble_isolate(self._h, dst_first, (self if src is None else src)._h, n,
+                                                    j.ctypes.data_as(C.POINTER(_capi.IsolateJobStruct)), flags,
+                                                    out.ctypes.data_as(C.POINTER(_capi.IsolatedStruct)), C.byref(ms)))
+        self._isolate_ms = float(ms.value)
+        return out[:, 0].astype(np.uint32), out[:, 1:].copy()
+
+    def isolate_gpu_ms(self) -> float:
+        """hipEvent time of the last `isolate` launch into this object, in milliseconds (None before the first)."""
+        return getattr(self, "_isolate_ms", None)
+
     def render_sheet(self, uniforms, tile_w: int, tile_h: int, columns: Optional[int] = None, spp: int = 1, first: int = 0,
                      count: Optional[int] = None, light: bool = False, depth: bool = False):
         """`ca3d_ensemble_render_sheet`: universes first .. first + count - 1 (default: all from `first`) as the tiles of one contact

@@ -489,6 +489,54 @@ def census(words, max_components: int = 64) -> Tuple[np.ndarray, int, int]:
     return out, n, int(np.count_nonzero(rest))
 
 
+# ------------------------------------------------------------------------------------------------- isolate
+# The definition of ca3d_ensemble_isolate (include/ca3d.h) in executable form, for one universe.
+
+ISOLATE_PLACEMENTS = ("keep", "centre", "origin")
+
+
+def isolate(words, cell: int, placement: str = "centre") -> Tuple[np.ndarray, int, Tuple[int, int, int]]:
+    """`ca3d_ensemble_isolate` for ONE packed 64^3 universe, in plain numpy: the connected component (26-neighbourhood inside the
+    closed cube, no face wraps: the census') that holds `cell` = x + 64 y + 4096 z, alone, translated by the shift of `placement` —
+    "keep": 0; "origin": -box_min; "centre": (64 - extent) // 2 - box_min per axis -> (words u32[8192], population, (dx, dy, dz)).
+    Any cell of the component selects it; a dead cell gives zeros, population 0 and a zero shift."""
+    G = 64
+    if placement not in ISOLATE_PLACEMENTS:
+        raise ValueError(f"unknown placement {placement!r}: one of {ISOLATE_PLACEMENTS}")
+    cell = int(cell)
+    if not 0 <= cell < G * G * G:
+        raise ValueError("a cell is x + 64 y + 4096 z, below 2^18")
+    w = np.ascontiguousarray(words, dtype="<u4").ravel()
+    if w.size != words_per_buffer(G):
+        raise ValueError("a universe holds 8192 words")
+    live = np.unpackbits(w.view(np.uint8), bitorder="little").reshape(G, G, G).astype(bool)  # [z, y, x]
+    z, y, x = cell >> 12, (cell >> 6) & 63, cell & 63
+    if not live[z, y, x]:
+        return np.zeros(words_per_buffer(G), dtype=np.uint32), 0, (0, 0, 0)
+    z0, z1, y0, y1, x0, x1 = z, z + 1, y, y + 1, x, x + 1  # the fill works in a window that grows with the component (census)
+    f = np.zeros((G, G, G), dtype=bool)
+    f[z, y, x] = True
+    size = 1
+    while True:
+        z0, y0, x0 = max(z0 - 1, 0), max(y0 - 1, 0), max(x0 - 1, 0)
+        z1, y1, x1 = min(z1 + 1, G), min(y1 + 1, G), min(x1 + 1, G)
+        win = (slice(z0, z1), slice(y0, y1), slice(x0, x1))
+        f[win] = _dilate_closed(f[win]) & live[win]
+        grown = int(np.count_nonzero(f[win]))
+        if grown == size:
+            break
+        size = grown
+    zs, ys, xs = np.nonzero(f)
+    shift = []
+    for v in (xs, ys, zs):
+        lo, extent = int(v.min()), int(v.max()) - int(v.min()) + 1
+        shift.append(0 if placement == "keep" else -lo if placement == "origin" else (G - extent) // 2 - lo)
+    dx, dy, dz = shift
+    moved = np.zeros((G, G, G), dtype=np.uint8)
+    moved[zs + dz, ys + dy, xs + dx] = 1
+    return np.packbits(moved.ravel(), bitorder="little").view("<u4").astype(np.uint32), int(zs.size), (dx, dy, dz)
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

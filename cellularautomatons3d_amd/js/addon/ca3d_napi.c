@@ -1312,6 +1312,37 @@ static napi_value js_ensemble_census(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* ensembleIsolate(dstHandle, dstFirst, srcHandle, Uint32Array(2 * nJobs) jobs (universe, cell pairs), flags, Int32Array(4 * nJobs) out)
+ * -> gpuMs: job k makes the object of src's universe jobs[2 k] that holds the cell jobs[2 k + 1] the only thing in dst's universe
+ * dstFirst + k (ca3d_ensemble_isolate); out[4 k ..] is ca3d_isolated's four words: population, dx, dy, dz */
+static napi_value js_ensemble_isolate(napi_env env, napi_callback_info info)
+{
+	napi_value argv[6];
+	if (!get_args(env, info, 6, argv)) return NULL;
+	ca3d_ensemble_t *dst = get_ensemble(env, argv[0]);
+	if (!dst) return NULL;
+	ca3d_ensemble_t *src = get_ensemble(env, argv[2]);
+	uint32_t dst_first, flags;
+	void *jobs, *out;
+	size_t njobs, nout;
+	if (!src || !get_u32(env, argv[1], &dst_first) || !get_typed(env, argv[3], napi_uint32_array, 0, &jobs, &njobs) || !get_u32(env, argv[4], &flags) ||
+	    !get_typed(env, argv[5], napi_int32_array, 0, &out, &nout))
+		return NULL;
+	if (njobs % 2u || nout != 2u * njobs || njobs / 2u > 0xFFFFFFFFu)
+	{
+		napi_throw_range_error(env, NULL, "jobs must hold a (universe, cell) pair and out four words a job");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_isolate_job) == 8 && sizeof(ca3d_isolated) == 16, "a job crosses as two words, a result as four");
+	float ms = 0.f;
+	/* (no job: the library refuses the call and names the reason; it reads neither array) */
+	int rc = ca3d_ensemble_isolate(dst, dst_first, src, (uint32_t)(njobs / 2u), (const ca3d_isolate_job *)jobs, flags, (ca3d_isolated *)out, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1534,7 +1565,7 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleConfigureClustered", js_ensemble_configure_clustered}, {"ensembleClustered", js_ensemble_clustered},
 	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables},
 	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats},
-	    {"ensembleCensus", js_ensemble_census}};
+	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

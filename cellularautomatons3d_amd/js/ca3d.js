@@ -229,6 +229,9 @@ const STOP_EXTINCT = 1, STOP_STILL = 2; // ca3d_step_until: bits of `reason`
 const STOP_PERIODIC = 4; // ... and of ca3d_step_until_cycle / ca3d_ensemble_step_until_cycle, which alone take it
 const STOP_MOVING = 8; // ... and of ca3d_ensemble_step_until_moving (Ensemble.stepUntilMoving), which alone takes it
 
+const ISOLATE_PLACEMENTS = ["keep", "centre", "origin"]; // index = CA3D_ISOLATE_KEEP / CENTRE / ORIGIN (Ensemble.isolate)
+const ISOLATE_COPY_RULES = 0x100;
+
 class Engine
 {
 	constructor(device)
@@ -562,6 +565,30 @@ class Ensemble
 			components.push(list);
 		}
 		return { components, nComponents, remaining, gpuMs };
+	}
+	/** Isolate (ca3d_ensemble_isolate): universe dstFirst + k of THIS ensemble becomes the connected object of universe jobs[k][0] of
+	 *  opts.src (default: this ensemble) that holds the cell jobs[k][1] (x + 64 y + 4096 z, any cell of the object — a census' firstCell
+	 *  will do), alone, translated as opts.placement says ("keep", "centre" — the default —, "origin"), at step 0, found and written on
+	 *  the device in one launch -> {population: Uint32Array(n), shift: Int32Array(3 n) (dx, dy, dz a job), gpuMs}. opts.copyRules
+	 *  (default true): the destination universe takes its source universe's rule (both ensembles of one kind). opts.dstFirst: 0.
+	 *  jobs: an array of [universe, cell] pairs, or a Uint32Array of such pairs. */
+	isolate(jobs, opts)
+	{
+		const o = Object.assign({ dstFirst: 0, src: null, placement: "centre", copyRules: true }, opts || {});
+		const placement = ISOLATE_PLACEMENTS.indexOf(o.placement);
+		if (placement < 0) throw new Error(`unknown placement ${JSON.stringify(o.placement)}: "keep", "centre" or "origin"`);
+		const flat = jobs instanceof Uint32Array ? jobs : Uint32Array.from(jobs.flat());
+		if (flat.length % 2) throw new RangeError("jobs: [universe, cell] pairs");
+		const n = flat.length / 2;
+		const out = new Int32Array(4 * n);
+		const gpuMs = this._a.ensembleIsolate(this._e, o.dstFirst, (o.src || this)._e, flat, placement | (o.copyRules ? ISOLATE_COPY_RULES : 0), out);
+		const population = new Uint32Array(n), shift = new Int32Array(3 * n);
+		for (let k = 0; k < n; k++)
+		{
+			population[k] = out[4 * k];
+			shift.set(out.subarray(4 * k + 1, 4 * k + 4), 3 * k);
+		}
+		return { population, shift, gpuMs };
 	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at

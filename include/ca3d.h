@@ -524,6 +524,60 @@ typedef struct ca3d_component
 } ca3d_component;              /* 32 bytes */
 int ca3d_ensemble_census(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t max_components, ca3d_component *out /* [count][max_components] */,
                          uint32_t *n_components /* [count] */, uint32_t *remaining /* [count] */, float *gpu_ms /* may be NULL */);
+/*
+ * Isolate (no reference counterpart): an object a census named becomes the only thing in a universe of its own, with room around it
+ * and the rule of the universe it came from, without a state leaving the device — ca3d_ensemble_step_until_cycle, _moving, _trace and
+ * ca3d_ensemble_render_sheet then classify and draw every object of every soup side by side. One launch of ca_ensemble_isolate64
+ * (csrc/ca_isolate.hip, one workgroup a job: the census' flood fill, then a translated write). host.isolate restates it.
+ *
+ * The definition. Job k writes universe dst_first + k of `dst`. Its state becomes the connected component of universe jobs[k].universe
+ *   of `src` that contains the cell jobs[k].cell (x + 64 y + 4096 z) — connectivity is the census': the 26-neighbourhood inside the
+ *   closed cube, no face wraps — translated by `shift`, and everything else is zero. ANY live cell of the object selects it, not only
+ *   the census' first_cell. A dead cell gives an empty universe, population 0 and a zero shift.
+ *   The shift, with the component's box (min, max) and extent e = max - min + 1 per axis, by the placement in the low byte of `flags`:
+ *     CA3D_ISOLATE_KEEP    0: the object stays where it was;
+ *     CA3D_ISOLATE_ORIGIN  -min: the state's ca3d_summary digest is then the census record's digest;
+ *     CA3D_ISOLATE_CENTRE  (64 - e) / 2 - min (integer division): about 30 cells of room each way for a small object.
+ *   The translated box is always inside the cube: nothing is clipped.
+ *   Both ping-pong buffers get the words, as with upload and seed; the destination universes' records are rebuilt at step 0 with no
+ *   previous state (the launch ca3d_ensemble_upload_state ends in), and those universes count as having a state.
+ *   CA3D_ISOLATE_COPY_RULES copies the source universe's stored rule words to the destination universe on the device: `src` and `dst`
+ *   must have the same neighbourhood and the same clustered property, every source universe named must have rules, and the
+ *   destinations count as having rules afterwards. Without the flag rules are untouched and the two ensembles may differ in kind.
+ *   out[k] (nullable array): the object's population and the shift applied.
+ *
+ * `src` and `dst` may be the same handle or two handles on the same device; when they are the same no job's universe may lie in
+ * [dst_first, dst_first + n_jobs). The launch runs on dst's stream behind what is queued there and behind what is queued on src's
+ * stream at the time of the call (an event recorded there, waited for on dst's). The call waits for its own result, as
+ * ca3d_ensemble_census does, so src may go on afterwards; src's states, records and counters are only read. gpu_ms (nullable) receives
+ * the hipEvent time around the launch. Jobs and results are staged in one device array on dst's handle (24 bytes a job, grown when a
+ * call needs more — the new array is allocated before the old one is freed — freed by a configure and by destroy).
+ *
+ * Errors — a refused call touches neither ensemble nor `out`, and names the job where there is one: a NULL handle or jobs, n_jobs == 0
+ * or more jobs than fit behind dst_first, a `universe` out of range, cell >= 1 << 18, an unknown placement or flag bit, handles on
+ * different devices, a source universe among the destinations — CA3D_ERR_INVALID_ARGUMENT; either ensemble not configured, a source
+ * universe without a state, with CA3D_ISOLATE_COPY_RULES one without rules — CA3D_ERR_NOT_CONFIGURED; with CA3D_ISOLATE_COPY_RULES
+ * ensembles of different kinds — CA3D_ERR_UNSUPPORTED.
+ */
+typedef struct ca3d_isolate_job
+{
+	uint32_t universe; /* of src */
+	uint32_t cell;     /* x + 64 y + 4096 z: any cell of the object */
+} ca3d_isolate_job;
+typedef struct ca3d_isolated
+{
+	uint32_t population;
+	int32_t shift[3]; /* dx, dy, dz applied */
+} ca3d_isolated;      /* 16 bytes */
+enum
+{
+	CA3D_ISOLATE_KEEP = 0,
+	CA3D_ISOLATE_CENTRE = 1,
+	CA3D_ISOLATE_ORIGIN = 2
+}; /* placement: the low byte of flags */
+#define CA3D_ISOLATE_COPY_RULES 0x100u
+int ca3d_ensemble_isolate(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensemble_t *src, uint32_t n_jobs, const ca3d_isolate_job *jobs, uint32_t flags,
+                          ca3d_isolated *out /* [n_jobs], may be NULL */, float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

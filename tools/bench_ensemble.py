@@ -61,6 +61,17 @@ digests included, in sampled ones. Reported: medians of --repeats measurements o
 the call, of read_state alone, and of read_state + labelling. No ratio is required. Written to profiles/ensemble_census_64.json unless
 --out says otherwise.
 
+--isolate measures the isolate (ca3d_ensemble_isolate, kernel ca_ensemble_isolate64: objects a census named, each made the only thing
+in a universe of its own, centred, with its source's rule) on the ash workload of --census (Moore B6 / S5-7, and_rounds 1, seeds 1 .. B,
+step_until_cycle(512)): a census at max_components 1024, then EVERY object of the B = 256 universes isolated into a second ensemble in
+one call. Against the loop it replaces on the same objects: per universe read_state and a labelling on the CPU (scipy.ndimage.label
+with a full 3 x 3 x 3 structure when scipy can be imported — one labelling a universe, the objects cut out of it — else host.isolate per
+object; the profile says which), per object the centred state built with numpy and upload_state into the second ensemble. Before timing,
+the isolated states, populations and shifts must equal host.isolate for every object of sampled universes, and after the loop the second
+ensemble must hold what the call left there. Reported: medians of --repeats measurements of the call's hipEvent time, of the host clock
+around the call, and of the host clock around the loop. No ratio is required. Written to profiles/ensemble_isolate_64.json unless --out
+says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -430,6 +441,91 @@ def census_rows(args):
     return rows, labeller
 
 
+def isolate_rows(args):
+    """isolate against the read_state + cut + upload_state loop: one row per B. -> (rows, the cutter's name)"""
+    try:
+        from scipy import ndimage
+        cutter = "scipy.ndimage.label, full 3 x 3 x 3 structure, one labelling a universe"
+    except ImportError:
+        ndimage, cutter = None, "host.isolate per object"
+    full = np.ones((3, 3, 3), dtype=int)
+    M = 1024
+    born, survive, rounds = CENSUS_ASH["ash B6/S5-7"]
+
+    def centred_by_label(words, cells):
+        """The centred states of the objects that hold `cells`, from one labelling of the universe."""
+        lab, _ = ndimage.label(np.unpackbits(words.view(np.uint8), bitorder="little").reshape(G, G, G), structure=full)
+        boxes = ndimage.find_objects(lab)
+        out = []
+        for cell in cells:
+            k = int(lab[cell >> 12, (cell >> 6) & 63, cell & 63])
+            sl = boxes[k - 1]
+            part = lab[sl] == k
+            moved = np.zeros((G, G, G), dtype=np.uint8)
+            lo = [(G - n) // 2 for n in part.shape]
+            moved[lo[0]:lo[0] + part.shape[0], lo[1]:lo[1] + part.shape[1], lo[2]:lo[2] + part.shape[2]] = part
+            out.append(np.packbits(moved.ravel(), bitorder="little").view("<u4"))
+        return out
+
+    ens, nursery = Ensemble(0), Ensemble(0)
+    rows = []
+    for B in args.universes:
+        ens.configure(B, neighbourhood="moore")
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        ens.seed_states(0, np.arange(1, B + 1), rounds)
+        done, reason, _ = ens.step_until_cycle(512)
+        comps, n, rest = ens.census(max_components=M)
+        if rest.any():
+            raise SystemExit(f"B {B}: a census of {M} objects a universe is not complete")
+        jobs = np.array([(u, int(c["first_cell"])) for u in range(B) for c in comps[u, :n[u]]], dtype=np.uint32).reshape(-1, 2)
+        starts = np.concatenate([[0], np.cumsum(n)])
+        J = len(jobs)
+        nursery.configure(J, neighbourhood="moore")
+        pop, shift = nursery.isolate(jobs, 0, ens, "centre", True)
+        sample = sorted({0, B // 2, B - 1})
+        for u in sample:
+            words = ens.read_state(u, 1)[0]
+            got = nursery.read_state(int(starts[u]), int(n[u]))
+            for k in range(int(n[u])):
+                j = int(starts[u]) + k
+                w, p, d = host.isolate(words, int(jobs[j, 1]), "centre")
+                if not np.array_equal(got[k], w) or (int(pop[j]), tuple(int(v) for v in shift[j])) != (p, d):
+                    raise SystemExit(f"B {B}: object {k} of universe {u} is not host.isolate's")
+        if not np.array_equal(pop, np.concatenate([comps["population"][u, :n[u]] for u in range(B)])):
+            raise SystemExit(f"B {B}: the isolated populations are not the census'")
+        left = nursery.read_state()
+        gpu, wall, loop = [], [], []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            nursery.isolate(jobs, 0, ens, "centre", True)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            gpu.append(nursery.isolate_gpu_ms())
+            t0 = time.perf_counter()
+            for u in range(B):
+                words = ens.read_state(u, 1)[0]
+                a, b = int(starts[u]), int(starts[u + 1])
+                cells = [int(c) for c in jobs[a:b, 1]]
+                cut = centred_by_label(words, cells) if ndimage is not None else [host.isolate(words, c, "centre")[0] for c in cells]
+                for k, w in enumerate(cut):
+                    nursery.upload_state(a + k, w)
+            loop.append((time.perf_counter() - t0) * 1e3)
+            if not np.array_equal(nursery.read_state(), left):
+                raise SystemExit(f"B {B}: the loop left other states than the call")
+        row = {"workload": "ash B6/S5-7", "universes": B, "max_components": M, "placement": "centre", "copy_rules": True,
+               "stepping": {"max_steps": 512, "stopped": int(np.count_nonzero(reason)), "median_steps_done": float(np.median(done))},
+               "objects": J, "objects_per_universe": {"min": int(n.min()), "median": float(np.median(n)), "max": int(n.max())},
+               "cells_per_object_median": float(np.median(pop)), "verified_against_host_isolate_in": sample,
+               "isolate_gpu_ms": statistics.median(gpu), "isolate_gpu_ms_all": gpu,
+               "isolate_wall_ms": statistics.median(wall), "isolate_wall_ms_all": wall,
+               "loop_wall_ms": statistics.median(loop), "loop_wall_ms_all": loop,
+               "loop_over_isolate_wall": statistics.median(loop) / statistics.median(wall)}
+        rows.append(row)
+        print(json.dumps(row))
+    ens.close()
+    nursery.close()
+    return rows, cutter
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -444,10 +540,11 @@ def main():
     ap.add_argument("--trace", action="store_true", help="measure step_trace against the step + summaries loop and plain stepping instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--sheet", action="store_true", help="measure render_sheet against the upload + render loop instead (B = 256 1024)")
     ap.add_argument("--census", action="store_true", help="measure census against read_state + labelling on the CPU instead (B = 256 1024)")
+    ap.add_argument("--isolate", action="store_true", help="measure isolate against the read_state + cut + upload_state loop instead (B = 256)")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -463,6 +560,27 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.isolate:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_isolate_64.json")
+        rows, cutter = isolate_rows(args)
+        result = {
+            "what": "B universes of 64^3 of ash (seed_states, seeds 1 .. B, and_rounds 1, Moore B6/S5-7, step_until_cycle(512)), a census at max_components 1024, then "
+                    "every object of every universe isolated into a second ensemble, centred, with its source's rule, in ONE Ensemble.isolate call — one launch of "
+                    "ca_ensemble_isolate64 and the reset launch — vs. the loop it replaces on the same objects: per universe read_state and a cut on the CPU, per "
+                    "object upload_state into the second ensemble",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"isolate": "ca_ensemble_isolate64"}, "cpu_cut": cutter,
+            "timing": f"isolate_gpu_ms: hipEvent time around the isolate launch; *_wall_ms: host clock around the call / the loop; medians of {args.repeats} alternating "
+                      "measurements after the isolated states, populations and shifts equalled host.isolate for every object of the sampled universes; after "
+                      "each loop the second ensemble held what the call had left there",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.census:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_census_64.json")
         rows, labeller = census_rows(args)
