@@ -107,6 +107,14 @@ int check_range(const ca3d_ensemble *e, uint32_t first, uint32_t count)
 	return CA3D_OK;
 }
 
+// every universe of a checked range holds a state
+int require_state(const ca3d_ensemble *e, uint32_t first, uint32_t count)
+{
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	return CA3D_OK;
+}
+
 // configure -> set_rules (every universe) -> upload (every universe) -> step
 int ensemble_ready(const ca3d_ensemble *e)
 {
@@ -386,53 +394,48 @@ int size_sheet_targets(ca3d_ensemble *e, size_t px)
 	return CA3D_OK;
 }
 
-// room for a census result of `bytes` bytes; a failure leaves the handle with what it had
+// a device scratch array of the handle and its byte count, grown to `bytes`: the new array first, so that a failure leaves the handle with
+// what it had; then the stream is drained, since a call that was only enqueued may still be using the old one. When the new array cannot
+// be had, *refused says why and the caller words the failure: its message names what the array is for.
+int grow_scratch(ca3d_ensemble *e, uint8_t *&array, size_t &have, size_t bytes, hipError_t *refused)
+{
+	*refused = hipSuccess;
+	if (bytes <= have) return CA3D_OK;
+	uint8_t *grown = nullptr;
+	if ((*refused = hipMalloc((void **)&grown, bytes)) != hipSuccess)
+	{
+		(void)hipGetLastError();
+		return *refused == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE;
+	}
+	if (array)
+	{
+		HIP_TRY(hipStreamSynchronize(e->stream));
+		hipFree(array);
+	}
+	array = grown;
+	have = bytes;
+	return CA3D_OK;
+}
+
+// room for a census result of `bytes` bytes
 int size_census(ca3d_ensemble *e, size_t bytes)
 {
 	if (!e->ev_census_start) HIP_TRY(hipEventCreate(&e->ev_census_start));
 	if (!e->ev_census_stop) HIP_TRY(hipEventCreate(&e->ev_census_stop));
-	if (bytes <= e->census_bytes) return CA3D_OK;
-	// the new array first: a failure leaves the handle as it was
-	uint8_t *grown = nullptr;
-	hipError_t err = hipMalloc((void **)&grown, bytes);
-	if (err != hipSuccess)
-	{
-		(void)hipGetLastError();
-		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating a census of %zu bytes: %s", bytes, hipGetErrorString(err));
-	}
-	if (e->census)
-	{
-		HIP_TRY(hipStreamSynchronize(e->stream));
-		hipFree(e->census);
-	}
-	e->census = grown;
-	e->census_bytes = bytes;
-	return CA3D_OK;
+	hipError_t refused;
+	const int rc = grow_scratch(e, e->census, e->census_bytes, bytes, &refused);
+	return refused == hipSuccess ? rc : fail(rc, "allocating a census of %zu bytes: %s", bytes, hipGetErrorString(refused));
 }
 
-// room for the jobs and results of an isolate call, `bytes` bytes; a failure leaves the handle with what it had
+// room for the jobs and results of an isolate call, `bytes` bytes
 int size_isolate(ca3d_ensemble *e, size_t bytes)
 {
 	if (!e->ev_isolate_start) HIP_TRY(hipEventCreate(&e->ev_isolate_start));
 	if (!e->ev_isolate_stop) HIP_TRY(hipEventCreate(&e->ev_isolate_stop));
 	if (!e->ev_isolate_src) HIP_TRY(hipEventCreateWithFlags(&e->ev_isolate_src, hipEventDisableTiming));
-	if (bytes <= e->isolate_bytes) return CA3D_OK;
-	// the new array first: a failure leaves the handle as it was
-	uint8_t *grown = nullptr;
-	hipError_t err = hipMalloc((void **)&grown, bytes);
-	if (err != hipSuccess)
-	{
-		(void)hipGetLastError();
-		return fail(err == hipErrorOutOfMemory ? CA3D_ERR_OUT_OF_MEMORY : CA3D_ERR_DEVICE, "allocating %zu bytes of isolate jobs: %s", bytes, hipGetErrorString(err));
-	}
-	if (e->isolate)
-	{
-		HIP_TRY(hipStreamSynchronize(e->stream));
-		hipFree(e->isolate);
-	}
-	e->isolate = grown;
-	e->isolate_bytes = bytes;
-	return CA3D_OK;
+	hipError_t refused;
+	const int rc = grow_scratch(e, e->isolate, e->isolate_bytes, bytes, &refused);
+	return refused == hipSuccess ? rc : fail(rc, "allocating %zu bytes of isolate jobs: %s", bytes, hipGetErrorString(refused));
 }
 
 } // namespace
@@ -702,8 +705,7 @@ int ca3d_ensemble_read_state(ca3d_ensemble_t *e, uint32_t first, uint32_t count,
 	if (rc) return rc;
 	if (!words || n_words != (size_t)count * kEnsembleWords)
 		return fail(CA3D_ERR_INVALID_ARGUMENT, "%u universes hold %zu words (got %zu)", count, (size_t)count * kEnsembleWords, n_words);
-	for (uint32_t u = first; u < first + count; u++)
-		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	if ((rc = require_state(e, first, count))) return rc;
 	HIP_TRY(hipSetDevice(e->device));
 	HIP_TRY(hipMemcpyAsync(words, e->state + (size_t)first * kEnsembleWords, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
@@ -762,8 +764,7 @@ int ca3d_ensemble_summarize(ca3d_ensemble_t *e, uint32_t first, uint32_t count, 
 	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
 	int rc = check_range(e, first, count);
 	if (rc) return rc;
-	for (uint32_t u = first; u < first + count; u++)
-		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	if ((rc = require_state(e, first, count))) return rc;
 	HIP_TRY(hipSetDevice(e->device));
 	HIP_TRY(hipMemcpyAsync(out, e->records + first, (size_t)count * sizeof(ca3d_summary), hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
@@ -815,8 +816,7 @@ int ca3d_ensemble_render_sheet(ca3d_ensemble_t *e, uint32_t first, uint32_t coun
 	const uint64_t rows = ((uint64_t)count + columns - 1u) / columns, W = (uint64_t)columns * tile_w, H = rows * tile_h;
 	if (W * H > (1ull << 26)) // (columns < 2^32, tile_w <= 2^10, H <= 2^30: no overflow)
 		return fail(CA3D_ERR_INVALID_ARGUMENT, "a sheet of %llu x %llu pixels: at most 2^26 pixels", (unsigned long long)W, (unsigned long long)H);
-	for (uint32_t u = first; u < first + count; u++)
-		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	if ((rc = require_state(e, first, count))) return rc;
 	HIP_TRY(hipSetDevice(e->device));
 	const size_t px = (size_t)(W * H);
 	if ((rc = size_sheet_targets(e, px))) return rc;
@@ -872,8 +872,7 @@ int ca3d_ensemble_census(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uin
 	if (rc) return rc;
 	if (max_components == 0 || max_components > kCensusMaxComponents)
 		return fail(CA3D_ERR_INVALID_ARGUMENT, "max_components %u: a census lists 1 to %u components a universe", max_components, kCensusMaxComponents);
-	for (uint32_t u = first; u < first + count; u++)
-		if (!e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_upload_state has not been called for universe %u", u);
+	if ((rc = require_state(e, first, count))) return rc;
 	HIP_TRY(hipSetDevice(e->device));
 	const size_t rec_bytes = (size_t)count * max_components * sizeof(ca3d_component), word_bytes = (size_t)count * sizeof(uint32_t);
 	if ((rc = size_census(e, rec_bytes + 2u * word_bytes))) return rc;

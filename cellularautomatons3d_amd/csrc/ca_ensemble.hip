@@ -35,6 +35,7 @@ namespace ca3d
 namespace
 {
 #include "ca_bitops.inc"
+#include "ca_wave_ops.inc"
 #include "ca_digest.h"
 
 typedef unsigned long long u64;
@@ -70,52 +71,6 @@ __device__ __forceinline__ u32 cycle_mix(u32 idx, u32 w)
 	// from zero in bit 31 alone cancel in the sum — an and-rounds fill dying out did exactly that one step before it was empty)
 	const u32 x = (w ^ (w >> 16) ^ (idx * 0x9E3779B1u)) * 0x85EBCA6Bu;
 	return x ^ (x >> 15);
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_add(T v)
-{
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-__device__ __forceinline__ u32 wave_or(u32 v)
-{
-	for (int o = 32; o > 0; o >>= 1) v |= (u32)__shfl_xor(v, o);
-	return v;
-}
-
-// The trace's sum over a wave, wave-uniform: four DPP adds leave every row of 16 lanes with its sum (lane ^ 1, lane ^ 2, the other quad
-// pair, the other half), four v_readlane and three scalar adds join the rows. No LDS, and no lane-address registers that would stay
-// alive across the steps, where the Moore step has none to spare (__shfl_xor's do).
-__device__ __forceinline__ u32 row16_sum(u32 v)
-{
-	v += dpp_mov<1 | (0 << 2) | (3 << 4) | (2 << 6)>(v); // quad_perm:[1,0,3,2]
-	v += dpp_mov<2 | (3 << 2) | (0 << 4) | (1 << 6)>(v); // quad_perm:[2,3,0,1]
-	v += dpp_mov<0x141>(v);                              // row_half_mirror
-	v += dpp_mov<0x140>(v);                              // row_mirror
-	return v;
-}
-__device__ __forceinline__ u32 wave_sum_uniform(u32 v)
-{
-	v = row16_sum(v);
-	return (u32)__builtin_amdgcn_readlane((int)v, 0) + (u32)__builtin_amdgcn_readlane((int)v, 16) + (u32)__builtin_amdgcn_readlane((int)v, 32) +
-	       (u32)__builtin_amdgcn_readlane((int)v, 48);
-}
-
-// The same for an OR (the *_moving kernels' x-occupancy words).
-__device__ __forceinline__ u32 row16_or(u32 v)
-{
-	v |= dpp_mov<1 | (0 << 2) | (3 << 4) | (2 << 6)>(v); // quad_perm:[1,0,3,2]
-	v |= dpp_mov<2 | (3 << 2) | (0 << 4) | (1 << 6)>(v); // quad_perm:[2,3,0,1]
-	v |= dpp_mov<0x141>(v);                              // row_half_mirror
-	v |= dpp_mov<0x140>(v);                              // row_mirror
-	return v;
-}
-__device__ __forceinline__ u32 wave_or_uniform(u32 v)
-{
-	v = row16_or(v);
-	return (u32)__builtin_amdgcn_readlane((int)v, 0) | (u32)__builtin_amdgcn_readlane((int)v, 16) | (u32)__builtin_amdgcn_readlane((int)v, 32) |
-	       (u32)__builtin_amdgcn_readlane((int)v, 48);
 }
 
 // The *_moving kernels (CA3D_STOP_MOVING): a bounding box travels as two words, x | y << 8 | z << 16 of box_min and of box_max. Inside

@@ -18,7 +18,9 @@ namespace ca3d
 {
 namespace
 {
-typedef uint32_t u32;
+#include "ca_bitops.inc"
+#include "ca_wave_ops.inc"
+
 typedef unsigned long long u64;
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
@@ -42,31 +44,10 @@ struct SummaryArgs
 
 #include "ca_digest.h"
 
-__device__ __forceinline__ u32 wave_sum(u32 v)
-{
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-__device__ __forceinline__ u32 wave_min(u32 v)
-{
-	for (int o = 32; o > 0; o >>= 1) v = min(v, (u32)__shfl_xor(v, o));
-	return v;
-}
-__device__ __forceinline__ u32 wave_max(u32 v)
-{
-	for (int o = 32; o > 0; o >>= 1) v = max(v, (u32)__shfl_xor(v, o));
-	return v;
-}
-
 // the workgroup's live cells of plane `plane` -> its slot (called by all threads, at a workgroup-uniform point)
 __device__ __forceinline__ void flush_plane(u32 *result, u32 plane, u32 count, u32 *lds)
 {
-	const u32 s = wave_sum(count);
+	const u32 s = wave_add(count);
 	if ((threadIdx.x & 63u) == 0u) lds[threadIdx.x >> 6] = s;
 	__syncthreads();
 	if (threadIdx.x == 0u)
@@ -174,8 +155,8 @@ __global__ __launch_bounds__(kThreads) void ca_summary(SummaryArgs a)
 	}
 	if (t0 < t1) flush_plane(a.result, plane, plane_pop, lds_plane);
 
-	// registers -> wave -> workgroup -> one set of atomics
-	const u64 s_pop = wave_sum64(pop), s_b = wave_sum64(births), s_d = wave_sum64(deaths), s_dig = wave_sum64(dig);
+	// registers -> wave -> workgroup -> one set of atomics (the counts are widened first: every sum from here on is a 64-bit one)
+	const u64 s_pop = wave_add((u64)pop), s_b = wave_add((u64)births), s_d = wave_add((u64)deaths), s_dig = wave_add(dig);
 	const u32 m[6] = {wave_min(xmin), wave_min(ymin), wave_min(zmin), wave_max(xmax), wave_max(ymax), wave_max(zmax)};
 	const u32 wave = tid >> 6;
 	if ((tid & 63u) == 0u)

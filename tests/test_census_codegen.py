@@ -1,44 +1,18 @@
 """ca_ensemble_census64 (csrc/ca_census.hip) holds a universe and the component being filled in registers, 1024 threads a workgroup:
 no scratch, nothing spilled, at most 128 VGPRs (a 1024-thread workgroup is four waves a SIMD) and at most 64 KiB of LDS. Read out of
 the kernel metadata of the gfx950 assembly, built with the Makefile's compiler and flags. It needs hipcc, no GPU."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cellularautomatons3d_amd", "csrc")
-FIELDS = ["group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count"]
-
-
-def _make_var(text, name):
-    m = re.search(r"^%s\s*\?=\s*(.*)$" % name, text, re.M)
-    assert m, f"{name} not found in csrc/Makefile"
-    return m.group(1).strip()
+import codegen_lib as cg
 
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
     """{symbol: {field: value}} of every kernel of ca_census.hip."""
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    hipcc = os.environ.get("HIPCC") or _make_var(mk, "HIPCC")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("hipcc is not installed")
-    assert re.search(r"^OBJS\s*:=.*\bca_census\.o\b", mk, re.M)
-    arch = _make_var(mk, "ARCH")
-    out = tmp_path_factory.mktemp("codegen") / "ca_census.s"
-    cmd = [hipcc, f"--offload-arch={arch}"] + _make_var(mk, "CXXFLAGS").split() + ["--cuda-device-only", "-S", "ca_census.hip", "-o", str(out)]
-    subprocess.run(cmd, cwd=CSRC, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    listing = out.read_text()
-    meta = listing[listing.index("amdhsa.kernels"):]
-    found = {}
-    for e in ("." + e for e in meta.split("  - .")):
-        m = re.search(r"\.name:\s+(\w+)", e)
-        if m and re.search(r"\.vgpr_count:", e):
-            found[m.group(1)] = {f: int(re.search(r"\.%s:\s+(\d+)" % f, e).group(1)) for f in FIELDS}
-    return found
+    assert re.search(r"^OBJS\s*:=.*\bca_census\.o\b", cg.makefile(), re.M)
+    return cg.kernel_metadata(cg.listings(tmp_path_factory.mktemp("codegen"), ["ca_census"])["ca_census"])
 
 
 def test_census_kernel_resources(kernels):

@@ -5,33 +5,15 @@ the request's branch, which then left at the head of the pass. This test reads t
 ahead-of-time kernel, built with the Makefile's compiler and flags. It needs hipcc, no GPU."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cellularautomatons3d_amd", "csrc")
-
-
-def _make_var(text, name):
-    m = re.search(r"^%s\s*\?=\s*(.*)$" % name, text, re.M)
-    assert m, f"{name} not found in csrc/Makefile"
-    return m.group(1).strip()
+import codegen_lib as cg
 
 
 @pytest.fixture(scope="module")
 def listing(tmp_path_factory):
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    hipcc = os.environ.get("HIPCC") or _make_var(mk, "HIPCC")
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("hipcc is not installed")
-    arch = _make_var(mk, "ARCH")
-    flags = _make_var(mk, "CXXFLAGS").split()
-    out = tmp_path_factory.mktemp("codegen") / "ca_resident.s"
-    cmd = [hipcc, f"--offload-arch={arch}"] + flags + ["--cuda-device-only", "-S", "ca_resident.hip", "-o", str(out)]
-    subprocess.run(cmd, cwd=CSRC, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return out.read_text()
+    return cg.listings(tmp_path_factory.mktemp("codegen"), ["ca_resident"])["ca_resident"]
 
 
 def _kernel(listing, fragment):
@@ -47,7 +29,7 @@ def _kernel(listing, fragment):
 
 
 def _pair_pre():
-    src = open(os.path.join(CSRC, "ca_resident_kernel.inc")).read()
+    src = open(os.path.join(cg.CSRC, "ca_resident_kernel.inc")).read()
     return int(re.search(r"^#define CA3D_RES_PAIR_PRE (\d+)", src, re.M).group(1))
 
 
