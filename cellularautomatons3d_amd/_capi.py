@@ -78,6 +78,23 @@ ISOLATE_PLACEMENTS = {"keep": 0, "centre": 1, "origin": 2}
 ISOLATE_COPY_RULES = 0x100
 
 
+class ComposePartStruct(C.Structure):
+    """ca3d_compose_part (include/ca3d.h): a source universe, an orientation 0 .. 47 and where the turned piece's box_min goes, 24 bytes
+    (`host.COMPOSE_PART_DTYPE`)."""
+    _fields_ = [("universe", C.c_uint32), ("orientation", C.c_uint32), ("at", C.c_int32 * 3), ("reserved", C.c_uint32)]
+
+
+class ComposedStruct(C.Structure):
+    """ca3d_composed (include/ca3d.h): what `ca3d_ensemble_compose` says of one destination, 16 bytes (`host.COMPOSED_DTYPE`)."""
+    _fields_ = [("population", C.c_uint32), ("placed", C.c_uint32), ("overlap", C.c_uint32), ("clipped", C.c_uint32)]
+
+
+#: the flag bits of `ca3d_ensemble_compose`, and the most parts a call takes
+COMPOSE_OVER = 0x1
+COMPOSE_COPY_RULES = 0x100
+COMPOSE_MAX_PARTS = 1 << 20
+
+
 class SeedStruct(C.Structure):
     """ca3d_seed (include/ca3d.h)."""
     _fields_ = [("seed", C.c_uint32), ("and_rounds", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
@@ -180,6 +197,8 @@ SYMBOLS = [
     ("ca3d_ensemble_census", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ComponentStruct), _u32p, _u32p, C.POINTER(C.c_float)]),
     ("ca3d_ensemble_isolate", C.c_int, [_H, C.c_uint32, _H, C.c_uint32, C.POINTER(IsolateJobStruct), C.c_uint32, C.POINTER(IsolatedStruct),
                                         C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_compose", C.c_int, [_H, C.c_uint32, C.c_uint32, _H, C.POINTER(ComposePartStruct), _u32p, C.c_uint32,
+                                        C.POINTER(ComposedStruct), C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

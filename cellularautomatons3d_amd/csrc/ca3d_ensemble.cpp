@@ -7,6 +7,7 @@
 // ca3d_ensemble_render_sheet draws a range of universes as the tiles of one contact sheet (render_sheet.hip).
 // ca3d_ensemble_census lists the connected objects of a range of universes (ca_census.hip).
 // ca3d_ensemble_isolate makes objects a census named the only thing in universes of their own (ca_isolate.hip).
+// ca3d_ensemble_compose stages whole universes, turned and shifted, into universes of their union (ca_compose.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -68,6 +69,12 @@ struct ca3d_ensemble
 	uint8_t *isolate = nullptr;
 	size_t isolate_bytes = 0;
 	hipEvent_t ev_isolate_start = nullptr, ev_isolate_stop = nullptr, ev_isolate_src = nullptr;
+	// ca3d_ensemble_compose, on the DESTINATION handle: the records of the call under way, [n_dst] of 16 bytes, then its parts, [n_parts]
+	// of 24 bytes, then part_begin, [n_dst + 1] words, in one device array of compose_bytes bytes, grown when a call needs more, gone
+	// with the other arrays at a configure; its event pair and the event that orders the launch behind the source's stream
+	uint8_t *compose = nullptr;
+	size_t compose_bytes = 0;
+	hipEvent_t ev_compose_start = nullptr, ev_compose_stop = nullptr, ev_compose_src = nullptr;
 };
 
 namespace
@@ -96,6 +103,9 @@ void free_arrays(ca3d_ensemble *e)
 	if (e->isolate) hipFree(e->isolate);
 	e->isolate = nullptr;
 	e->isolate_bytes = 0;
+	if (e->compose) hipFree(e->compose);
+	e->compose = nullptr;
+	e->compose_bytes = 0;
 	e->n = 0;
 	e->timed = false;
 }
@@ -438,6 +448,17 @@ int size_isolate(ca3d_ensemble *e, size_t bytes)
 	return refused == hipSuccess ? rc : fail(rc, "allocating %zu bytes of isolate jobs: %s", bytes, hipGetErrorString(refused));
 }
 
+// room for the records, parts and part_begin of a compose call, `bytes` bytes
+int size_compose(ca3d_ensemble *e, size_t bytes)
+{
+	if (!e->ev_compose_start) HIP_TRY(hipEventCreate(&e->ev_compose_start));
+	if (!e->ev_compose_stop) HIP_TRY(hipEventCreate(&e->ev_compose_stop));
+	if (!e->ev_compose_src) HIP_TRY(hipEventCreateWithFlags(&e->ev_compose_src, hipEventDisableTiming));
+	hipError_t refused;
+	const int rc = grow_scratch(e, e->compose, e->compose_bytes, bytes, &refused);
+	return refused == hipSuccess ? rc : fail(rc, "allocating %zu bytes of compose parts: %s", bytes, hipGetErrorString(refused));
+}
+
 } // namespace
 
 extern "C"
@@ -489,6 +510,9 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	if (e->ev_isolate_start) hipEventDestroy(e->ev_isolate_start);
 	if (e->ev_isolate_stop) hipEventDestroy(e->ev_isolate_stop);
 	if (e->ev_isolate_src) hipEventDestroy(e->ev_isolate_src);
+	if (e->ev_compose_start) hipEventDestroy(e->ev_compose_start);
+	if (e->ev_compose_stop) hipEventDestroy(e->ev_compose_stop);
+	if (e->ev_compose_src) hipEventDestroy(e->ev_compose_src);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
 	return CA3D_OK;
@@ -958,6 +982,92 @@ int ca3d_ensemble_isolate(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensembl
 	{
 		if (!dst->has_state[u]) { dst->has_state[u] = 1; dst->missing_state--; }
 		if (copy_rules && !dst->has_rules[u]) { dst->has_rules[u] = 1; dst->missing_rules--; }
+	}
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_compose(ca3d_ensemble_t *dst, uint32_t dst_first, uint32_t n_dst, ca3d_ensemble_t *src, const ca3d_compose_part *parts,
+                          const uint32_t *part_begin, uint32_t flags, ca3d_composed *out, float *gpu_ms) CA3D_API_TRY
+{
+	if (!dst || !src) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!part_begin) return fail(CA3D_ERR_INVALID_ARGUMENT, "part_begin is NULL");
+	if (!dst->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called for the destination ensemble");
+	if (!src->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called for the source ensemble");
+	if (n_dst == 0 || dst_first >= dst->n || n_dst > dst->n - dst_first)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "%u destinations in universes [%u, %u + %u) of %u", n_dst, dst_first, dst_first, n_dst, dst->n);
+	const bool over = (flags & CA3D_COMPOSE_OVER) != 0u, copy_rules = (flags & CA3D_COMPOSE_COPY_RULES) != 0u;
+	if (flags & ~(CA3D_COMPOSE_OVER | CA3D_COMPOSE_COPY_RULES)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in flags %#x", flags);
+	if (part_begin[0] != 0u) return fail(CA3D_ERR_INVALID_ARGUMENT, "part_begin[0] is %u, not 0", part_begin[0]);
+	for (uint32_t k = 0; k < n_dst; k++)
+		if (part_begin[k + 1] < part_begin[k])
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "part_begin decreases: part_begin[%u] = %u, part_begin[%u] = %u", k, part_begin[k], k + 1, part_begin[k + 1]);
+	const uint32_t n_parts = part_begin[n_dst];
+	if (n_parts > CA3D_COMPOSE_MAX_PARTS) return fail(CA3D_ERR_INVALID_ARGUMENT, "%u parts: a call takes %u at most", n_parts, CA3D_COMPOSE_MAX_PARTS);
+	if (n_parts && !parts) return fail(CA3D_ERR_INVALID_ARGUMENT, "parts is NULL");
+	if (src->device != dst->device) return fail(CA3D_ERR_INVALID_ARGUMENT, "the source ensemble is on device %d, the destination on device %d", src->device, dst->device);
+	if (copy_rules && (src->neighbourhood != dst->neighbourhood || src->clustered != dst->clustered))
+		return fail(CA3D_ERR_UNSUPPORTED, "CA3D_COMPOSE_COPY_RULES: source and destination ensemble differ in neighbourhood or in being clustered (%u and %u rule words a universe)",
+		            rule_words(src), rule_words(dst));
+	for (uint32_t k = 0; k < n_dst; k++)
+	{
+		if (over && !dst->has_state[dst_first + k])
+			return fail(CA3D_ERR_NOT_CONFIGURED, "CA3D_COMPOSE_OVER: ca3d_ensemble_upload_state has not been called for destination universe %u", dst_first + k);
+		for (uint32_t i = part_begin[k]; i < part_begin[k + 1]; i++)
+		{
+			const ca3d_compose_part &p = parts[i];
+			if (p.universe >= src->n) return fail(CA3D_ERR_INVALID_ARGUMENT, "part %u: universe %u of %u", i, p.universe, src->n);
+			if (p.orientation >= 48u) return fail(CA3D_ERR_INVALID_ARGUMENT, "part %u: orientation %u — an orientation is 0 .. 47", i, p.orientation);
+			for (int d = 0; d < 3; d++)
+				if (p.at[d] < -64 || p.at[d] > 64) return fail(CA3D_ERR_INVALID_ARGUMENT, "part %u: at[%d] = %d lies outside -64 .. 64", i, d, p.at[d]);
+			if (p.reserved != 0u) return fail(CA3D_ERR_INVALID_ARGUMENT, "part %u: reserved is %u, not 0", i, p.reserved);
+			if (src == dst && p.universe >= dst_first && p.universe - dst_first < n_dst)
+				return fail(CA3D_ERR_INVALID_ARGUMENT, "part %u: source universe %u lies among the destinations [%u, %u + %u) of the same ensemble", i, p.universe, dst_first, dst_first, n_dst);
+			if (!src->has_state[p.universe]) return fail(CA3D_ERR_NOT_CONFIGURED, "part %u: ca3d_ensemble_upload_state has not been called for source universe %u", i, p.universe);
+			if (copy_rules && i == part_begin[k] && !src->has_rules[p.universe])
+				return fail(CA3D_ERR_NOT_CONFIGURED, "part %u: ca3d_ensemble_set_rules has not been called for source universe %u", i, p.universe);
+		}
+	}
+	HIP_TRY(hipSetDevice(dst->device));
+	const size_t out_bytes = (size_t)n_dst * sizeof(ca3d_composed), part_bytes = (size_t)n_parts * sizeof(ca3d_compose_part),
+	             begin_bytes = ((size_t)n_dst + 1u) * sizeof(uint32_t);
+	int rc = size_compose(dst, out_bytes + part_bytes + begin_bytes);
+	if (rc) return rc;
+	ComposeLaunch l{};
+	l.src_state = src->state;
+	l.dst_state = dst->state; l.dst_prev = dst->prev;
+	l.src_rules = src->rules; l.dst_rules = dst->rules;
+	l.out = reinterpret_cast<ca3d_composed *>(dst->compose);
+	l.parts = reinterpret_cast<const ca3d_compose_part *>(dst->compose + out_bytes);
+	l.part_begin = reinterpret_cast<const uint32_t *>(dst->compose + out_bytes + part_bytes);
+	l.dst_first = dst_first; l.n_dst = n_dst;
+	l.over = over;
+	l.rule_words = copy_rules ? rule_words(dst) : 0u;
+	if (src != dst)
+	{
+		// behind what is queued on the source's stream now
+		HIP_TRY(hipEventRecord(dst->ev_compose_src, src->stream));
+		HIP_TRY(hipStreamWaitEvent(dst->stream, dst->ev_compose_src, 0));
+	}
+	if (n_parts) HIP_TRY(hipMemcpyAsync(dst->compose + out_bytes, parts, part_bytes, hipMemcpyHostToDevice, dst->stream));
+	HIP_TRY(hipMemcpyAsync(dst->compose + out_bytes + part_bytes, part_begin, begin_bytes, hipMemcpyHostToDevice, dst->stream));
+	HIP_TRY(hipEventRecord(dst->ev_compose_start, dst->stream));
+	HIP_TRY(launch_compose(l, dst->stream));
+	HIP_TRY(hipEventRecord(dst->ev_compose_stop, dst->stream));
+	// the records of the new states: step 0, no previous state (the launch ca3d_ensemble_upload_state ends in)
+	EnsembleLaunch r = launch_of(dst);
+	r.first = dst_first; r.count = n_dst;
+	r.reset = true;
+	r.final = true;
+	HIP_TRY(launch_ensemble(r, dst->stream));
+	if (out) HIP_TRY(hipMemcpyAsync(out, l.out, out_bytes, hipMemcpyDeviceToHost, dst->stream));
+	HIP_TRY(hipStreamSynchronize(dst->stream)); // the caller's parts are consumed, and the source may go on
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, dst->ev_compose_start, dst->ev_compose_stop));
+	for (uint32_t k = 0; k < n_dst; k++)
+	{
+		const uint32_t u = dst_first + k;
+		if (!dst->has_state[u]) { dst->has_state[u] = 1; dst->missing_state--; }
+		if (copy_rules && part_begin[k + 1] > part_begin[k] && !dst->has_rules[u]) { dst->has_rules[u] = 1; dst->missing_rules--; }
 	}
 	return CA3D_OK;
 }

@@ -256,6 +256,23 @@ struct IsolateLaunch
 	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
 };
 hipError_t launch_isolate(const IsolateLaunch &l, hipStream_t stream);
+// ca_compose.hip: destination universe dst_first + k becomes the union of parts part_begin[k] .. part_begin[k + 1] - 1, each the whole
+// state of a source universe turned and shifted (ca3d_ensemble_compose), in both buffers; one workgroup of ca_ensemble_compose64 a
+// destination. The caller has checked every universe, orientation, `at` and range, and that no source universe is a destination.
+struct ComposeLaunch
+{
+	const uint32_t *src_state;      // [Bs][8192], the source ensemble's current states
+	uint32_t *dst_state, *dst_prev; // [Bd][8192], the destination ensemble's two buffers
+	const uint32_t *src_rules;      // [Bs][rule_words] / [Bd][rule_words]: a destination with parts takes its first part's when rule_words != 0
+	uint32_t *dst_rules;
+	const ca3d_compose_part *parts; // device, [part_begin[n_dst]]
+	const uint32_t *part_begin;     // device, [n_dst + 1]
+	ca3d_composed *out;             // device, [n_dst]: every entry is written
+	uint32_t dst_first, n_dst;
+	bool over;                      // start from the destination's current state
+	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
+};
+hipError_t launch_compose(const ComposeLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

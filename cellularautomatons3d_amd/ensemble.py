@@ -253,6 +253,34 @@ class Ensemble:
         """hipEvent time of the last `isolate` launch into this object, in milliseconds (None before the first)."""
         return getattr(self, "_isolate_ms", None)
 
+    def compose(self, layouts, dst_first: int = 0, src: Optional["Ensemble"] = None, over: bool = False,
+                copy_rules: bool = True) -> np.ndarray:
+        """`ca3d_ensemble_compose`, the inverse of `isolate`: universe dst_first + k of THIS ensemble becomes the union of the pieces
+        layouts[k], a list of (universe, orientation, (x, y, z)): the WHOLE state of that universe of `src` (default: this ensemble),
+        turned by orientation 0 .. 47 (`host.orientation_matrix`) with the turned piece's box_min put at (x, y, z), -64 .. 64 each;
+        cells that leave the cube are clipped. `over`: on top of the destination's current state, else from nothing; an empty list
+        leaves it empty (or as it is). `copy_rules`: a destination takes the rule of its first piece's universe (both ensembles of one
+        kind). One launch for all destinations, at step 0 -> records [n] of `host.COMPOSED_DTYPE` (population, placed, overlap,
+        clipped). `host.compose` is the same on the CPU for one destination; `compose_gpu_ms()` tells what the launch took."""
+        begin = np.zeros(len(layouts) + 1, dtype=np.uint32)
+        flat = []
+        for k, layout in enumerate(layouts):
+            flat.extend(layout)
+            begin[k + 1] = len(flat)
+        parts = host.compose_parts(flat)
+        out = np.zeros(len(layouts), dtype=host.COMPOSED_DTYPE)
+        ms = C.c_float(0.0)
+        flags = (_capi.COMPOSE_OVER if over else 0) | (_capi.COMPOSE_COPY_RULES if copy_rules else 0)
+        _capi.check(self._lib.ca3d_ensemble_compose(self._h, dst_first, len(layouts), (self if src is None else src)._h,
+                                                    parts.ctypes.data_as(C.POINTER(_capi.ComposePartStruct)), begin.ctypes.data_as(_u32p),
+                                                    flags, out.ctypes.data_as(C.POINTER(_capi.ComposedStruct)), C.byref(ms)))
+        self._compose_ms = float(ms.value)
+        return out
+
+    def compose_gpu_ms(self) -> float:
+        """hipEvent time of the last `compose` launch into this object, in milliseconds (None before the first)."""
+        return getattr(self, "_compose_ms", None)
+
     def render_sheet(self, uniforms, tile_w: int, tile_h: int, columns: Optional[int] = None, spp: int = 1, first: int = 0,
                      count: Optional[int] = None, light: bool = False, depth: bool = False):
         """`ca3d_ensemble_render_sheet`: universes first .. first + count - 1 (default: all from `first`) as the tiles of one contact

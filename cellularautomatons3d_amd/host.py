@@ -537,6 +537,108 @@ def isolate(words, cell: int, placement: str = "centre") -> Tuple[np.ndarray, in
     return np.packbits(moved.ravel(), bitorder="little").view("<u4").astype(np.uint32), int(zs.size), (dx, dy, dz)
 
 
+# ------------------------------------------------------------------------------------------------- compose
+# The definition of ca3d_ensemble_compose (include/ca3d.h) in executable form, for one destination, and the 48 orientations it turns
+# a piece by.
+
+#: orientation o turns by the signed permutation perm = ORIENTATION_PERMS[o % 6], bit i of o // 6 mirroring OUTPUT axis i
+ORIENTATION_PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+#: ca3d_compose_part, 24 bytes, and ca3d_composed, 16 bytes (include/ca3d.h)
+COMPOSE_PART_DTYPE = np.dtype([("universe", "<u4"), ("orientation", "<u4"), ("at", "<i4", (3,)), ("reserved", "<u4")])
+COMPOSED_DTYPE = np.dtype([("population", "<u4"), ("placed", "<u4"), ("overlap", "<u4"), ("clipped", "<u4")])
+
+
+def _orientation(o) -> Tuple[Tuple[int, int, int], int]:
+    if isinstance(o, bool) or int(o) != o or not 0 <= int(o) < 48:
+        raise ValueError("an orientation is 0 .. 47")
+    return ORIENTATION_PERMS[int(o) % 6], int(o) // 6
+
+
+def orientation_matrix(o: int) -> np.ndarray:
+    """The 3 x 3 integer matrix M of orientation o: output axis i is input axis perm[i], negated where bit i of o // 6 is set, so a
+    direction v of the piece turns into M @ v. Determinant +1: a rotation; -1: a reflection."""
+    perm, f = _orientation(o)
+    m = np.zeros((3, 3), dtype=np.int64)
+    for i in range(3):
+        m[i, perm[i]] = -1 if f >> i & 1 else 1
+    return m
+
+
+def orientation_from_matrix(m) -> int:
+    """The orientation whose `orientation_matrix` is m (a signed permutation matrix; anything else is a ValueError)."""
+    m = np.asarray(m)
+    if m.shape != (3, 3) or not np.array_equal(np.abs(m).sum(axis=0), (1, 1, 1)) or not np.array_equal(np.abs(m).sum(axis=1), (1, 1, 1)) \
+            or not np.isin(m, (-1, 0, 1)).all():
+        raise ValueError("not a signed permutation matrix")
+    perm = tuple(int(np.flatnonzero(m[i])[0]) for i in range(3))
+    f = sum(1 << i for i in range(3) if m[i, perm[i]] < 0)
+    return ORIENTATION_PERMS.index(perm) + 6 * f
+
+
+def orient_vector(o: int, v) -> Tuple[int, int, int]:
+    """A direction v = (x, y, z) of a piece — a ship's shift — as it points after the piece is turned by orientation o."""
+    return tuple(int(c) for c in orientation_matrix(o) @ np.asarray(v, dtype=np.int64))
+
+
+def compose_parts(parts) -> np.ndarray:
+    """A list of (universe, orientation, (x, y, z)) as an array of COMPOSE_PART_DTYPE (reserved 0)."""
+    try:
+        flat = np.array([(u, o, at[0], at[1], at[2], len(at)) for u, o, at in parts], dtype=np.int64).reshape(-1, 6)
+    except (TypeError, IndexError, ValueError):
+        raise ValueError("a part is (universe, orientation, (x, y, z))") from None
+    if (flat[:, 5] != 3).any() or (flat[:, :2] < 0).any() or (flat[:, :2] >= 1 << 32).any() or (np.abs(flat[:, 2:5]) >= 1 << 31).any():
+        raise ValueError("a part is (universe, orientation, (x, y, z))")
+    out = np.zeros(len(flat), dtype=COMPOSE_PART_DTYPE)
+    out["universe"], out["orientation"], out["at"] = flat[:, 0], flat[:, 1], flat[:, 2:5]
+    return out
+
+
+def compose(states, parts, base=None) -> Tuple[np.ndarray, np.ndarray]:
+    """`ca3d_ensemble_compose` for ONE destination, in plain numpy. `states[u]` is the packed 64^3 state of source universe u (a
+    sequence or a dict), `parts` a list of (universe, orientation, (x, y, z)), `base` the destination's state under OVER (None: from
+    nothing) -> (words u32[8192], record of COMPOSED_DTYPE). A live cell c of a piece with box (min, max), extent e, goes to q + at:
+    r[i] = c[perm[i]] - min[perm[i]], q[i] = e[perm[i]] - 1 - r[i] where output axis i is mirrored, else r[i]; it is set when it lies
+    inside the cube and counts as clipped otherwise."""
+    G = 64
+    nw = words_per_buffer(G)
+
+    def cells(w):
+        w = np.ascontiguousarray(w, dtype="<u4").ravel()
+        if w.size != nw:
+            raise ValueError("a universe holds 8192 words")
+        return np.unpackbits(w.view(np.uint8), bitorder="little").reshape(G, G, G)  # [z, y, x]
+
+    dest = np.zeros((G, G, G), dtype=np.uint8) if base is None else cells(base).copy()
+    base_pop = int(dest.sum())
+    placed = clipped = 0
+    for universe, o, at in parts:
+        perm, f = _orientation(o)
+        at = tuple(int(v) for v in at)
+        if len(at) != 3 or not all(-64 <= v <= 64 for v in at):
+            raise ValueError("at is (x, y, z), -64 .. 64 each")
+        zs, ys, xs = np.nonzero(cells(states[universe]))
+        if zs.size == 0:
+            continue
+        c = (xs, ys, zs)
+        q = []
+        for i in range(3):
+            src = c[perm[i]]
+            r = src - src.min()
+            q.append((int(src.max()) - int(src.min()) - r if f >> i & 1 else r) + at[i])
+        inside = np.ones(zs.size, dtype=bool)
+        for v in q:
+            inside &= (v >= 0) & (v < G)
+        dest[q[2][inside], q[1][inside], q[0][inside]] = 1
+        placed += int(inside.sum())
+        clipped += int(zs.size - inside.sum())
+    rec = np.zeros((), dtype=COMPOSED_DTYPE)
+    rec["population"] = int(dest.sum())
+    rec["placed"] = placed
+    rec["overlap"] = base_pop + placed - int(dest.sum())
+    rec["clipped"] = clipped
+    return np.packbits(dest.ravel(), bitorder="little").view("<u4").astype(np.uint32), rec
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

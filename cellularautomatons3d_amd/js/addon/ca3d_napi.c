@@ -1343,6 +1343,42 @@ static napi_value js_ensemble_isolate(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* ensembleCompose(dstHandle, dstFirst, srcHandle, Int32Array(6 * nParts) parts (universe, orientation, x, y, z, 0 each),
+ * Uint32Array(nDst + 1) partBegin, flags, Uint32Array(4 * nDst) out) -> gpuMs: dst's universe dstFirst + k becomes the union of parts
+ * partBegin[k] .. partBegin[k + 1] - 1, src's universes turned and shifted (ca3d_ensemble_compose); out[4 k ..] is ca3d_composed's four
+ * words: population, placed, overlap, clipped */
+static napi_value js_ensemble_compose(napi_env env, napi_callback_info info)
+{
+	napi_value argv[7];
+	if (!get_args(env, info, 7, argv)) return NULL;
+	ca3d_ensemble_t *dst = get_ensemble(env, argv[0]);
+	if (!dst) return NULL;
+	ca3d_ensemble_t *src = get_ensemble(env, argv[2]);
+	uint32_t dst_first, flags;
+	void *parts, *begin, *out;
+	size_t nparts, nbegin, nout;
+	if (!src || !get_u32(env, argv[1], &dst_first) || !get_typed(env, argv[3], napi_int32_array, 0, &parts, &nparts) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 0, &begin, &nbegin) || !get_u32(env, argv[5], &flags) ||
+	    !get_typed(env, argv[6], napi_uint32_array, 0, &out, &nout))
+		return NULL;
+	/* the library reads partBegin[0 .. nDst] and parts[0 .. partBegin[nDst]): both must lie inside the arrays given */
+	if (nbegin < 1u || nbegin - 1u > 0xFFFFFFFFu || nout != 4u * (nbegin - 1u) || nparts % 6u ||
+	    (nbegin > 1u && (size_t)((const uint32_t *)begin)[nbegin - 1u] > nparts / 6u))
+	{
+		napi_throw_range_error(env, NULL, "parts must hold six words a part, partBegin one entry a destination and one more, its last no more than the parts, out four words a destination");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_compose_part) == 24 && sizeof(ca3d_composed) == 16, "a part crosses as six words, a record as four");
+	float ms = 0.f;
+	/* (no destination: the library refuses the call and names the reason; it reads no array) */
+	int rc = ca3d_ensemble_compose(dst, dst_first, (uint32_t)(nbegin - 1u), src, (const ca3d_compose_part *)parts, (const uint32_t *)begin, flags,
+	                               (ca3d_composed *)out, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1565,7 +1601,7 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleConfigureClustered", js_ensemble_configure_clustered}, {"ensembleClustered", js_ensemble_clustered},
 	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables},
 	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats},
-	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}};
+	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}, {"ensembleCompose", js_ensemble_compose}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

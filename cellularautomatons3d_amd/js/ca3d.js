@@ -231,6 +231,7 @@ const STOP_MOVING = 8; // ... and of ca3d_ensemble_step_until_moving (Ensemble.s
 
 const ISOLATE_PLACEMENTS = ["keep", "centre", "origin"]; // index = CA3D_ISOLATE_KEEP / CENTRE / ORIGIN (Ensemble.isolate)
 const ISOLATE_COPY_RULES = 0x100;
+const COMPOSE_OVER = 0x1, COMPOSE_COPY_RULES = 0x100; // CA3D_COMPOSE_OVER / CA3D_COMPOSE_COPY_RULES (Ensemble.compose)
 
 class Engine
 {
@@ -589,6 +590,35 @@ class Ensemble
 			shift.set(out.subarray(4 * k + 1, 4 * k + 4), 3 * k);
 		}
 		return { population, shift, gpuMs };
+	}
+	/** Compose (ca3d_ensemble_compose), the inverse of isolate: universe dstFirst + k of THIS ensemble becomes the union of the pieces
+	 *  layouts[k], an array of [universe, orientation, [x, y, z]]: the WHOLE state of that universe of opts.src (default: this ensemble),
+	 *  turned by orientation 0 .. 47 (perm = PERMS[o % 6], bit i of floor(o / 6) mirrors output axis i) with the turned piece's boxMin
+	 *  put at [x, y, z], -64 .. 64 each; cells that leave the cube are clipped. opts.over (default false): on top of the destination's
+	 *  current state; opts.copyRules (default true): a destination takes the rule of its first piece's universe (both ensembles of one
+	 *  kind); opts.dstFirst: 0. One launch for all destinations, at step 0
+	 *  -> {population, placed, overlap, clipped: Uint32Array(n) each, gpuMs}. */
+	compose(layouts, opts)
+	{
+		const o = Object.assign({ dstFirst: 0, src: null, over: false, copyRules: true }, opts || {});
+		const n = layouts.length;
+		const begin = new Uint32Array(n + 1);
+		const flat = [];
+		layouts.forEach((layout, k) =>
+		{
+			for (const part of layout)
+			{
+				if (!Array.isArray(part) || part.length !== 3 || part[2].length !== 3) throw new RangeError("a part is [universe, orientation, [x, y, z]]");
+				flat.push(part[0], part[1], part[2][0], part[2][1], part[2][2], 0);
+			}
+			begin[k + 1] = flat.length / 6;
+		});
+		const out = new Uint32Array(4 * n);
+		const gpuMs = this._a.ensembleCompose(this._e, o.dstFirst, (o.src || this)._e, Int32Array.from(flat), begin,
+			(o.over ? COMPOSE_OVER : 0) | (o.copyRules ? COMPOSE_COPY_RULES : 0), out);
+		const r = { population: new Uint32Array(n), placed: new Uint32Array(n), overlap: new Uint32Array(n), clipped: new Uint32Array(n), gpuMs };
+		for (let k = 0; k < n; k++) { r.population[k] = out[4 * k]; r.placed[k] = out[4 * k + 1]; r.overlap[k] = out[4 * k + 2]; r.clipped[k] = out[4 * k + 3]; }
+		return r;
 	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at

@@ -578,6 +578,67 @@ enum
 #define CA3D_ISOLATE_COPY_RULES 0x100u
 int ca3d_ensemble_isolate(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensemble_t *src, uint32_t n_jobs, const ca3d_isolate_job *jobs, uint32_t flags,
                           ca3d_isolated *out /* [n_jobs], may be NULL */, float *gpu_ms /* may be NULL */);
+/*
+ * Compose (no reference counterpart): the inverse of isolate. A destination universe becomes the union of several pieces, each the
+ * WHOLE current state of a source universe — usually an isolated object — turned by one of the 48 symmetries of the cube and put where
+ * the caller says, without a state leaving the device: a glider thrown at a block from every direction, two ships on a collision
+ * course, an object dropped into a living soup. One launch of ca_ensemble_compose64 (csrc/ca_compose.hip, one workgroup a destination)
+ * for all destinations of a call. host.compose restates it in plain numpy; host.orientation_matrix, orientation_from_matrix and
+ * orient_vector speak about the orientations.
+ *
+ * The definition. Destination dst_first + k of `dst` takes parts part_begin[k] .. part_begin[k + 1] - 1; part_begin[0] is 0 and the
+ *   array does not decrease. A destination with no parts becomes empty, or stays as it is under CA3D_COMPOSE_OVER.
+ *   Orientation o is a signed permutation: perm = PERMS[o % 6] with PERMS = (0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0), and
+ *   bit i of f = o / 6 mirrors OUTPUT axis i. With the piece's bounding box (min, max) and extent e = max - min + 1, a live cell c of
+ *   the piece goes to q + at, where
+ *     r[i] = c[perm[i]] - min[perm[i]],   e'[i] = e[perm[i]],   q[i] = e'[i] - 1 - r[i] when bit i of f is set, else r[i]:
+ *   `at` is where box_min of the TURNED piece goes. The cell is set when all three coordinates lie in 0 .. 63; otherwise it counts as
+ *   clipped. An empty piece contributes nothing. Orientation 0 with at = min reproduces the piece; the 24 orientations whose matrix
+ *   has determinant +1 are the rotations, the other 24 reflections.
+ *   The result is the OR of the base (zero, or the destination's current state under CA3D_COMPOSE_OVER) and all parts: it does not
+ *   depend on the order of the parts. Both ping-pong buffers get the words; the destinations' records are rebuilt at step 0 with no
+ *   previous state (the launch ca3d_ensemble_upload_state and ca3d_ensemble_isolate end in), and they count as having a state.
+ *   CA3D_COMPOSE_COPY_RULES: a destination takes the stored rule words of its FIRST part's source universe, on the device, under
+ *   isolate's conditions — both ensembles of one kind, every source universe named by a first part with rules; those destinations
+ *   count as having rules afterwards. A destination without parts keeps the rules it has.
+ *   out[k] (nullable array): population of the destination afterwards; placed, the cells of its parts that landed inside the cube,
+ *   summed over the parts; overlap = base population + placed - population, the cells that landed on a live cell; clipped, the cells
+ *   of its parts that fell outside the cube (all four modulo 2^32).
+ *
+ * `src` and `dst` may be the same handle or two handles on the same device; when they are the same no part's universe may lie in
+ * [dst_first, dst_first + n_dst). Ordering is isolate's: the launch runs on dst's stream behind what is queued there and behind what
+ * is queued on src's stream at the time of the call, and the call waits for dst's stream. gpu_ms (nullable) receives the hipEvent time
+ * around the launch. Records, parts and part_begin are staged in one device array on dst's handle (grown when a call needs more,
+ * freed by a configure and by destroy).
+ *
+ * Errors — everything is checked before anything is queued; a refused call touches neither ensemble nor `out`: a NULL handle, a NULL
+ * part_begin, NULL parts where there are parts, n_dst == 0 or more destinations than fit behind dst_first, part_begin[0] != 0 or a
+ * decreasing part_begin, more than 1 << 20 parts, a `universe` out of range, orientation >= 48, an `at` outside -64 .. 64, reserved
+ * != 0, an unknown flag bit, handles on different devices, a source universe among the destinations — CA3D_ERR_INVALID_ARGUMENT;
+ * either ensemble not configured, a source universe without a state, CA3D_COMPOSE_OVER on a destination without a state, with
+ * CA3D_COMPOSE_COPY_RULES a first part's source without rules — CA3D_ERR_NOT_CONFIGURED; with CA3D_COMPOSE_COPY_RULES ensembles of
+ * different kinds — CA3D_ERR_UNSUPPORTED.
+ */
+typedef struct ca3d_compose_part
+{
+	uint32_t universe;    /* of src: its whole current state is the piece */
+	uint32_t orientation; /* 0 .. 47 */
+	int32_t at[3];        /* x, y, z: where box_min of the TURNED piece goes; -64 .. 64 each */
+	uint32_t reserved;    /* 0 */
+} ca3d_compose_part;      /* 24 bytes */
+typedef struct ca3d_composed
+{
+	uint32_t population; /* of the destination afterwards */
+	uint32_t placed;     /* cells of its parts that landed inside the cube, summed over parts */
+	uint32_t overlap;    /* base population + placed - population: cells that landed on a live cell */
+	uint32_t clipped;    /* cells of its parts that fell outside the cube */
+} ca3d_composed;         /* 16 bytes */
+#define CA3D_COMPOSE_OVER 0x1u         /* start from the destination's current state, not from zero */
+#define CA3D_COMPOSE_COPY_RULES 0x100u /* a destination takes the rule of its FIRST part's source universe */
+#define CA3D_COMPOSE_MAX_PARTS (1u << 20)
+int ca3d_ensemble_compose(ca3d_ensemble_t *dst, uint32_t dst_first, uint32_t n_dst, ca3d_ensemble_t *src, const ca3d_compose_part *parts,
+                          const uint32_t *part_begin /* [n_dst + 1] */, uint32_t flags, ca3d_composed *out /* [n_dst], may be NULL */,
+                          float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

@@ -72,6 +72,17 @@ ensemble must hold what the call left there. Reported: medians of --repeats meas
 around the call, and of the host clock around the loop. No ratio is required. Written to profiles/ensemble_isolate_64.json unless --out
 says otherwise.
 
+--compose measures the compose (ca3d_ensemble_compose, kernel ca_ensemble_compose64: whole universes staged, turned and shifted, into
+universes of their union) on the objects of --isolate: the ash of B = 256 universes, a census, EVERY object isolated (centred) into a
+nursery whose last universe holds a 2 x 2 x 2 block, then one destination an object, each of two parts — the object, turned, and the
+block — in one call. Three mixes of orientations: all 48 (k % 48), the eight that leave x on x, and the other forty; and, beside them,
+one part at orientation 0 (the bytes isolate writes) and the isolate launch on the same objects; and the dense case, 4096 destinations
+of one whole soup each (and_rounds 1), for the eight and for the forty, without a loop beside it. Against the loop it replaces on the same
+layouts, on the first --loop-destinations destinations: read_state of the sources, host.compose, upload_state. Before timing, states
+and records must equal host.compose in sampled destinations, and after the loop the destinations must hold what the call left there.
+Reported: medians of --repeats measurements. No ratio is required. Written to profiles/ensemble_compose_64.json unless --out says
+otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -526,6 +537,103 @@ def isolate_rows(args):
     return rows, cutter
 
 
+def compose_rows(args):
+    """compose against the read_state + host.compose + upload_state loop: one row per B and mix of orientations. -> rows"""
+    M = 1024
+    born, survive, rounds = CENSUS_ASH["ash B6/S5-7"]
+    x_keeping = [o for o in range(48) if host.ORIENTATION_PERMS[o % 6][0] == 0]
+    mixes = {"all 48": list(range(48)), "the 8 that leave x on x": x_keeping, "the other 40": [o for o in range(48) if o not in x_keeping],
+             "one part, orientation 0": None}
+    block = host.cells_to_words(G, [(i, j, k) for i in (0, 1) for j in (0, 1) for k in (0, 1)])
+    ens, nursery, stage = Ensemble(0), Ensemble(0), Ensemble(0)
+    rows = []
+    for B in args.universes:
+        ens.configure(B, neighbourhood="moore")
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        ens.seed_states(0, np.arange(1, B + 1), rounds)
+        done, reason, _ = ens.step_until_cycle(512)
+        comps, n, rest = ens.census(max_components=M)
+        if rest.any():
+            raise SystemExit(f"B {B}: a census of {M} objects a universe is not complete")
+        jobs = np.array([(u, int(c["first_cell"])) for u in range(B) for c in comps[u, :n[u]]], dtype=np.uint32).reshape(-1, 2)
+        J = len(jobs)
+        nursery.configure(J + 1, neighbourhood="moore")
+        nursery.upload_state(J, block)
+        nursery.set_rule_strings(J, neighbourhood="moore", born=born, survive=survive)
+        pop, _ = nursery.isolate(jobs, 0, ens, "centre", True)
+        iso = []
+        for _ in range(args.repeats):
+            nursery.isolate(jobs, 0, ens, "centre", True)
+            iso.append(nursery.isolate_gpu_ms())
+        stage.configure(J, neighbourhood="moore")
+        L = min(args.loop_destinations, J)
+        for name, mix in mixes.items():
+            if mix is None:
+                layouts = [[(k, 0, (8, 8, 8))] for k in range(J)]
+            else:
+                layouts = [[(k, mix[k % len(mix)], (8 + k % 24, 8, 8)), (J, 0, (48, 48, 48))] for k in range(J)]
+            recs = stage.compose(layouts, 0, nursery, False, True)
+            sample = sorted({0, 1, J // 3, J // 2, J - 2, J - 1} | set(range(100, 148)))
+            for k in sample:
+                pieces = {u: nursery.read_state(u, 1)[0] for u, _, _ in layouts[k]}
+                w, r = host.compose(pieces, layouts[k])
+                if not np.array_equal(stage.read_state(k, 1)[0], w) or recs[k].tolist() != r.tolist():
+                    raise SystemExit(f"B {B}, {name}: destination {k} is not host.compose's")
+            left = stage.read_state(0, L)
+            gpu, wall, loop = [], [], []
+            for _ in range(args.repeats):
+                t0 = time.perf_counter()
+                stage.compose(layouts, 0, nursery, False, True)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                gpu.append(stage.compose_gpu_ms())
+                t0 = time.perf_counter()
+                for k in range(L):
+                    pieces = {u: nursery.read_state(u, 1)[0] for u, _, _ in layouts[k]}
+                    stage.upload_state(k, host.compose(pieces, layouts[k])[0])
+                loop.append((time.perf_counter() - t0) * 1e3)
+                if not np.array_equal(stage.read_state(0, L), left):
+                    raise SystemExit(f"B {B}, {name}: the loop left other states than the call")
+            row = {"workload": "ash B6/S5-7", "universes": B, "mix": name, "destinations": J, "parts_per_destination": len(layouts[0]),
+                   "cells_per_object_median": float(np.median(pop)), "clipped_cells": int(recs["clipped"].sum()),
+                   "verified_against_host_compose_in": len(sample),
+                   "compose_gpu_ms": statistics.median(gpu), "compose_gpu_ms_all": gpu,
+                   "compose_wall_ms": statistics.median(wall), "compose_wall_ms_all": wall,
+                   "isolate_gpu_ms_same_objects": statistics.median(iso), "isolate_gpu_ms_same_objects_all": iso,
+                   "loop_destinations": L, "loop_wall_ms": statistics.median(loop), "loop_wall_ms_all": loop,
+                   "loop_wall_ms_per_destination": statistics.median(loop) / L,
+                   "compose_wall_ms_per_destination": statistics.median(wall) / J}
+            rows.append(row)
+            print(json.dumps(row))
+        # the dense case: whole soups, one part a destination, where every bit of the gather is a cell
+        D = 4096
+        ens.seed_states(0, np.arange(1, B + 1), 1)
+        stage.configure(D, neighbourhood="moore")
+        for name in ("the 8 that leave x on x", "the other 40"):
+            mix = mixes[name]
+            layouts = [[(k % B, mix[k % len(mix)], (k % 5 - 2, 0, 0))] for k in range(D)]
+            recs = stage.compose(layouts, 0, ens, False, True)
+            sample = list(range(0, D, D // 48))
+            for k in sample:
+                w, r = host.compose({layouts[k][0][0]: ens.read_state(layouts[k][0][0], 1)[0]}, layouts[k])
+                if not np.array_equal(stage.read_state(k, 1)[0], w) or recs[k].tolist() != r.tolist():
+                    raise SystemExit(f"B {B}, soups, {name}: destination {k} is not host.compose's")
+            gpu, wall = [], []
+            for _ in range(args.repeats):
+                t0 = time.perf_counter()
+                stage.compose(layouts, 0, ens, False, True)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                gpu.append(stage.compose_gpu_ms())
+            row = {"workload": "soups, and_rounds 1 (65 536 cells, box 64^3)", "universes": B, "mix": name, "destinations": D, "parts_per_destination": 1,
+                   "clipped_cells": int(recs["clipped"].sum()), "verified_against_host_compose_in": len(sample),
+                   "compose_gpu_ms": statistics.median(gpu), "compose_gpu_ms_all": gpu,
+                   "compose_wall_ms": statistics.median(wall), "compose_wall_ms_all": wall, "loop_wall_ms": None}
+            rows.append(row)
+            print(json.dumps(row))
+    for e in (ens, nursery, stage):
+        e.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -541,10 +649,12 @@ def main():
     ap.add_argument("--sheet", action="store_true", help="measure render_sheet against the upload + render loop instead (B = 256 1024)")
     ap.add_argument("--census", action="store_true", help="measure census against read_state + labelling on the CPU instead (B = 256 1024)")
     ap.add_argument("--isolate", action="store_true", help="measure isolate against the read_state + cut + upload_state loop instead (B = 256)")
+    ap.add_argument("--compose", action="store_true", help="measure compose against the read_state + host.compose + upload_state loop instead (B = 256)")
+    ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose: destinations the CPU loop is run on")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -560,6 +670,27 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.compose:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_compose_64.json")
+        rows = compose_rows(args)
+        result = {
+            "what": "B universes of 64^3 of ash (seed_states, seeds 1 .. B, and_rounds 1, Moore B6/S5-7, step_until_cycle(512)), a census at max_components 1024, every "
+                    "object isolated (centred) into a nursery, then one destination an object composed of two parts — the object, turned, and a 2 x 2 x 2 block — "
+                    "with the object's rule, in ONE Ensemble.compose call — one launch of ca_ensemble_compose64 and the reset launch — vs. the loop it replaces "
+                    "on the same layouts, run on the first loop_destinations destinations: read_state of the sources, host.compose, upload_state",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"compose": "ca_ensemble_compose64", "isolate": "ca_ensemble_isolate64"},
+            "timing": f"compose_gpu_ms / isolate_gpu_ms_same_objects: hipEvent time around the launch; *_wall_ms: host clock around the call / the loop; medians of "
+                      f"{args.repeats} alternating measurements after states and records equalled host.compose in the sampled destinations; after each loop its "
+                      "destinations held what the call had left there",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.isolate:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_isolate_64.json")
         rows, cutter = isolate_rows(args)
