@@ -89,6 +89,12 @@ class ComposedStruct(C.Structure):
     _fields_ = [("population", C.c_uint32), ("placed", C.c_uint32), ("overlap", C.c_uint32), ("clipped", C.c_uint32)]
 
 
+class CanonStruct(C.Structure):
+    """ca3d_canon (include/ca3d.h): what `ca3d_ensemble_canon` says of one universe, 32 bytes (`host.CANON_DTYPE`)."""
+    _fields_ = [("key", C.c_uint64), ("symmetry", C.c_uint64), ("orientation", C.c_uint32), ("population", C.c_uint32),
+                ("box_min", C.c_uint32), ("box_max", C.c_uint32)]
+
+
 #: the flag bits of `ca3d_ensemble_compose`, and the most parts a call takes
 COMPOSE_OVER = 0x1
 COMPOSE_COPY_RULES = 0x100
@@ -199,6 +205,7 @@ SYMBOLS = [
                                         C.POINTER(C.c_float)]),
     ("ca3d_ensemble_compose", C.c_int, [_H, C.c_uint32, C.c_uint32, _H, C.POINTER(ComposePartStruct), _u32p, C.c_uint32,
                                         C.POINTER(ComposedStruct), C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_canon", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(CanonStruct), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

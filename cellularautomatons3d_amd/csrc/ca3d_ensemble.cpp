@@ -8,6 +8,7 @@
 // ca3d_ensemble_census lists the connected objects of a range of universes (ca_census.hip).
 // ca3d_ensemble_isolate makes objects a census named the only thing in universes of their own (ca_isolate.hip).
 // ca3d_ensemble_compose stages whole universes, turned and shifted, into universes of their union (ca_compose.hip).
+// ca3d_ensemble_canon names universes up to the 48 symmetries of the cube and translation (ca_canon.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -75,6 +76,11 @@ struct ca3d_ensemble
 	uint8_t *compose = nullptr;
 	size_t compose_bytes = 0;
 	hipEvent_t ev_compose_start = nullptr, ev_compose_stop = nullptr, ev_compose_src = nullptr;
+	// ca3d_ensemble_canon: the result of the call under way — [count] records of 32 bytes, then [count][48] digests — in one device array
+	// of canon_bytes bytes, grown when a call needs more, gone with the other arrays at a configure; its event pair
+	uint8_t *canon = nullptr;
+	size_t canon_bytes = 0;
+	hipEvent_t ev_canon_start = nullptr, ev_canon_stop = nullptr;
 };
 
 namespace
@@ -106,6 +112,9 @@ void free_arrays(ca3d_ensemble *e)
 	if (e->compose) hipFree(e->compose);
 	e->compose = nullptr;
 	e->compose_bytes = 0;
+	if (e->canon) hipFree(e->canon);
+	e->canon = nullptr;
+	e->canon_bytes = 0;
 	e->n = 0;
 	e->timed = false;
 }
@@ -459,6 +468,16 @@ int size_compose(ca3d_ensemble *e, size_t bytes)
 	return refused == hipSuccess ? rc : fail(rc, "allocating %zu bytes of compose parts: %s", bytes, hipGetErrorString(refused));
 }
 
+// room for the records and digests of a canon call, `bytes` bytes
+int size_canon(ca3d_ensemble *e, size_t bytes)
+{
+	if (!e->ev_canon_start) HIP_TRY(hipEventCreate(&e->ev_canon_start));
+	if (!e->ev_canon_stop) HIP_TRY(hipEventCreate(&e->ev_canon_stop));
+	hipError_t refused;
+	const int rc = grow_scratch(e, e->canon, e->canon_bytes, bytes, &refused);
+	return refused == hipSuccess ? rc : fail(rc, "allocating %zu bytes of canon records: %s", bytes, hipGetErrorString(refused));
+}
+
 } // namespace
 
 extern "C"
@@ -513,6 +532,8 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	if (e->ev_compose_start) hipEventDestroy(e->ev_compose_start);
 	if (e->ev_compose_stop) hipEventDestroy(e->ev_compose_stop);
 	if (e->ev_compose_src) hipEventDestroy(e->ev_compose_src);
+	if (e->ev_canon_start) hipEventDestroy(e->ev_canon_start);
+	if (e->ev_canon_stop) hipEventDestroy(e->ev_canon_stop);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
 	return CA3D_OK;
@@ -1069,6 +1090,32 @@ int ca3d_ensemble_compose(ca3d_ensemble_t *dst, uint32_t dst_first, uint32_t n_d
 		if (!dst->has_state[u]) { dst->has_state[u] = 1; dst->missing_state--; }
 		if (copy_rules && part_begin[k + 1] > part_begin[k] && !dst->has_rules[u]) { dst->has_rules[u] = 1; dst->missing_rules--; }
 	}
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_canon(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_canon *out, uint64_t *digests, float *gpu_ms) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	if ((rc = require_state(e, first, count))) return rc;
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t rec_bytes = (size_t)count * sizeof(ca3d_canon), dig_bytes = (size_t)count * 48u * sizeof(uint64_t);
+	if ((rc = size_canon(e, rec_bytes + dig_bytes))) return rc;
+	CanonLaunch l{};
+	l.state = e->state;
+	l.first = first; l.count = count;
+	l.out = reinterpret_cast<ca3d_canon *>(e->canon);
+	l.digests = digests ? reinterpret_cast<uint64_t *>(e->canon + rec_bytes) : nullptr;
+	HIP_TRY(hipEventRecord(e->ev_canon_start, e->stream));
+	HIP_TRY(launch_canon(l, e->stream));
+	HIP_TRY(hipEventRecord(e->ev_canon_stop, e->stream));
+	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, e->stream));
+	if (digests) HIP_TRY(hipMemcpyAsync(digests, l.digests, dig_bytes, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->ev_canon_start, e->ev_canon_stop));
 	return CA3D_OK;
 }
 CA3D_API_CATCH

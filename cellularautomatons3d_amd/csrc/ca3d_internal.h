@@ -273,6 +273,17 @@ struct ComposeLaunch
 	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
 };
 hipError_t launch_compose(const ComposeLaunch &l, hipStream_t stream);
+// ca_canon.hip: the key, orientation and symmetry group of universes [first, first + count) of an ensemble's state array
+// (ca3d_ensemble_canon), one workgroup of ca_ensemble_canon64 each; out and digests are indexed by universe - first. The caller has
+// checked the range. The states are only read.
+struct CanonLaunch
+{
+	const uint32_t *state; // [B][8192], the ensemble's current states
+	uint32_t first, count;
+	ca3d_canon *out;       // device, [count]: every entry is written
+	uint64_t *digests;     // device, [count][48], or null: the digest of every orientation
+};
+hipError_t launch_canon(const CanonLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

@@ -18,6 +18,10 @@
 //    of the turned box only, so a small object costs a few reads a row.
 // The image is two planes of words, [word][z][y] with 65 words a plane of rows: lanes that run along the piece's y are 1 word apart,
 // lanes that run along its z 65 — both reach 32 different banks; with the natural [z][y][2] they would be 128 words apart, one bank.
+//
+// ca_canon.hip carries the image, the map and the row assembly written out, with at = 0: as an include shared by both
+// kernels the text changed this kernel's register allocation and instruction count, so it stays here as it was
+// measured: change that text with this one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

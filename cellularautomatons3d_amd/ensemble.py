@@ -281,6 +281,60 @@ class Ensemble:
         """hipEvent time of the last `compose` launch into this object, in milliseconds (None before the first)."""
         return getattr(self, "_compose_ms", None)
 
+    def canon(self, first: int = 0, count: Optional[int] = None, digests: bool = False):
+        """`ca3d_ensemble_canon`: the name of universes first .. first + count - 1 (default: all from `first`) up to the 48 orientations
+        of `compose` and any translation, found on the device in one launch behind the queued steps -> records [count] of
+        `host.CANON_DTYPE`: `key`, equal for all turned and shifted copies of a state — `np.unique(rec["key"], return_counts=True)` is a
+        catalogue; `orientation`, which turns the state into the one whose digest is the key; `symmetry`, bit o set when turning by o
+        leaves the state as it is (`host.symmetry_orientations`, `host.is_chiral`); population, box_min, box_max as in a census record.
+        The WHOLE state of a universe is named: isolate objects first. With `digests` -> (records, digests u64[count, 48]), the digest
+        of every orientation. `host.canon` is the same on the CPU for one universe. The call only reads; `canon_gpu_ms()` tells what
+        the launch took."""
+        count = self.n - first if count is None else count
+        rec = np.zeros(max(count, 0), dtype=host.CANON_DTYPE)
+        dig = np.zeros((max(count, 0), 48), dtype=np.uint64) if digests else None
+        ms = C.c_float(0.0)
+        _capi.check(self._lib.ca3d_ensemble_canon(self._h, first, count, rec.ctypes.data_as(C.POINTER(_capi.CanonStruct)),
+                                                  dig.ctypes.data_as(C.POINTER(C.c_uint64)) if digests else None, C.byref(ms)))
+        self._canon_ms = float(ms.value)
+        return (rec, dig) if digests else rec
+
+    def canon_gpu_ms(self) -> float:
+        """hipEvent time of the last `canon` launch of this object, in milliseconds (None before the first)."""
+        return getattr(self, "_canon_ms", None)
+
+    def canon_phases(self, periods, first: int = 0, count: Optional[int] = None,
+                     max_period: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """`canon` over a whole period, for universes already classified as oscillators or ships (`step_until_cycle`,
+        `step_until_moving`): universe first + k takes the smallest key over its phases t = 0 .. periods[k] - 1
+        -> (key u64[count], phase u32[count], orientation u32[count], symmetry u64[count]), with the phase, orientation and symmetry
+        of the smallest t that reaches the key. All phases of all 48 turned copies of a glider then share one key.
+
+        WHAT IT COSTS AND CHANGES: max(periods) `canon` launches with a `step(1)` behind each. `step` has no range, so afterwards
+        EVERY universe of the ensemble, inside the range or not, is max(periods) steps further — a universe of the range is back in
+        its phase 0 only when max(periods) is a multiple of its period — and every universe needs rules. A ship must stay clear of
+        the faces for that long: `isolate`'s centred placement leaves about 30 cells. A period of 0, or max(periods) > `max_period`,
+        is a ValueError before anything is queued."""
+        count = self.n - first if count is None else count
+        p = np.ascontiguousarray(_as_u32(periods)).ravel()
+        if p.size != count:
+            raise ValueError("periods holds one period for every universe of the range")
+        if p.size == 0 or int(p.min()) == 0:
+            raise ValueError("a period is at least 1")
+        if int(p.max()) > max_period:
+            raise ValueError(f"the largest period is {int(p.max())}: more than max_period = {max_period}")
+        key = np.full(count, np.iinfo(np.uint64).max, dtype=np.uint64)
+        phase, orientation = (np.zeros(count, dtype=np.uint32) for _ in range(2))
+        symmetry = np.zeros(count, dtype=np.uint64)
+        for t in range(int(p.max())):
+            rec = self.canon(first, count)
+            # strictly smaller, or the first round: the smallest t that reaches the key keeps it
+            better = (t < p) & ((rec["key"] < key) | (t == 0))
+            key[better], phase[better] = rec["key"][better], t
+            orientation[better], symmetry[better] = rec["orientation"][better], rec["symmetry"][better]
+            self.step(1)
+        return key, phase, orientation, symmetry
+
     def render_sheet(self, uniforms, tile_w: int, tile_h: int, columns: Optional[int] = None, spp: int = 1, first: int = 0,
                      count: Optional[int] = None, light: bool = False, depth: bool = False):
         """`ca3d_ensemble_render_sheet`: universes first .. first + count - 1 (default: all from `first`) as the tiles of one contact

@@ -639,6 +639,92 @@ def compose(states, parts, base=None) -> Tuple[np.ndarray, np.ndarray]:
     return np.packbits(dest.ravel(), bitorder="little").view("<u4").astype(np.uint32), rec
 
 
+# ------------------------------------------------------------------------------------------------- canon
+# The definition of ca3d_ensemble_canon (include/ca3d.h) in executable form, for one universe: a state's name up to the 48 orientations
+# and translation, and its symmetry group.
+
+#: ca3d_canon (include/ca3d.h), 32 bytes
+CANON_DTYPE = np.dtype([("key", "<u8"), ("symmetry", "<u8"), ("orientation", "<u4"), ("population", "<u4"), ("box_min", "<u4"),
+                        ("box_max", "<u4")])
+
+
+def _box_digest(box: np.ndarray) -> int:
+    """`state_summary(64, words)["digest"]` of the 64^3 state that holds the cells `box` [z, y, x] (u8, at most 64 each way) at the
+    origin and nothing else: only the box's rows are packed and mixed."""
+    ez, ey, ex = box.shape
+    rows = np.zeros((ez, ey, 64), dtype=np.uint8)
+    rows[:, :, :ex] = box
+    w = np.packbits(rows, axis=-1, bitorder="little").view("<u4").reshape(ez, ey, 2)
+    index = ((np.arange(ez, dtype=np.uint64)[:, None, None] * np.uint64(64) + np.arange(ey, dtype=np.uint64)[None, :, None]) * np.uint64(2)
+             + np.arange(2, dtype=np.uint64)[None, None, :])
+    live = w != 0
+    with np.errstate(over="ignore"):
+        z = (index[live] << np.uint64(32)) | w[live].astype(np.uint64)
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+        return int(np.add.reduce(z, dtype=np.uint64))
+
+
+def canon(words) -> Tuple[np.ndarray, np.ndarray]:
+    """`ca3d_ensemble_canon` for ONE packed 64^3 universe, in plain numpy -> (record of CANON_DTYPE, digests u64[48]). With T_o the state
+    turned by orientation o, the turned box's minimum at the origin (`compose([S], [(0, o, (0, 0, 0))])[0]`): digests[o] is
+    `state_summary(64, T_o)["digest"]`, key the smallest of them, orientation the smallest o that reaches it, bit o of symmetry set
+    exactly when T_o equals T_0 cell for cell. An empty universe: key 0, orientation 0, all 48 symmetry bits, boxes 0. The state is
+    cropped to its bounding box before it is turned: a small object costs microseconds an orientation."""
+    G = 64
+    w = np.ascontiguousarray(words, dtype="<u4").ravel()
+    if w.size != words_per_buffer(G):
+        raise ValueError("a universe holds 8192 words")
+    rec = np.zeros((), dtype=CANON_DTYPE)
+    digests = np.zeros(48, dtype=np.uint64)
+    cells = np.unpackbits(w.view(np.uint8), bitorder="little").reshape(G, G, G)  # [z, y, x]
+    zs, ys, xs = (np.flatnonzero(cells.any(axis=a)) for a in ((1, 2), (0, 2), (0, 1)))
+    if zs.size == 0:
+        rec["symmetry"] = (1 << 48) - 1
+        return rec, digests
+    lo, hi = (int(xs[0]), int(ys[0]), int(zs[0])), (int(xs[-1]), int(ys[-1]), int(zs[-1]))
+    box = cells[lo[2]:hi[2] + 1, lo[1]:hi[1] + 1, lo[0]:hi[0] + 1]
+    symmetry = 0
+    turned0 = None
+    for o in range(48):
+        perm, f = _orientation(o)
+        # output coordinate i is input coordinate perm[i]; array axis a holds coordinate 2 - a
+        t = np.transpose(box, tuple(2 - perm[2 - a] for a in range(3)))
+        mirrored = tuple(2 - i for i in range(3) if f >> i & 1)
+        if mirrored:
+            t = np.flip(t, axis=mirrored)
+        if o == 0:
+            turned0 = t
+        if t.shape == turned0.shape and np.array_equal(t, turned0):
+            symmetry |= 1 << o
+        digests[o] = _box_digest(t)
+    rec["key"] = digests.min()
+    rec["orientation"] = int(np.argmin(digests))  # the first of equal minima
+    rec["symmetry"] = symmetry
+    rec["population"] = int(box.sum(dtype=np.uint64))
+    rec["box_min"] = lo[0] | lo[1] << 8 | lo[2] << 16
+    rec["box_max"] = hi[0] | hi[1] << 8 | hi[2] << 16
+    return rec, digests
+
+
+def symmetry_orientations(mask: int) -> List[int]:
+    """The orientations 0 .. 47 whose bit is set in a `ca3d_canon.symmetry` mask, ascending: the state's symmetry group."""
+    mask = int(mask)
+    return [o for o in range(48) if mask >> o & 1]
+
+
+def is_chiral(mask: int) -> bool:
+    """True when the symmetry group `mask` holds no orientation with determinant -1: the state differs from its mirror image however
+    that is turned."""
+    def mirrors(o):  # the determinant: the permutation's sign (odd: one transposition) times -1 for every mirrored axis
+        perm, f = _orientation(o)
+        return (sum(perm[i] != i for i in range(3)) == 2) != (bin(f).count("1") & 1 == 1)
+
+    return not any(mirrors(o) for o in symmetry_orientations(mask))
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

@@ -1379,6 +1379,36 @@ static napi_value js_ensemble_compose(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* ensembleCanon(handle, first, count, Uint32Array(count * 8) records, Uint32Array(count * 96) digests or null) -> gpuMs: the name of
+ * universes [first, first + count) up to the 48 orientations and translation (ca3d_ensemble_canon); a record is ca3d_canon's eight
+ * words: key low, key high, symmetry low, symmetry high, orientation, population, boxMin, boxMax; a digest crosses as low word, high
+ * word (js/ca3d.js opens them) */
+static napi_value js_ensemble_canon(napi_env env, napi_callback_info info)
+{
+	napi_value argv[5];
+	if (!get_args(env, info, 5, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, count;
+	void *recs, *dig;
+	size_t nrecs, ndig;
+	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count) || !get_typed(env, argv[3], napi_uint32_array, 0, &recs, &nrecs) ||
+	    !get_typed(env, argv[4], napi_uint32_array, 1, &dig, &ndig))
+		return NULL;
+	/* (count 0: the library refuses the call and names the reason; it writes neither array) */
+	if (count && (nrecs != (size_t)count * 8u || (dig && ndig != (size_t)count * 96u)))
+	{
+		napi_throw_range_error(env, NULL, "records must hold eight words a universe, digests 96 words a universe or be null");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_canon) == 32, "a record crosses as eight words");
+	float ms = 0.f;
+	int rc = ca3d_ensemble_canon(e, first, count, (ca3d_canon *)recs, (uint64_t *)dig, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1601,7 +1631,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleConfigureClustered", js_ensemble_configure_clustered}, {"ensembleClustered", js_ensemble_clustered},
 	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables},
 	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats},
-	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}, {"ensembleCompose", js_ensemble_compose}};
+	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}, {"ensembleCompose", js_ensemble_compose},
+	    {"ensembleCanon", js_ensemble_canon}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

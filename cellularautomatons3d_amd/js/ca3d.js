@@ -620,6 +620,31 @@ class Ensemble
 		for (let k = 0; k < n; k++) { r.population[k] = out[4 * k]; r.placed[k] = out[4 * k + 1]; r.overlap[k] = out[4 * k + 2]; r.clipped[k] = out[4 * k + 3]; }
 		return r;
 	}
+	/** Canon (ca3d_ensemble_canon): the name of universes opts.first .. opts.first + opts.count - 1 (default: all from `first`) up to the
+	 *  48 orientations of compose and any translation, found on the device in one launch behind the queued steps
+	 *  -> {records, gpuMs}, records[k] = {key (BigInt: equal for all turned and shifted copies of a state), symmetry (BigInt: bit o set
+	 *  when turning by o leaves the state as it is), orientation (which turns the state into the one whose digest is the key),
+	 *  population, boxMin [x, y, z], boxMax}; with opts.digests also digests[k], an array of 48 BigInt, the digest of every
+	 *  orientation. The WHOLE state of a universe is named: isolate objects first. The call only reads. */
+	canon(opts)
+	{
+		const o = Object.assign({ first: 0, digests: false }, opts || {});
+		const count = o.count === undefined ? this.n - o.first : o.count;
+		// (a count the library refuses gets no arrays: it names the reason)
+		const words = new Uint32Array(count > 0 ? count * 8 : 0);
+		const dwords = o.digests ? new Uint32Array(count > 0 ? count * 96 : 0) : null;
+		const gpuMs = this._a.ensembleCanon(this._e, o.first, count, words, dwords);
+		const box = (w) => [w & 0xFF, (w >>> 8) & 0xFF, (w >>> 16) & 0xFF];
+		const big = (a, i) => BigInt(a[i + 1]) << 32n | BigInt(a[i]);
+		const records = [], digests = [];
+		for (let k = 0; k < count; k++)
+		{
+			const r = words.subarray(8 * k, 8 * k + 8);
+			records.push({ key: big(r, 0), symmetry: big(r, 2), orientation: r[4], population: r[5], boxMin: box(r[6]), boxMax: box(r[7]) });
+			if (dwords) digests.push(Array.from({ length: 48 }, (_, i) => big(dwords, 96 * k + 2 * i)));
+		}
+		return dwords ? { records, digests, gpuMs } : { records, gpuMs };
+	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at
 	 *  64^3 with "render_skip" 0, bit for bit. `uniforms`: Float32Array(128) filled for a tileW x tileH window, one block for every tile;

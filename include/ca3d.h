@@ -639,6 +639,48 @@ typedef struct ca3d_composed
 int ca3d_ensemble_compose(ca3d_ensemble_t *dst, uint32_t dst_first, uint32_t n_dst, ca3d_ensemble_t *src, const ca3d_compose_part *parts,
                           const uint32_t *part_begin /* [n_dst + 1] */, uint32_t flags, ca3d_composed *out /* [n_dst], may be NULL */,
                           float *gpu_ms /* may be NULL */);
+/*
+ * Canon (no reference counterpart): a universe's name up to the 48 symmetries of the cube and any translation, so that a census becomes
+ * a catalogue — a glider flying along +x+y and one flying along -z+x, or the 24 turned copies of a still life, get ONE key. One launch
+ * of ca_ensemble_canon64 (csrc/ca_canon.hip, one workgroup a universe) for universes first .. first + count - 1, behind whatever is
+ * queued on the ensemble's stream. Nothing state-sized leaves the device. host.canon restates it in plain numpy;
+ * host.symmetry_orientations and host.is_chiral read the symmetry mask.
+ *
+ * The definition. For the packed 64^3 state S of a universe and an orientation o in 0 .. 47 (ca3d_ensemble_compose's numbering), T_o(S)
+ *   is S turned by o with the turned bounding box's minimum at the origin: what ca3d_ensemble_compose makes of the one part
+ *   (universe, o, at = (0, 0, 0)). T_0(S) is S translated to the origin. Nothing is ever clipped.
+ *   digests[o] is the `digest` of ca3d_summary for T_o(S): the digest_mix sum over the non-zero words, word index (z * 64 + y) * 2 + h.
+ *     For a universe that holds one object digests[0] is that object's census digest.
+ *   key is the smallest of the 48 digests as an unsigned 64-bit number; orientation the smallest o with digests[o] == key. The key is
+ *     equal for all 48 turned and arbitrarily translated copies of a state (they have the same 48 states T_o, in another order).
+ *   symmetry has bit o set exactly when T_o(S) equals T_0(S) WORD FOR WORD — an exact comparison, never one of digests: the symmetry
+ *     group of the state in the numbering of the orientations. Bit 0 is always set; bits 48 .. 63 are zero.
+ *   population, box_min and box_max are those of a census record: the live cells, and the bounding box of S, inclusive, each corner
+ *     packed x | y << 8 | z << 16.
+ *   An empty universe gives key 0, orientation 0, symmetry 2^48 - 1, population 0 and both boxes 0.
+ *   The call works on the WHOLE state of a universe, as compose does: several objects in one universe are one constellation with one
+ *   key. It is not invariant under an oscillator's or a ship's phase (Ensemble.canon_phases takes the smallest key over a period).
+ *
+ * The call only reads: states, records, step counters, anchors and steps_done are unchanged. It needs no rules. It waits for its own
+ * result, as ca3d_ensemble_census does. digests (nullable) receives all 48 digests of every universe: the minimum alone would hide a
+ * wrong digest in 47 of 48 orientations. gpu_ms (nullable) receives the hipEvent time around the launch. The result is staged in one
+ * device array on the handle (32 + 384 bytes a universe, grown when a call needs more — the new array is allocated before the old one
+ * is freed — freed by a configure and by destroy).
+ *
+ * Errors: NULL handle or out — CA3D_ERR_INVALID_ARGUMENT without touching a device; not configured — CA3D_ERR_NOT_CONFIGURED;
+ * count == 0, first + count > n — CA3D_ERR_INVALID_ARGUMENT; a universe of the range without a state — CA3D_ERR_NOT_CONFIGURED, the
+ * message names the first such universe. A refused call touches none of the caller's arrays.
+ */
+typedef struct ca3d_canon
+{
+	uint64_t key;              /* the smallest of the 48 digests */
+	uint64_t symmetry;         /* bit o: T_o equals T_0 word for word */
+	uint32_t orientation;      /* the smallest o whose digest is the key */
+	uint32_t population;
+	uint32_t box_min, box_max; /* of the state as it lies: x | y << 8 | z << 16, inclusive */
+} ca3d_canon;                  /* 32 bytes */
+int ca3d_ensemble_canon(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_canon *out /* [count] */,
+                        uint64_t *digests /* [count][48], may be NULL */, float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

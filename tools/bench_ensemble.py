@@ -83,6 +83,15 @@ and records must equal host.compose in sampled destinations, and after the loop 
 Reported: medians of --repeats measurements. No ratio is required. Written to profiles/ensemble_compose_64.json unless --out says
 otherwise.
 
+--canon measures the canon (ca3d_ensemble_canon, kernel ca_ensemble_canon64: a universe's key up to the 48 orientations and translation,
+its orientation and its symmetry group) on two workloads: the objects of --isolate — the ash of B = 256 universes, a census, EVERY object
+isolated (centred) into a nursery, then ONE call over the nursery — and B dense soups (and_rounds 1). For each: the launch's hipEvent
+time without and with the digests array, the host clock around the call, the census launch on the same universes for scale, and the
+loop the call replaces — read_state and host.canon — on the first --loop-destinations universes ONLY (1 024 by default); for the ash,
+the number of distinct census digests against the number of distinct keys, which is the point of it. Before timing, records and all 48
+digests must equal host.canon in sampled universes, and every loop's keys must equal the call's. Reported: medians of --repeats
+measurements. No ratio is required. Written to profiles/ensemble_canon_64.json unless --out says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -634,6 +643,83 @@ def compose_rows(args):
     return rows
 
 
+def canon_rows(args):
+    """canon against the read_state + host.canon loop, with the census launch on the same universes for scale: per B one row for the
+    ash's objects in a nursery and one for B dense soups. -> rows"""
+    M = 1024
+    born, survive, rounds = CENSUS_ASH["ash B6/S5-7"]
+    ens, nursery = Ensemble(0), Ensemble(0)
+    rows = []
+
+    def measure(e, n, label, B, extra):
+        """One row: canon over universes 0 .. n - 1 of `e`, verified against host.canon in a sample, then timed."""
+        L = min(args.loop_destinations, n)
+        rec, dig = e.canon(0, n, digests=True)
+        sample = sorted({0, 1, n // 3, n // 2, n - 1} | set(range(min(100, n - 1), min(124, n))))
+        for k in sample:
+            r, d = host.canon(e.read_state(k, 1)[0])
+            if rec[k].tobytes() != r.tobytes() or not np.array_equal(dig[k], d):
+                raise SystemExit(f"B {B}, {label}: universe {k} is not host.canon's")
+        gpu, gpu_dig, wall, cen, loop = [], [], [], [], []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            plain = e.canon(0, n)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            gpu.append(e.canon_gpu_ms())
+            e.canon(0, n, digests=True)
+            gpu_dig.append(e.canon_gpu_ms())
+            e.census(0, n, max_components=M)
+            cen.append(e.census_gpu_ms())
+            t0 = time.perf_counter()
+            keys = [host.canon(e.read_state(k, 1)[0])[0]["key"] for k in range(L)]
+            loop.append((time.perf_counter() - t0) * 1e3)
+            if plain["key"][:L].tolist() != [int(k) for k in keys] or plain.tobytes() != rec.tobytes():
+                raise SystemExit(f"B {B}, {label}: the loop found other keys than the call")
+        row = {"workload": label, "universes": B, "canon_universes": n, "verified_against_host_canon_in": len(sample),
+               "canon_gpu_ms": statistics.median(gpu), "canon_gpu_ms_all": gpu,
+               "canon_gpu_ms_with_digests": statistics.median(gpu_dig), "canon_gpu_ms_with_digests_all": gpu_dig,
+               "canon_gpu_us_per_universe": statistics.median(gpu) * 1e3 / n,
+               "canon_wall_ms": statistics.median(wall), "canon_wall_ms_all": wall,
+               "census_gpu_ms_same_universes": statistics.median(cen), "census_gpu_ms_same_universes_all": cen,
+               "loop_universes": L, "loop_wall_ms": statistics.median(loop), "loop_wall_ms_all": loop,
+               "loop_wall_ms_per_universe": statistics.median(loop) / L, "canon_wall_ms_per_universe": statistics.median(wall) / n}
+        row.update(extra(rec, dig))
+        rows.append(row)
+        print(json.dumps(row))
+
+    for B in args.universes:
+        ens.configure(B, neighbourhood="moore")
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        ens.seed_states(0, np.arange(1, B + 1), rounds)
+        done, reason, _ = ens.step_until_cycle(512)
+        comps, n, rest = ens.census(max_components=M)
+        if rest.any():
+            raise SystemExit(f"B {B}: a census of {M} objects a universe is not complete")
+        jobs = np.array([(u, int(c["first_cell"])) for u in range(B) for c in comps[u, :n[u]]], dtype=np.uint32).reshape(-1, 2)
+        census_digests = np.concatenate([comps["digest"][u, :n[u]] for u in range(B)])
+        J = len(jobs)
+        nursery.configure(J, neighbourhood="moore")
+        pop, _ = nursery.isolate(jobs, 0, ens, "centre", True)
+
+        def catalogue(rec, dig):
+            if not np.array_equal(dig[:, 0], census_digests):
+                raise SystemExit(f"B {B}: digests[:, 0] are not the census digests")
+            keys, counts = np.unique(rec["key"], return_counts=True)
+            groups = np.array([bin(int(s)).count("1") for s in rec["symmetry"]])
+            return {"objects": J, "cells_per_object_median": float(np.median(pop)),
+                    "distinct_census_digests": int(np.unique(census_digests).size), "distinct_keys": int(keys.size),
+                    "most_common_key_count": int(counts.max()), "objects_with_a_symmetry_besides_the_identity": int((groups > 1).sum()),
+                    "chiral_objects": int(sum(host.is_chiral(s) for s in rec["symmetry"]))}
+
+        measure(nursery, J, "ash B6/S5-7: every object of a census, isolated (centred) into a nursery", B, catalogue)
+        # the dense case: whole soups, where every bit of the forty's gather is a cell
+        ens.seed_states(0, np.arange(1, B + 1), 1)
+        measure(ens, B, "soups, and_rounds 1 (65 536 cells, box 64^3)", B, lambda rec, dig: {"distinct_keys": int(np.unique(rec["key"]).size)})
+    ens.close()
+    nursery.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -650,11 +736,12 @@ def main():
     ap.add_argument("--census", action="store_true", help="measure census against read_state + labelling on the CPU instead (B = 256 1024)")
     ap.add_argument("--isolate", action="store_true", help="measure isolate against the read_state + cut + upload_state loop instead (B = 256)")
     ap.add_argument("--compose", action="store_true", help="measure compose against the read_state + host.compose + upload_state loop instead (B = 256)")
-    ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose: destinations the CPU loop is run on")
+    ap.add_argument("--canon", action="store_true", help="measure canon against the read_state + host.canon loop instead (B = 256)")
+    ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose, --canon: destinations / universes the CPU loop is run on")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate or args.compose else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose or args.canon else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -670,6 +757,27 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.canon:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_canon_64.json")
+        rows = canon_rows(args)
+        result = {
+            "what": "B universes of 64^3 of ash (seed_states, seeds 1 .. B, and_rounds 1, Moore B6/S5-7, step_until_cycle(512)), a census at max_components 1024, every "
+                    "object isolated (centred) into a nursery, then ONE Ensemble.canon call over the nursery — one launch of ca_ensemble_canon64, the records "
+                    "copied to the host; and the same call over B dense soups (and_rounds 1) — vs. the loop it replaces, run on the first loop_universes "
+                    "universes only: read_state and host.canon; the census launch on the same universes for scale",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"canon": "ca_ensemble_canon64", "census": "ca_ensemble_census64"},
+            "timing": f"canon_gpu_ms / census_gpu_ms_same_universes: hipEvent time around the launch (canon without the digests array, and with it); *_wall_ms: "
+                      f"host clock around the call / the loop; medians of {args.repeats} alternating measurements after records and all 48 digests equalled "
+                      "host.canon in the sampled universes; every loop's keys equalled the call's",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.compose:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_compose_64.json")
         rows = compose_rows(args)
