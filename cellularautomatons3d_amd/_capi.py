@@ -95,6 +95,13 @@ class CanonStruct(C.Structure):
                 ("box_min", C.c_uint32), ("box_max", C.c_uint32)]
 
 
+class CanonPeriodStruct(C.Structure):
+    """ca3d_canon_period (include/ca3d.h): what `ca3d_ensemble_canon_period` says of one universe, 32 bytes
+    (`host.CANON_PERIOD_DTYPE`)."""
+    _fields_ = [("key", C.c_uint64), ("symmetry", C.c_uint64), ("orientation", C.c_uint32), ("phase", C.c_uint32),
+                ("population", C.c_uint32), ("flags_shift", C.c_uint32)]
+
+
 #: the flag bits of `ca3d_ensemble_compose`, and the most parts a call takes
 COMPOSE_OVER = 0x1
 COMPOSE_COPY_RULES = 0x100
@@ -206,6 +213,8 @@ SYMBOLS = [
     ("ca3d_ensemble_compose", C.c_int, [_H, C.c_uint32, C.c_uint32, _H, C.POINTER(ComposePartStruct), _u32p, C.c_uint32,
                                         C.POINTER(ComposedStruct), C.POINTER(C.c_float)]),
     ("ca3d_ensemble_canon", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(CanonStruct), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_canon_period", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.POINTER(CanonPeriodStruct), C.POINTER(C.c_uint64), C.c_uint32,
+                                             C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

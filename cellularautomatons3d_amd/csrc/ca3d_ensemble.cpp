@@ -9,6 +9,7 @@
 // ca3d_ensemble_isolate makes objects a census named the only thing in universes of their own (ca_isolate.hip).
 // ca3d_ensemble_compose stages whole universes, turned and shifted, into universes of their union (ca_compose.hip).
 // ca3d_ensemble_canon names universes up to the 48 symmetries of the cube and translation (ca_canon.hip).
+// ca3d_ensemble_canon_period does so over a period of each universe's own steps, inside the kernel (ca_canon_period.hip).
 #include <cstring>
 #include <new>
 #include <string>
@@ -77,10 +78,13 @@ struct ca3d_ensemble
 	size_t compose_bytes = 0;
 	hipEvent_t ev_compose_start = nullptr, ev_compose_stop = nullptr, ev_compose_src = nullptr;
 	// ca3d_ensemble_canon: the result of the call under way — [count] records of 32 bytes, then [count][48] digests — in one device array
-	// of canon_bytes bytes, grown when a call needs more, gone with the other arrays at a configure; its event pair
+	// of canon_bytes bytes, grown when a call needs more, gone with the other arrays at a configure; its event pair.
+	// ca3d_ensemble_canon_period stages in the same array — [count] records of 32 bytes, then [count][keys_stride] keys, then the
+	// uploaded periods, [count] words — and has an event pair of its own
 	uint8_t *canon = nullptr;
 	size_t canon_bytes = 0;
 	hipEvent_t ev_canon_start = nullptr, ev_canon_stop = nullptr;
+	hipEvent_t ev_canon_period_start = nullptr, ev_canon_period_stop = nullptr;
 };
 
 namespace
@@ -534,6 +538,8 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	if (e->ev_compose_src) hipEventDestroy(e->ev_compose_src);
 	if (e->ev_canon_start) hipEventDestroy(e->ev_canon_start);
 	if (e->ev_canon_stop) hipEventDestroy(e->ev_canon_stop);
+	if (e->ev_canon_period_start) hipEventDestroy(e->ev_canon_period_start);
+	if (e->ev_canon_period_stop) hipEventDestroy(e->ev_canon_period_stop);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
 	return CA3D_OK;
@@ -1116,6 +1122,55 @@ int ca3d_ensemble_canon(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d
 	if (digests) HIP_TRY(hipMemcpyAsync(digests, l.digests, dig_bytes, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->ev_canon_start, e->ev_canon_stop));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_canon_period(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *periods, ca3d_canon_period *out, uint64_t *keys,
+                               uint32_t keys_stride, float *gpu_ms) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!periods) return fail(CA3D_ERR_INVALID_ARGUMENT, "periods is NULL");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	uint32_t longest = 0;
+	for (uint32_t k = 0; k < count; k++)
+	{
+		if (periods[k] == 0 || periods[k] > CA3D_CANON_MAX_PERIOD)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "periods[%u] is %u: a period is 1 .. %u", k, periods[k], (unsigned)CA3D_CANON_MAX_PERIOD);
+		if (periods[k] > longest) longest = periods[k];
+	}
+	if (keys && keys_stride < longest) return fail(CA3D_ERR_INVALID_ARGUMENT, "keys_stride is %u: less than the largest period, %u", keys_stride, longest);
+	if ((rc = require_state(e, first, count))) return rc;
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_rules[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_set_rules has not been called for universe %u", u);
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t rec_bytes = (size_t)count * sizeof(ca3d_canon_period), key_bytes = keys ? (size_t)count * keys_stride * sizeof(uint64_t) : 0,
+	             period_bytes = (size_t)count * sizeof(uint32_t);
+	if ((rc = size_canon(e, rec_bytes + key_bytes + period_bytes))) return rc;
+	if (!e->ev_canon_period_start) HIP_TRY(hipEventCreate(&e->ev_canon_period_start));
+	if (!e->ev_canon_period_stop) HIP_TRY(hipEventCreate(&e->ev_canon_period_stop));
+	CanonPeriodLaunch l{};
+	l.state = e->state;
+	l.rules = e->rules;
+	l.neighbourhood = e->neighbourhood;
+	l.clustered = e->clustered;
+	l.first = first; l.count = count;
+	l.out = reinterpret_cast<ca3d_canon_period *>(e->canon);
+	l.keys = keys ? reinterpret_cast<uint64_t *>(e->canon + rec_bytes) : nullptr;
+	l.keys_stride = keys ? keys_stride : 0u;
+	uint32_t *periods_dev = reinterpret_cast<uint32_t *>(e->canon + rec_bytes + key_bytes);
+	l.periods = periods_dev;
+	// (from pageable memory: the copy has left the caller's array when the call returns)
+	HIP_TRY(hipMemcpyAsync(periods_dev, periods, period_bytes, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipEventRecord(e->ev_canon_period_start, e->stream));
+	HIP_TRY(launch_canon_period(l, e->stream));
+	HIP_TRY(hipEventRecord(e->ev_canon_period_stop, e->stream));
+	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, e->stream));
+	if (keys) HIP_TRY(hipMemcpyAsync(keys, l.keys, key_bytes, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->ev_canon_period_start, e->ev_canon_period_stop));
 	return CA3D_OK;
 }
 CA3D_API_CATCH

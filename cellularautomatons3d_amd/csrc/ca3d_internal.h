@@ -284,6 +284,23 @@ struct CanonLaunch
 	uint64_t *digests;     // device, [count][48], or null: the digest of every orientation
 };
 hipError_t launch_canon(const CanonLaunch &l, hipStream_t stream);
+// ca_canon_period.hip: canon over periods[k] steps of universe first + k, for universes [first, first + count) of an ensemble's state
+// and rule arrays (ca3d_ensemble_canon_period), one workgroup each of ca_ensemble_canon_period_vn64, _moore64 or _clustered64 by the
+// ensemble's kind; out, keys and periods are indexed by universe - first. The caller has checked the range, every period (1 ..
+// CA3D_CANON_MAX_PERIOD) and keys_stride >= max(periods). States and rules are only read.
+struct CanonPeriodLaunch
+{
+	const uint32_t *state;   // [B][8192], the ensemble's current states
+	const uint32_t *rules;   // [B][ensemble_rule_words()]
+	int neighbourhood;       // CA3D_ENSEMBLE_*
+	bool clustered;
+	uint32_t first, count;
+	const uint32_t *periods; // device, [count]
+	ca3d_canon_period *out;  // device, [count]: every entry is written
+	uint64_t *keys;          // device, [count][keys_stride], or null: every slot is written, those past the period with zero
+	uint32_t keys_stride;
+};
+hipError_t launch_canon_period(const CanonPeriodLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

@@ -16,7 +16,8 @@
 // sum the 16 partials of their o, wave 0 takes the 64-bit minimum and thread 0 writes the record.
 //
 // THE MAP AND THE ROW ASSEMBLY ARE ca_compose.hip's (its header), written out here with at = 0, so that the intervals
-// are [0, e'[i] - 1] and nothing is clipped: change that text with this one.
+// are [0, e'[i] - 1] and nothing is clipped: change that text with this one. ca_canon_period.hip (canon over a period)
+// carries the image, the orientation loop and the join of THIS file written out inside its loop over the phases: change it with this one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

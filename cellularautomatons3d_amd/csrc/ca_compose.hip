@@ -21,7 +21,7 @@
 //
 // ca_canon.hip carries the image, the map and the row assembly written out, with at = 0: as an include shared by both
 // kernels the text changed this kernel's register allocation and instruction count, so it stays here as it was
-// measured: change that text with this one.
+// measured: change that text with this one. ca_canon_period.hip carries ca_canon.hip's copy once more: that one too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

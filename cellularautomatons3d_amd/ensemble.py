@@ -303,12 +303,46 @@ class Ensemble:
         """hipEvent time of the last `canon` launch of this object, in milliseconds (None before the first)."""
         return getattr(self, "_canon_ms", None)
 
+    def canon_period(self, periods, first: int = 0, count: Optional[int] = None, keys: bool = False):
+        """`ca3d_ensemble_canon_period`: universe first + k (default range: all from `first`) named over periods[k] steps of its own,
+        taken INSIDE one launch behind the queued steps; the ensemble is left exactly as it is -> records [count] of
+        `host.CANON_PERIOD_DTYPE`: `key`, the smallest `canon` key over the phases t = 0 .. periods[k] - 1 — all phases of all 48
+        turned copies of a glider share it —, `phase`, the smallest t that reaches it, that phase's `orientation`, `symmetry` and
+        `population`, and `flags_shift`: bit 0 (`host.CANON_CLOSED`) says that after periods[k] steps the state is back up to a
+        translation, compared word for word — the period given is a multiple of the true one —, and `host.unpack_shift` gives the
+        translation, (0, 0, 0) for an oscillator or a still life. `periods` is one number for all or one per universe, each 1 ..
+        `host.CANON_MAX_PERIOD`. With `keys` -> (records, keys u64[count, max(periods)]): the key of every phase, zero past a
+        universe's period. Every universe of the range needs a rule. `host.canon_period` is the same on the CPU for one universe;
+        `canon_period_gpu_ms()` tells what the launch took."""
+        count = self.n - first if count is None else count
+        p = _as_u32(periods).ravel()
+        if np.ndim(periods) == 0:
+            p = np.full(max(count, 0), p[0], dtype=np.uint32)
+        if p.size != max(count, 0):
+            raise ValueError("periods holds one period for every universe of the range")
+        stride = int(p.max()) if p.size else 0
+        rec = np.zeros(p.size, dtype=host.CANON_PERIOD_DTYPE)
+        # (a period the library refuses must not size an array: the call below fails before it looks at `ks`)
+        ks = np.zeros((p.size, stride if stride <= host.CANON_MAX_PERIOD else 0), dtype=np.uint64) if keys else None
+        ms = C.c_float(0.0)
+        _capi.check(self._lib.ca3d_ensemble_canon_period(self._h, first, count, p.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                         rec.ctypes.data_as(C.POINTER(_capi.CanonPeriodStruct)),
+                                                         ks.ctypes.data_as(C.POINTER(C.c_uint64)) if keys else None, stride if keys else 0,
+                                                         C.byref(ms)))
+        self._canon_period_ms = float(ms.value)
+        return (rec, ks) if keys else rec
+
+    def canon_period_gpu_ms(self) -> float:
+        """hipEvent time of the last `canon_period` launch of this object, in milliseconds (None before the first)."""
+        return getattr(self, "_canon_period_ms", None)
+
     def canon_phases(self, periods, first: int = 0, count: Optional[int] = None,
                      max_period: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """`canon` over a whole period, for universes already classified as oscillators or ships (`step_until_cycle`,
         `step_until_moving`): universe first + k takes the smallest key over its phases t = 0 .. periods[k] - 1
         -> (key u64[count], phase u32[count], orientation u32[count], symmetry u64[count]), with the phase, orientation and symmetry
-        of the smallest t that reaches the key. All phases of all 48 turned copies of a glider then share one key.
+        of the smallest t that reaches the key. All phases of all 48 turned copies of a glider then share one key. `canon_period`
+        does the same in one launch, leaves the ensemble as it is and also says whether the period closes.
 
         WHAT IT COSTS AND CHANGES: max(periods) `canon` launches with a `step(1)` behind each. `step` has no range, so afterwards
         EVERY universe of the ensemble, inside the range or not, is max(periods) steps further — a universe of the range is back in

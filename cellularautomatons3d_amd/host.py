@@ -725,6 +725,63 @@ def is_chiral(mask: int) -> bool:
     return not any(mirrors(o) for o in symmetry_orientations(mask))
 
 
+# ------------------------------------------------------------------------------------------ canon over a period
+# The definition of ca3d_ensemble_canon_period (include/ca3d.h) in executable form, for one universe whose phases the caller has stepped.
+
+#: ca3d_canon_period (include/ca3d.h), 32 bytes
+CANON_PERIOD_DTYPE = np.dtype([("key", "<u8"), ("symmetry", "<u8"), ("orientation", "<u4"), ("phase", "<u4"), ("population", "<u4"),
+                               ("flags_shift", "<u4")])
+#: bit 0 of `flags_shift`, and the longest period a call takes
+CANON_CLOSED = 1
+CANON_MAX_PERIOD = 4096
+
+
+def unpack_shift(flags_shift: int) -> Tuple[int, int, int]:
+    """(dx, dy, dz) of a `ca3d_canon_period.flags_shift`: the signed bytes in bits 8 .. 15, 16 .. 23 and 24 .. 31."""
+    v = int(flags_shift)
+    return tuple(((v >> s & 0xFF) ^ 0x80) - 0x80 for s in (8, 16, 24))
+
+
+def _at_origin(words) -> Tuple[np.ndarray, Tuple[int, int, int]]:
+    """-> (the cells of a packed 64^3 state cropped to its bounding box [z, y, x], box_min (x, y, z)); an empty state: a box of one dead
+    cell at (0, 0, 0)."""
+    cells = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").ravel().view(np.uint8), bitorder="little").reshape(64, 64, 64)
+    zs, ys, xs = (np.flatnonzero(cells.any(axis=a)) for a in ((1, 2), (0, 2), (0, 1)))
+    if zs.size == 0:
+        return cells[:1, :1, :1], (0, 0, 0)
+    return cells[zs[0]:zs[-1] + 1, ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1], (int(xs[0]), int(ys[0]), int(zs[0]))
+
+
+def canon_period(states) -> Tuple[np.ndarray, np.ndarray]:
+    """`ca3d_ensemble_canon_period` for ONE universe, in plain numpy over `canon`. `states` is [p + 1, 8192]: the phases S_0 .. S_p of
+    a period p >= 1, stepped by the caller (an oracle, `Ensemble.step`) -> (record of CANON_PERIOD_DTYPE, keys u64[p]). keys[t] is
+    `canon(S_t)`'s key; the record's key is the smallest of them, `phase` the smallest t that reaches it, orientation, symmetry and
+    population that phase's. CLOSED (bit 0 of flags_shift) is set exactly when S_p translated to the origin equals S_0 translated to
+    the origin cell for cell; the shift (`unpack_shift`) is then box_min(S_p) - box_min(S_0), and zero when S_0 is empty."""
+    s = np.ascontiguousarray(states, dtype="<u4")
+    if s.ndim != 2 or s.shape[0] < 2 or s.shape[1] != words_per_buffer(64):
+        raise ValueError("states is [p + 1, 8192] with p >= 1: the phases S_0 .. S_p")
+    p = s.shape[0] - 1
+    if p > CANON_MAX_PERIOD:
+        raise ValueError(f"a period is at most {CANON_MAX_PERIOD}")
+    recs = [canon(s[t])[0] for t in range(p)]
+    keys = np.array([int(r["key"]) for r in recs], dtype=np.uint64)
+    t = int(np.argmin(keys))  # the first of equal minima
+    rec = np.zeros((), dtype=CANON_PERIOD_DTYPE)
+    rec["key"], rec["phase"] = keys[t], t
+    for f in ("symmetry", "orientation", "population"):
+        rec[f] = recs[t][f]
+    (a, amin), (b, bmin) = _at_origin(s[0]), _at_origin(s[p])
+    flags_shift = 0
+    if a.shape == b.shape and np.array_equal(a, b):
+        flags_shift = CANON_CLOSED
+        if a.any():
+            for i in range(3):
+                flags_shift |= ((bmin[i] - amin[i]) & 0xFF) << (8 + 8 * i)
+    rec["flags_shift"] = flags_shift
+    return rec, keys
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

@@ -1409,6 +1409,40 @@ static napi_value js_ensemble_canon(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* ensembleCanonPeriod(handle, first, Uint32Array(count) periods, Uint32Array(count * 8) records, Uint32Array(count * keysStride * 2) keys
+ * or null, keysStride) -> gpuMs: universes [first, first + count) named over periods[k] steps of their own, taken inside the kernel
+ * (ca3d_ensemble_canon_period); a record is ca3d_canon_period's eight words: key low, key high, symmetry low, symmetry high,
+ * orientation, phase, population, flagsShift; a key crosses as low word, high word (js/ca3d.js opens them) */
+static napi_value js_ensemble_canon_period(napi_env env, napi_callback_info info)
+{
+	napi_value argv[6];
+	if (!get_args(env, info, 6, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	uint32_t first, stride;
+	void *periods, *recs, *keys;
+	size_t count, nrecs, nkeys;
+	if (!e || !get_u32(env, argv[1], &first) || !get_typed(env, argv[2], napi_uint32_array, 0, &periods, &count) ||
+	    !get_typed(env, argv[3], napi_uint32_array, 0, &recs, &nrecs) || !get_typed(env, argv[4], napi_uint32_array, 1, &keys, &nkeys) ||
+	    !get_u32(env, argv[5], &stride))
+		return NULL;
+	if (count > 0xFFFFFFFFu || nrecs != count * 8u || (keys && nkeys != count * (size_t)stride * 2u))
+	{
+		napi_throw_range_error(env, NULL, "records must hold eight words a universe, keys two words a universe and slot of keysStride or be null");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_canon_period) == 32, "a record crosses as eight words");
+	float ms = 0.f;
+	/* (count 0: the library refuses the call and names the reason; it reads and writes no array, and an empty typed array may have no
+	 * address at all) */
+	uint32_t none[8];
+	if (!count) periods = recs = none;
+	int rc = ca3d_ensemble_canon_period(e, first, (uint32_t)count, (const uint32_t *)periods, (ca3d_canon_period *)recs, (uint64_t *)keys, stride, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1632,7 +1666,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables},
 	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats},
 	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}, {"ensembleCompose", js_ensemble_compose},
-	    {"ensembleCanon", js_ensemble_canon}};
+	    {"ensembleCanon", js_ensemble_canon},
+	    {"ensembleCanonPeriod", js_ensemble_canon_period}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

@@ -232,6 +232,7 @@ const STOP_MOVING = 8; // ... and of ca3d_ensemble_step_until_moving (Ensemble.s
 const ISOLATE_PLACEMENTS = ["keep", "centre", "origin"]; // index = CA3D_ISOLATE_KEEP / CENTRE / ORIGIN (Ensemble.isolate)
 const ISOLATE_COPY_RULES = 0x100;
 const COMPOSE_OVER = 0x1, COMPOSE_COPY_RULES = 0x100; // CA3D_COMPOSE_OVER / CA3D_COMPOSE_COPY_RULES (Ensemble.compose)
+const CANON_CLOSED = 0x1, CANON_MAX_PERIOD = 4096; // CA3D_CANON_CLOSED / CA3D_CANON_MAX_PERIOD (Ensemble.canonPeriod)
 
 class Engine
 {
@@ -644,6 +645,37 @@ class Ensemble
 			if (dwords) digests.push(Array.from({ length: 48 }, (_, i) => big(dwords, 96 * k + 2 * i)));
 		}
 		return dwords ? { records, digests, gpuMs } : { records, gpuMs };
+	}
+	/** Canon over a period (ca3d_ensemble_canon_period): universe opts.first + k named over opts.periods[k] steps of its own, taken INSIDE
+	 *  one launch behind the queued steps; the ensemble is left exactly as it is. opts.periods: one number for universes opts.first ..
+	 *  opts.first + opts.count - 1 (default: all from `first`), or an array with one period per universe of the range, each 1 .. 4096
+	 *  -> {records, gpuMs}, records[k] = {key (BigInt: the smallest canon key over the phases t = 0 .. period - 1; all phases of all
+	 *  48 turned copies of a glider share it), symmetry (BigInt), orientation, phase (the smallest t that reaches the key),
+	 *  population (of that phase), closed (after `period` steps the state is back up to a translation, compared word for word: the
+	 *  period is a multiple of the true one), shift [dx, dy, dz] (that translation: all 0 for an oscillator or a still life)}; with
+	 *  opts.keys also keys[k], an array of periods[k] BigInt, the key of every phase. Every universe of the range needs a rule. */
+	canonPeriod(opts)
+	{
+		const o = Object.assign({ first: 0, keys: false }, opts || {});
+		const scalar = typeof o.periods === "number";
+		const count = scalar ? (o.count === undefined ? this.n - o.first : o.count) : o.periods.length;
+		const periods = scalar ? new Uint32Array(count > 0 ? count : 0).fill(o.periods) : Uint32Array.from(o.periods);
+		// (a period the library refuses sizes no array: it names the reason)
+		const longest = periods.reduce((m, p) => Math.max(m, p), 0), stride = longest <= CANON_MAX_PERIOD ? longest : 0;
+		const words = new Uint32Array(periods.length * 8);
+		const kwords = o.keys ? new Uint32Array(periods.length * stride * 2) : null;
+		const gpuMs = this._a.ensembleCanonPeriod(this._e, o.first, periods, words, kwords, stride);
+		const big = (a, i) => BigInt(a[i + 1]) << 32n | BigInt(a[i]);
+		const byte = (w, s) => ((w >>> s & 0xFF) ^ 0x80) - 0x80;
+		const records = [], keys = [];
+		for (let k = 0; k < periods.length; k++)
+		{
+			const r = words.subarray(8 * k, 8 * k + 8);
+			records.push({ key: big(r, 0), symmetry: big(r, 2), orientation: r[4], phase: r[5], population: r[6], closed: (r[7] & CANON_CLOSED) !== 0,
+				shift: [byte(r[7], 8), byte(r[7], 16), byte(r[7], 24)] });
+			if (kwords) keys.push(Array.from({ length: periods[k] }, (_, t) => big(kwords, 2 * (stride * k + t))));
+		}
+		return kwords ? { records, keys, gpuMs } : { records, gpuMs };
 	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at

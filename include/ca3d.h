@@ -681,6 +681,50 @@ typedef struct ca3d_canon
 } ca3d_canon;                  /* 32 bytes */
 int ca3d_ensemble_canon(ca3d_ensemble_t *e, uint32_t first, uint32_t count, ca3d_canon *out /* [count] */,
                         uint64_t *digests /* [count][48], may be NULL */, float *gpu_ms /* may be NULL */);
+/*
+ * Canon over a period (no reference counterpart): what moves or oscillates named as still lifes are — all phases of a glider, in all 48
+ * orientations, get ONE key — with the proof that the period given closes. One launch of ca_ensemble_canon_period_vn64, _moore64 or
+ * _clustered64 (csrc/ca_canon_period.hip, by the ensemble's kind, one workgroup a universe) for universes first .. first + count - 1,
+ * behind whatever is queued on the ensemble's stream. Universe first + k is followed over periods[k] steps of its own INSIDE the
+ * kernel; nothing is written back to the ensemble. host.canon_period restates it in plain numpy over host.canon.
+ *
+ * The definition. Let S_0 be the universe's current state and S_t what the ensemble's own step makes of it after t steps: the
+ *   universe's rule, - faces dead, + faces wrapping, exactly as ca3d_ensemble_step does. k_t is ca3d_ensemble_canon's record of S_t.
+ *   key is the smallest k_t.key for t < period, as an unsigned 64-bit number; phase the smallest t that reaches it; orientation,
+ *     symmetry and population are that k_t's.
+ *   keys[u][t] is k_t.key for t < period; the slots from period up to keys_stride are zero. keys is part of the interface on purpose,
+ *     as digests is for canon: the minimum alone would hide a wrong key in all phases but one.
+ *   CLOSED (bit 0 of flags_shift) is set exactly when T_0(S_period) equals T_0(S_0) WORD FOR WORD, T_0 being canon's "translated to
+ *     the origin" — a comparison of words, never of digests. The state is then back up to a translation, and the period given is a
+ *     multiple of the true one.
+ *   dx, dy, dz (bits 8 .. 15, 16 .. 23, 24 .. 31 of flags_shift, signed bytes) are box_min(S_period) - box_min(S_0) per axis when CLOSED
+ *     is set and S_0 is not empty, and zero otherwise. (0, 0, 0) with CLOSED is an oscillator or a still life, anything else a ship.
+ *   An empty S_0 gives key 0, phase 0, symmetry 2^48 - 1, population 0 and shift 0; CLOSED is then set exactly when S_period is empty.
+ *   A ship that meets a face within the period is whatever the definition gives: usually not CLOSED.
+ *
+ * The call only reads: states, records, step counters, anchors, steps_done and stats are unchanged. It needs a rule on every universe
+ * of the range. It waits for its own result, as ca3d_ensemble_canon does. gpu_ms (nullable) receives the hipEvent time around the
+ * launch. The result is staged in canon's device array on the handle: the records, count * keys_stride keys, then the periods.
+ *
+ * Errors: NULL handle, periods or out — CA3D_ERR_INVALID_ARGUMENT without touching a device; not configured — CA3D_ERR_NOT_CONFIGURED;
+ * count == 0, first + count > n, a period of 0 or above CA3D_CANON_MAX_PERIOD, keys given with keys_stride < max(periods) —
+ * CA3D_ERR_INVALID_ARGUMENT; a universe of the range without a state, or without a rule — CA3D_ERR_NOT_CONFIGURED, the message names
+ * the first such universe. A refused call touches none of the caller's arrays.
+ */
+#define CA3D_CANON_CLOSED 1u          /* flags_shift bit 0 */
+#define CA3D_CANON_MAX_PERIOD 4096u
+typedef struct ca3d_canon_period
+{
+	uint64_t key;          /* smallest ca3d_canon key over phases t = 0 .. period - 1 */
+	uint64_t symmetry;     /* of the smallest t that reaches the key */
+	uint32_t orientation;  /* likewise */
+	uint32_t phase;        /* that t */
+	uint32_t population;   /* of that phase */
+	uint32_t flags_shift;  /* bit 0 CLOSED; bits 8..15, 16..23, 24..31: dx, dy, dz as int8 */
+} ca3d_canon_period;       /* 32 bytes */
+int ca3d_ensemble_canon_period(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *periods /* [count] */,
+                               ca3d_canon_period *out /* [count] */, uint64_t *keys /* [count][keys_stride], may be NULL */,
+                               uint32_t keys_stride, float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

@@ -92,6 +92,17 @@ the number of distinct census digests against the number of distinct keys, which
 digests must equal host.canon in sampled universes, and every loop's keys must equal the call's. Reported: medians of --repeats
 measurements. No ratio is required. Written to profiles/ensemble_canon_64.json unless --out says otherwise.
 
+--canon-period measures canon over a period (ca3d_ensemble_canon_period, kernels ca_ensemble_canon_period_moore64 ...: the smallest
+canon key over the phases of a period stepped INSIDE the launch, and whether the period closes) against Ensemble.canon_phases, the
+Python loop it replaces (per phase a canon launch and a step launch; it leaves the ensemble max(periods) steps further), on the
+nursery of --canon with periods all 4 and all 1, and on B dense soups (and_rounds 1, the ash's rule) with periods all 4. For each: the
+launch's hipEvent time and the host clock around the call; canon_phases' host clock and its summed hipEvent time, period x (canon
+launch + step launch), measured by the same loop written out; for period 1 the plain canon launch beside it, the price of carrying the
+step's registers and LDS. The universes are put back before every measurement. Before timing, records and keys must equal
+host.canon_period of the CPU oracle's phases in sampled universes, and canon_phases' key, phase, orientation and symmetry must equal
+the call's everywhere. Reported: medians of --repeats measurements. No ratio is required. Written to
+profiles/ensemble_canon_period_64.json unless --out says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -720,6 +731,101 @@ def canon_rows(args):
     return rows
 
 
+def canon_period_rows(args):
+    """canon_period against canon_phases: per B the ash nursery with periods 4 and 1 and B dense soups with period 4. -> rows"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as ol
+
+    M = 1024
+    born, survive, rounds = CENSUS_ASH["ash B6/S5-7"]
+    rules = ol.Rules.from_strings(neighbourhood="moore", born=born, survive=survive)
+    ens, nursery = Ensemble(0), Ensemble(0)
+    rows = []
+
+    def measure(e, n, restore, period, label, B):
+        """One row: canon_period over universes 0 .. n - 1 of `e` with one period, verified, then timed beside canon_phases."""
+        periods = np.full(n, period, dtype=np.uint32)
+        restore()
+        rec, keys = e.canon_period(periods, 0, n, keys=True)
+        sample = sorted({0, 1, n // 3, n // 2, n - 1} | set(range(min(100, n - 1), min(108, n))))
+        for k in sample:
+            t = [e.read_state(k, 1)[0]]
+            for _ in range(period):
+                t.append(ol.packed_step(G, t[-1], rules))
+            r, ks = host.canon_period(np.stack(t))
+            if rec[k].tobytes() != r.tobytes() or not np.array_equal(keys[k], ks):
+                raise SystemExit(f"B {B}, {label}: universe {k} is not host.canon_period's")
+        gpu, gpu_keys, wall, old_wall, old_gpu, old_canon, old_step, plain = [], [], [], [], [], [], [], []
+        for _ in range(args.repeats):
+            restore()
+            e.synchronize()
+            t0 = time.perf_counter()
+            now = e.canon_period(periods, 0, n)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            gpu.append(e.canon_period_gpu_ms())
+            e.canon_period(periods, 0, n, keys=True)
+            gpu_keys.append(e.canon_period_gpu_ms())
+            if now.tobytes() != rec.tobytes():
+                raise SystemExit(f"B {B}, {label}: two calls differ")
+            e.canon(0, n)
+            plain.append(e.canon_gpu_ms())
+            t0 = time.perf_counter()
+            key, phase, orientation, symmetry = e.canon_phases(periods, 0, n, max_period=max(64, period))
+            e.synchronize()
+            old_wall.append((time.perf_counter() - t0) * 1e3)
+            if not (np.array_equal(key, rec["key"]) and np.array_equal(phase, rec["phase"]) and np.array_equal(orientation, rec["orientation"])
+                    and np.array_equal(symmetry, rec["symmetry"])):
+                raise SystemExit(f"B {B}, {label}: canon_phases found something else than the call")
+            restore()
+            c_ms = s_ms = 0.0
+            for _ in range(period):  # canon_phases' launches, timed one by one
+                e.canon(0, n)
+                c_ms += e.canon_gpu_ms()
+                e.step(1)
+                e.synchronize()
+                s_ms += e.stats().gpu_ms
+            old_canon.append(c_ms)
+            old_step.append(s_ms)
+            old_gpu.append(c_ms + s_ms)
+        med = statistics.median
+        row = {"workload": label, "universes": B, "canon_universes": n, "period": period, "verified_against_host_canon_period_in": len(sample),
+               "closed": int((rec["flags_shift"] & 1).sum()), "ships": int(((rec["flags_shift"] & 1).astype(bool) & ((rec["flags_shift"] >> 8) != 0)).sum()),
+               "distinct_keys": int(np.unique(rec["key"]).size),
+               "canon_period_gpu_ms": med(gpu), "canon_period_gpu_ms_all": gpu,
+               "canon_period_gpu_ms_with_keys": med(gpu_keys), "canon_period_gpu_ms_with_keys_all": gpu_keys,
+               "canon_period_wall_ms": med(wall), "canon_period_wall_ms_all": wall,
+               "canon_gpu_ms_one_launch": med(plain), "canon_gpu_ms_one_launch_all": plain,
+               "canon_phases_wall_ms": med(old_wall), "canon_phases_wall_ms_all": old_wall,
+               "canon_phases_gpu_ms_summed": med(old_gpu), "canon_phases_gpu_ms_summed_all": old_gpu,
+               "canon_phases_canon_gpu_ms_summed": med(old_canon), "canon_phases_step_gpu_ms_summed": med(old_step),
+               "gpu_ratio_phases_over_period": med(old_gpu) / med(gpu), "wall_ratio_phases_over_period": med(old_wall) / med(wall)}
+        rows.append(row)
+        print(json.dumps(row))
+
+    for B in args.universes:
+        ens.configure(B, neighbourhood="moore")
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        ens.seed_states(0, np.arange(1, B + 1), rounds)
+        ens.step_until_cycle(512)
+        comps, n, rest = ens.census(max_components=M)
+        if rest.any():
+            raise SystemExit(f"B {B}: a census of {M} objects a universe is not complete")
+        jobs = np.array([(u, int(c["first_cell"])) for u in range(B) for c in comps[u, :n[u]]], dtype=np.uint32).reshape(-1, 2)
+        J = len(jobs)
+        nursery.configure(J, neighbourhood="moore")
+        put_back = lambda: nursery.isolate(jobs, 0, ens, "centre", True)  # noqa: E731
+        for period in (4, 1):
+            measure(nursery, J, put_back, period, "ash B6/S5-7: every object of a census, isolated (centred) into a nursery", B)
+        soups = Ensemble(0)
+        soups.configure(B, neighbourhood="moore")
+        soups.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        measure(soups, B, lambda: soups.seed_states(0, np.arange(1, B + 1), 1), 4, "soups, and_rounds 1 (65 536 cells, box 64^3), B6/S5-7", B)
+        soups.close()
+    ens.close()
+    nursery.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -737,11 +843,12 @@ def main():
     ap.add_argument("--isolate", action="store_true", help="measure isolate against the read_state + cut + upload_state loop instead (B = 256)")
     ap.add_argument("--compose", action="store_true", help="measure compose against the read_state + host.compose + upload_state loop instead (B = 256)")
     ap.add_argument("--canon", action="store_true", help="measure canon against the read_state + host.canon loop instead (B = 256)")
+    ap.add_argument("--canon-period", action="store_true", help="measure canon_period against canon_phases instead (B = 256)")
     ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose, --canon: destinations / universes the CPU loop is run on")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate or args.compose or args.canon else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -757,6 +864,32 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.canon_period:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_canon_period_64.json")
+        rows = canon_period_rows(args)
+        result = {
+            "what": "B universes of 64^3 of ash (seed_states, seeds 1 .. B, and_rounds 1, Moore B6/S5-7, step_until_cycle(512)), a census at max_components 1024, every "
+                    "object isolated (centred) into a nursery, then ONE Ensemble.canon_period call over the nursery with periods all 4, and all 1 — one launch of "
+                    "ca_ensemble_canon_period_moore64, the records copied to the host; and the same call with periods all 4 over B dense soups (and_rounds 1) under "
+                    "the same rule — vs. Ensemble.canon_phases on the same universes, the loop it replaces: per phase one launch of ca_ensemble_canon64 and one "
+                    "step launch of ca_ensemble_moore64",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"canon_period": "ca_ensemble_canon_period_moore64", "canon": "ca_ensemble_canon64", "step": "ca_ensemble_moore64"},
+            "timing": f"canon_period_gpu_ms: hipEvent time around the launch (without the keys array, and with it); canon_phases_gpu_ms_summed: the hipEvent times of "
+                      f"canon_phases' launches, period x (canon + step(1)), from the same loop written out; canon_gpu_ms_one_launch: one plain canon launch on the "
+                      f"same universes; *_wall_ms: host clock around the call; medians of {args.repeats} alternating measurements, the universes put back before "
+                      "each, after records and keys equalled host.canon_period of the CPU oracle's phases in the sampled universes; canon_phases' results equalled "
+                      "the call's everywhere",
+            "not_measured": "von Neumann and clustered ensembles, periods above 4, larger B, the kernel's phases one by one (occupancy, leaf reloads, the single "
+                            "exchange buffer)",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.canon:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_canon_64.json")
         rows = canon_rows(args)
