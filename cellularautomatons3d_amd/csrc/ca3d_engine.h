@@ -50,6 +50,7 @@ struct ca3d_engine
 	int want_stats = 1; // record the event pair ca3d_get_stats reads (a marker packet each: costs ~1 us of GPU idle per call)
 	std::map<uint64_t, hipGraphExec_t> slab_graphs; // (phase, start buffer, sub-steps) -> captured slab batch
 	uint32_t pending_edges = 0;                     // sub-steps of an edge phase awaiting its interior phase
+	bool pending_binary = true;                     // binary_state of the buffer that edge phase started from: its interior phase reads it again
 	int roll_z = 0;       // forced planes per thread of the rolling-window kernel (0: automatic)
 	int roll_tile = 1;    // tile form of the rolling-window kernel (x-shifted rows shared through LDS)
 	int use_roll = 1;     // rolling-window form of the class kernels where it applies (needs use_jit)

@@ -117,6 +117,12 @@ static int slab_batch(ca3d_engine *h, uint32_t n_steps, int phase)
 	rc = bind_device(h);
 	if (rc) return rc;
 	if (n_steps == 0) return CA3D_OK;
+	// Unpacked layout: the first sub-step of a batch reads the state as uploaded, which may hold cell values above 1 (the ballot kernel
+	// must not be given those); every later one reads what a kernel wrote. The interior phase starts from that same buffer once more,
+	// after the edge phase has marked the state as 0 / 1: its first sub-step (and whether the batch may be a graph) goes by what the
+	// edge phase found.
+	if (phase == CA3D_SLAB_PHASE_EDGES) h->pending_binary = h->binary_state;
+	else if (phase == CA3D_SLAB_PHASE_INTERIOR) h->binary_state = h->pending_binary;
 	h->buffers_exposed = false;
 	const uint32_t L = h->nplanes, K = h->ghost, n = n_steps;
 	// The packed kernel's bottom face is dead (z == -1 is dropped): the slab that owns global plane 0 never needs

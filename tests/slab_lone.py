@@ -1,0 +1,273 @@
+"""A lone slab: ONE engine stands for one rank of a Z-slab split, the test plays its neighbours with the oracle's full-grid states.
+
+Any `z0`, `nz`, `K` that `ca3d_configure_slab` accepts can be driven this way (the splits of tests/test_gpu_slab.py are even: their slab
+bounds are multiples of G / P), so the per-step kernels meet plane ranges of any length, offset and residue — the shifted last z-run, the
+fall-throughs of ranges shorter than a kernel's planes per thread, a global plane 0 that lies anywhere inside the plane array.
+
+Array plane j of a slab holds global plane z = z0 - K + j. What the harness writes into a ghost plane:
+  0 <= z < G   that plane of the oracle state
+  z >= G       plane z - G (the copy that wraps: compute_clustered.wgsl:104 `<= G`)
+  z < 0        packed: words of all ones — the -z face is dead, so they must never matter, and all ones is the filler most likely to
+               show a missing mask; unpacked (a torus): plane z + G
+Everything expected comes from `ol.packed_step` / `ol.unpacked_step` on the FULL grid; nothing is ever taken from the engine, every
+comparison is exact. The engine is a parameter: tests/test_slab_lone_cpu.py drives a CPU stand-in through the same code, which proves
+that these expectations follow from the reference semantics alone.
+"""
+import numpy as np
+
+import oracle_lib as ol
+from cellularautomatons3d_amd import LAYOUT_PACKED32, LAYOUT_UNPACKED, SLAB_PHASE_EDGES, SLAB_PHASE_INTERIOR, host, slab
+from cellularautomatons3d_amd._capi import SLAB_RECV_HIGH, SLAB_RECV_LOW, SLAB_SEND_HIGH, SLAB_SEND_LOW
+
+_TRAJECTORIES = {}
+
+
+# ---- the geometries: (z0, nz, K, batches) as functions of the grid, so that tests/test_slab_lone_cpu.py runs at G = 96 exactly the
+# tuples tests/test_gpu_slab_ranges.py runs at its grids. Every second batch has another length than the first (it starts from the other
+# ping-pong buffer and replays or creates another cached graph), except where K = 1 leaves one length only.
+def even_split_geometries(G):
+    """Shapes an even split can produce, at offsets and lengths it never does."""
+    return [
+        (0, 37, 3, (3, 2)),                   # bottom: the low ghost (all ones) is neither computed nor read
+        ((G // 3) | 1, 33, 4, (4, 3)),        # middle: odd z0, odd nz
+        (G - 29, 29, 5, (5, 2)),              # top: the high ghost is the copy of planes 0 .. K-1, global plane 0 inside the array
+        (50, 7, 3, (3, 1)),                   # thin: cannot be split, the edge phase runs whole batches
+        (0, G, 4, (2, 4)),                    # one rank holds the whole grid
+    ]
+
+
+def uneven_split_geometries(G):
+    """Shapes NO even split produces: a high ghost that straddles plane G, and a slab that starts inside the first K planes (part of its
+    low ghost lies below the dead face: planes of all ones that the kernels do compute and must never let through)."""
+    return [
+        (G - 40, 38, 5, (4, 5)),
+        (2, 30, 5, (5, 3)),
+        (3, 41, 4, (2, 4)),
+    ]
+
+
+def short_edge_geometries(G):
+    """Edge zones of 1 .. 7 planes: shorter than the planes per thread a forced depth asks for (the launcher's fall-throughs)."""
+    return [
+        ((G // 2) | 1, 21, 1, (1, 1)),        # edge zones of ONE plane
+        (G // 4 + 2, 35, 3, (3, 2)),          # 7, 5, 3 planes
+    ]
+
+
+def nearly_whole_geometries(G):
+    """Slabs long enough for the kernels' deep forms on the grids that have no other way to them (the rows kernel's threshold is
+    ~ 0.8 .. 0.98 of the grid); K = 2 keeps the interior of the phased form above it even at 288."""
+    return [
+        (0, G, 4, (4, 3)),
+        (9, G - 9, 5, (5, 2)),
+        (0, G, 2, (2, 1)),
+        (G // 8 + 1, G // 2 + 1, 3, (3, 2)),  # half the grid: below every such threshold
+        (20, G - 20, 20, (10, 3)),            # top slab, deep ghosts: the copy of plane 0 (dead face below it) moves through every position of a z-run
+    ]
+
+
+def window_geometries(G):
+    """70 .. 101 array planes of odd lengths, with ghost zones deep enough for two-range launches of 8, 16 and 30 planes per thread."""
+    return [
+        (0, 61, 20, (3, 2)),                  # 101 array planes; edge zones of 41 .. 37 planes
+        (G // 4 + 1, 57, 20, (3, 2)),         # 97
+        (G - 75, 75, 12, (4, 3)),             # 99, top slab; edge zones of 26 .. 20
+        (G // 8 + 1, 63, 8, (8, 5)),          # 79; edge zones of 22 .. 8
+    ]
+
+
+def deep_ghost_top_geometries(G):
+    """A top slab with ghost zones of 20 planes and a batch of 17: the copy of plane 0 above the last owned plane (its -z face is dead, the
+    plane below it is not) is computed 16 times, one plane further from the start of the range each time — every position of a z-run of up
+    to 16 planes. (A batch this long cannot be split: the phased form runs it whole.)"""
+    return [(G - 61, 61, 20, (17, 4))]
+
+
+def aligned_and_not_geometries(G):
+    """One geometry whose z0, K and nz are all multiples of 4 (the z-aligned entry of the class kernels is chosen per launch: such a
+    slab is where its ranges can start and end on multiples of 4), and three that are not."""
+    return [
+        (G // 4, 32, 4, (4, 2)),
+        ((G // 3) | 1, 33, 4, (4, 3)),
+        (G - 29, 29, 5, (5, 2)),
+        (2, 30, 5, (5, 3)),
+    ]
+
+
+def ring_geometries(G):
+    """Unpacked layout (a torus: no dead face): odd z0, nz = 21; the low ghost wraps below plane 0, the high ghost past plane G - 1."""
+    return [
+        (1, 21, 3, (3, 2)),
+        (G - 21, 21, 4, (2, 4)),
+        (17, 21, 2, (2, 1)),
+    ]
+
+
+class Trajectory:
+    """Oracle states 0, 1, 2 ... of a full grid, computed on demand and kept (read-only)."""
+
+    def __init__(self, G, r, layout, state0):
+        self.G, self.r, self.layout = G, r, layout
+        state0.setflags(write=False)
+        self.states = [state0]
+
+    def __call__(self, n):
+        while len(self.states) <= n:
+            cur = self.states[-1]
+            if self.layout == LAYOUT_PACKED32:
+                nxt = ol.packed_step(self.G, cur, self.r)
+            else:
+                nxt = ol.unpacked_step(self.G, cur, self.r.main, self.r.survive, self.r.born)
+            nxt.setflags(write=False)
+            self.states.append(nxt)
+        return self.states[n]
+
+
+def start_state(G, seed, and_rounds=0, layout=LAYOUT_PACKED32, max_value=1):
+    """`host.random_fill` of the full grid. Unpacked: one u32 per cell, 0 / 1 from the fill's bits; `max_value` 2 turns about a quarter of
+    the live cells into 2 (a state the ballot kernel must not be given: the literal kernel takes it)."""
+    if layout == LAYOUT_PACKED32:
+        return host.random_fill(host.words_per_buffer(G), seed=seed, and_rounds=and_rounds)
+    w = host.random_fill(G ** 3, seed=seed, and_rounds=and_rounds)
+    cells = (w & 1).astype(np.uint32)
+    if max_value == 2:
+        cells += cells & ((w >> 1) & 1).astype(np.uint32) & ((w >> 2) & 1).astype(np.uint32)
+    return cells
+
+
+def trajectory(G, rule_name, r, seed, and_rounds=0, layout=LAYOUT_PACKED32, max_value=1):
+    """The memoised oracle trajectory per (grid, rule, seed ...): shared by every geometry and form of a test."""
+    key = (G, rule_name, seed, and_rounds, layout, max_value)
+    if key not in _TRAJECTORIES:
+        _TRAJECTORIES[key] = Trajectory(G, r, layout, start_state(G, seed, and_rounds, layout, max_value))
+    return _TRAJECTORIES[key]
+
+
+def plane_words(G, layout):
+    return (G // 32) * G if layout == LAYOUT_PACKED32 else G * G
+
+
+def ghost_planes(G, layout, state, z_first, count):
+    """`count` planes from global plane `z_first` on, as the ghosts of a slab hold them (module docstring)."""
+    pw = plane_words(G, layout)
+    planes = state.reshape(G, pw)
+    out = np.empty((count, pw), dtype=np.uint32)
+    for i in range(count):
+        z = z_first + i
+        if z < 0 and layout == LAYOUT_PACKED32:
+            out[i] = 0xFFFFFFFF
+        else:
+            out[i] = planes[z % G]
+    return out.reshape(-1)
+
+
+def owned_planes(G, layout, state, z_first, count):
+    pw = plane_words(G, layout)
+    return state[z_first * pw:(z_first + count) * pw]
+
+
+def _region(eng, region):
+    """The engine's device memory of a slab region as a torch tensor (the CPU stand-in hands out a view of its own buffer)."""
+    own = getattr(eng, "slab_region_tensor", None)
+    if own is not None:
+        return own(region)
+    return slab.device_tensor(*eng.slab_region(region), 0)
+
+
+def _settle(t):
+    if t.is_cuda:
+        import torch
+
+        torch.cuda.synchronize()
+
+
+def _write_region(eng, region, words):
+    import torch
+
+    t = _region(eng, region)
+    assert t.numel() == words.size, (region, t.numel(), words.size)
+    t.copy_(torch.from_numpy(words.view(np.int32).copy()))
+    _settle(t)
+
+
+def _read_region(eng, region):
+    t = _region(eng, region)
+    return t.cpu().numpy().view(np.uint32).copy()
+
+
+def _equal(got, want, what, G, layout, z_first):
+    """Exact comparison; on failure the first differing (z, y, word) is named."""
+    if np.array_equal(got, want):
+        return
+    i = int(np.flatnonzero(got != want)[0])
+    pw = plane_words(G, layout)
+    row = G // 32 if layout == LAYOUT_PACKED32 else G
+    z, rest = divmod(i, pw)
+    y, w = divmod(rest, row)
+    n_bad = int(np.count_nonzero(got != want))
+    raise AssertionError(f"{what}: {n_bad} of {got.size} words differ, first at global z {z_first + z} (slab plane {z}), y {y}, word {w}: "
+                         f"got {int(got[i]):#010x}, want {int(want[i]):#010x}")
+
+
+def write_ghosts(eng, G, layout, state, z0, nz, K):
+    """Both ghost zones of the buffer `slab_region` refers to, from a full-grid state; returns what was written (low, high)."""
+    low = ghost_planes(G, layout, state, z0 - K, K)
+    high = ghost_planes(G, layout, state, z0 + nz, K)
+    eng.synchronize()
+    _write_region(eng, SLAB_RECV_LOW, low)
+    _write_region(eng, SLAB_RECV_HIGH, high)
+    return low, high
+
+
+def run_lone_slab(eng, traj, r, z0, nz, K, batches, phased, layout=LAYOUT_PACKED32, options=()):
+    """Configure `eng` as the slab [z0, z0 + nz) with K ghost planes of traj's grid, upload its planes of oracle state 0 and run
+    `batches` (sub-step counts, each <= K), whole (`slab_step`) or phased (edges, ghost refresh, interior); after every batch the owned
+    planes must equal the oracle's. `options`: (name, value) pairs set after the slab is configured and before the rules."""
+    G = traj.G
+    what = f"G {G} slab z0 {z0} nz {nz} K {K} {'phased' if phased else 'whole'}"
+    eng.configure_slab(G, z0, nz, K, layout)
+    for name, value in options:
+        eng.set_option(name, value)
+    eng.set_rules(r.main, r.edges, r.corners, r.survive, r.born)
+    eng.upload_state(owned_planes(G, layout, traj(0), z0, nz))
+    write_ghosts(eng, G, layout, traj(0), z0, nz, K)
+    done = 0
+    for n in batches:
+        assert 1 <= n <= K
+        now = traj(done + n)
+        at = f"{what}, batch of {n} after {done} steps"
+        if not phased:
+            eng.slab_step(n)
+            eng.synchronize()
+        else:
+            eng.slab_step_phase(n, SLAB_PHASE_EDGES)
+            eng.synchronize()
+            # the planes the neighbours are waiting for are final before the interior has run
+            _equal(_read_region(eng, SLAB_SEND_LOW), owned_planes(G, layout, now, z0, K), at + ": send_low after the edge phase", G, layout, z0)
+            _equal(_read_region(eng, SLAB_SEND_HIGH), owned_planes(G, layout, now, z0 + nz - K, K), at + ": send_high after the edge phase", G,
+                   layout, z0 + nz - K)
+            low, high = write_ghosts(eng, G, layout, now, z0, nz, K)
+            eng.slab_step_phase(n, SLAB_PHASE_INTERIOR)
+            eng.synchronize()
+            # the interior phase neither reads nor disturbs the ghost planes that arrive while it runs
+            _equal(_read_region(eng, SLAB_RECV_LOW), low, at + ": recv_low after the interior phase", G, layout, z0 - K)
+            _equal(_read_region(eng, SLAB_RECV_HIGH), high, at + ": recv_high after the interior phase", G, layout, z0 + nz)
+        done += n
+        _equal(eng.read_state(), owned_planes(G, layout, now, z0, nz), at + ": owned planes", G, layout, z0)
+        if not phased:
+            write_ghosts(eng, G, layout, now, z0, nz, K)
+
+
+def launches(nz, K, batches, dead_bottom, phased):
+    """The plane ranges of every per-step launch such a run makes, from `slab.batch_ranges` (== ca3d_slab_step_phase): a list of tuples
+    of range LENGTHS — (all,) for a whole sub-step, (low, high) for the two edge zones of a phased one, (interior,) for its interior. Empty
+    ranges are left out, as the launcher leaves them out."""
+    out = []
+    for n in batches:
+        for names in ((("low", "high"), ("interior",)) if phased else (("all",),)):
+            for s in range(1, n + 1):
+                rg = slab.batch_ranges(nz, K, n, s, dead_bottom)
+                lens = tuple(rg[k][1] - rg[k][0] for k in names if rg[k][1] > rg[k][0])
+                if lens:
+                    out.append(lens)
+    return out

@@ -138,9 +138,12 @@ def test_von_neumann_tables_through_every_branch_of_vn_next(eng, born, survive):
             np.testing.assert_array_equal(eng.read_state(), ol.packed_run(G, st, r, steps), err_msg=f"B{born}/S{survive} at {G} ({eng.info().kernel_name})")
 
 
-# every rule-set at 96 / 160 / 384; at 768 (3.5 s per case: the oracle) one rule per kernel form — von Neumann, clustered, a 2D rule, a wide
-# Moore table, an edges-only rule-set: the forms 768 selects are the ones 384 selects for the other rules (both are multiples of 128)
-@pytest.mark.parametrize("G,name", [(G, n) for G in (96, 160, 384) for n in RULESETS] + [(768, n) for n in ("default", "clustered", "life2d", "moore_wide", "vn_edges_only")])
+# every rule-set at 96 / 160 / 224 / 288 / 320 / 352 / 384 — the rows kernel's deep entry is compiled with 3 planes per thread at 288, 4 at
+# 320, 6 at 352 (8 from 416 up: 768, 992 below), and 352 is the one grid whose full range is no multiple of its depth (352 % 6 = 4: the last
+# z-run is shifted back); 7, 9, 10 and 11 words per row leave 63, 63, 60 and 55 active lanes per wave; at 768 (3.5 s per case: the oracle)
+# one rule per kernel form — von Neumann, clustered, a 2D rule, a wide Moore table, an edges-only rule-set: the forms 768 selects are the
+# ones 384 selects for the other rules (both are multiples of 128)
+@pytest.mark.parametrize("G,name", [(G, n) for G in (96, 160, 224, 288, 320, 352, 384) for n in RULESETS] + [(768, n) for n in ("default", "clustered", "life2d", "moore_wide", "vn_edges_only")])
 def test_rows_kernel_on_grids_that_are_not_powers_of_two(eng, G, name):
     """The grids the reference UI offers are the multiples of 32 up to 1024 (main_pathtraced.js:268-279, 675-693). Those that are not
     powers of two run the rows kernel (ca_packed_rows_kernel.inc, compiled for grid and rule at run time): against the oracle, and
