@@ -51,6 +51,7 @@ struct ca3d_engine
 	std::map<uint64_t, hipGraphExec_t> slab_graphs; // (phase, start buffer, sub-steps) -> captured slab batch
 	uint32_t pending_edges = 0;                     // sub-steps of an edge phase awaiting its interior phase
 	bool pending_binary = true;                     // binary_state of the buffer that edge phase started from: its interior phase reads it again
+	bool pending_resident = false;                  // that edge phase ran the whole batch (a slab too thin to split) as ONE resident launch
 	int roll_z = 0;       // forced planes per thread of the rolling-window kernel (0: automatic)
 	int roll_tile = 1;    // tile form of the rolling-window kernel (x-shifted rows shared through LDS)
 	int use_roll = 1;     // rolling-window form of the class kernels where it applies (needs use_jit)

@@ -151,7 +151,8 @@ static int slab_batch(ca3d_engine *h, uint32_t n_steps, int phase)
 		return CA3D_OK;
 	};
 	const bool graphable = graphs_allowed(h) && n > 1;
-	const bool resident = what == CA3D_SLAB_PHASE_ALL && resident_wanted(h, n);
+	// (the interior phase of a thin slab commits what its edge phase ran: how that batch ran is what the edge phase noted)
+	const bool resident = what < 0 ? h->pending_resident : what == CA3D_SLAB_PHASE_ALL && resident_wanted(h, n);
 	if (what < 0) { /* nothing to enqueue */ }
 	else if (resident)
 	{
@@ -182,6 +183,7 @@ static int slab_batch(ca3d_engine *h, uint32_t n_steps, int phase)
 	if (phase == CA3D_SLAB_PHASE_EDGES)
 	{
 		h->pending_edges = n; // ca3d_slab_region now refers to the buffer the batch ends in
+		h->pending_resident = resident;
 		return CA3D_OK;
 	}
 	h->pending_edges = 0;

@@ -255,7 +255,7 @@ int ca3d_synchronize(ca3d_t *h);
  * ca3d_slab_step_phase(EDGES) + (INTERIOR) and ca3d_slab_run (with and without overlap) through the per-step kernels the owned
  * planes of the other buffer DO hold step - 1 (sub-step n - 1 of a batch of n <= ghost sub-steps still covers every owned plane) and
  * has_previous is 1; it is 0 after a batch that ran as ONE launch of the resident slab kernel (kernel name ca_resident_slab_vn:
- * that launch writes the final state only). population, box, digest and plane counts are exact on slabs in every case and cover
+ * that launch writes the final state only), also where a slab too thin to split ran it in the EDGES phase. population, box, digest and plane counts are exact on slabs in every case and cover
  * the OWNED planes only (ghosts are never counted). Between the EDGES and the INTERIOR phase of a batch the edge zones have been
  * ping-ponged through both buffers and neither holds a state: the call fails with CA3D_ERR_INVALID_ARGUMENT there.
  *

@@ -103,6 +103,78 @@ def ring_geometries(G):
     ]
 
 
+def resident_slab_geometries(G, PZ):
+    """Lone slabs for the resident slab kernel at PZ planes per tile layer (ca_resident.hip, resident_slab_planes: 8 layers, so the
+    plane array has L = nz + 2 K = 8 PZ planes): (label, z0, nz, K, batches). Every batch is 8 sub-steps or longer (`resident_min`:
+    a shorter one takes the per-step kernels). The kernel updates ALL planes of the array in every sub-step, the low ghost of rank 0 (all
+    ones here) and the planes below global plane 0 included, and resolves the plane whose global z is 0 (the dead face is below it) from a
+    run-time plane index: `resident_slab_dead_planes` says where that plane sits in each of these and when a missing mask would show."""
+    L = 8 * PZ
+    k_last = max(8, PZ + 1)
+    d = ((k_last + 1) // PZ) * PZ - 1
+    k_thin = max(9, 2 * PZ - 3)  # the smallest K >= 9 with nz + 2 <= 2 K + 2 * 8: no batch can be split, the edge phase runs it whole
+    k_first = PZ if PZ >= 8 else 2 * PZ
+    out = [
+        ("bottom", 0, L - 16, 8, (8,)),                             # rank 0: global plane 0 is the first owned plane, all ones below it
+        ("low_inside", 3, L - 16, 8, (8,)),                         # global plane 0 is array plane 5, all ones below it
+        ("low_last", k_last - d, L - 2 * k_last, k_last, (8,)),     # global plane 0 is the LAST plane of a tile layer
+        ("middle", 40, L - 18, 9, (9, 8)),                          # no dead face; an odd batch (the other buffer, the other tag parity), then one in place
+        ("thin", 50, L - 2 * k_thin, k_thin, (8, 9)),               # phased: the edge phase IS the resident launch
+        ("top", G - (L - 16), L - 16, 8, (8,)),                     # rank P-1: the first high ghost plane is the copy of global plane 0
+        ("top_first", G - (L - 2 * k_first), L - 2 * k_first, k_first, (9, 8) if k_first >= 9 else (8,)),  # ... and the FIRST plane of a layer with a layer below it
+    ]
+    if PZ >= 34:
+        # a high ghost that straddles plane G: the copy of plane 0 at position 32 or 33 of the last layer, a thread's SECOND y-face entry.
+        # j planes above the last owned one, it shows there after j + 2 sub-steps: j <= 6 in a batch of 8 (position 32 at 34 planes, 33 at 36)
+        j = min(33 - PZ + 8, 6)
+        out.append(("straddle", G - (L - 16) - j, L - 16, 8, (8,)))
+    for label, z0, nz, K, batches in out:
+        assert nz + 2 * K == L and 1 <= K <= nz and z0 >= 0 and z0 + nz <= G and all(8 <= n <= K for n in batches), (PZ, label)
+    return out
+
+
+def resident_slab_thin(nz, K, batches):
+    """No batch can be split into edges and interior (ca3d_slab.cpp, slab_batch: `splittable`): the phased form runs each as one launch."""
+    return all(nz + 2 <= 2 * K + 2 * n for n in batches)
+
+
+def resident_slab_dead_planes(G, PZ, geometries):
+    """The launcher's arithmetic (ca3d_step.cpp, resident_slab_steps) restated: the array plane whose global z is 0 is
+    dead = (-(z0 - K)) mod G, inside the array when dead < L; the kernel looks for it at position dead % PZ of tile layer dead // PZ.
+    Returns (label, layer, position) for every geometry in which a kernel WITHOUT the mask there would leave a wrong owned plane: the
+    wrong plane is `dead` itself after the first sub-step and moves one plane towards the owned ones with every further sub-step —
+      in the low ghost or the first owned plane (1 <= dead <= K): plane K after K - dead + 1 sub-steps;
+      in the high ghost, j planes above the last owned one (dead = K + nz + j): plane K + nz - 1 after j + 2 sub-steps.
+    (dead == 0 has no plane below it in the array: the kernel reads nothing there.)
+    tests/test_slab_lone_cpu.py checks this rule against a stand-in that has no dead face at all."""
+    out = []
+    for label, z0, nz, K, batches in geometries:
+        L = nz + 2 * K
+        dead = (-(z0 - K)) % G
+        if dead >= L:
+            continue
+        n = max(batches)  # (every batch starts from the oracle's planes: the longest one decides)
+        if 1 <= dead <= K:
+            shows = n >= K - dead + 1
+        else:
+            shows = dead >= K + nz and n >= dead - (K + nz) + 2
+        if shows:
+            out.append((label, dead // PZ, dead % PZ))
+    return out
+
+
+def assert_resident_slab_coverage(G, PZ):
+    """The dead face where the kernel resolves it in three different ways: position 0 of a layer (`below_of(0, zlo)`: the plane below
+    comes from the tile underneath), position PZ - 1 (the early `nl`), a position strictly inside (the pass), and, where a y face has
+    two words per thread (34 and 36 planes), one among a thread's second entries (`dmask` at face plane >= 32)."""
+    at = resident_slab_dead_planes(G, PZ, resident_slab_geometries(G, PZ))
+    positions = {p for _, _, p in at}
+    assert 0 in positions and PZ - 1 in positions and any(0 < p < PZ - 1 for p in positions), (PZ, at)
+    assert any(p == 0 and layer > 0 for _, layer, p in at), (PZ, at)  # ... with a tile underneath
+    assert PZ < 34 or any(p >= 32 for p in positions), (PZ, at)
+    return at
+
+
 class Trajectory:
     """Oracle states 0, 1, 2 ... of a full grid, computed on demand and kept (read-only)."""
 
@@ -219,10 +291,11 @@ def write_ghosts(eng, G, layout, state, z0, nz, K):
     return low, high
 
 
-def run_lone_slab(eng, traj, r, z0, nz, K, batches, phased, layout=LAYOUT_PACKED32, options=()):
+def run_lone_slab(eng, traj, r, z0, nz, K, batches, phased, layout=LAYOUT_PACKED32, options=(), after_batch=None):
     """Configure `eng` as the slab [z0, z0 + nz) with K ghost planes of traj's grid, upload its planes of oracle state 0 and run
     `batches` (sub-step counts, each <= K), whole (`slab_step`) or phased (edges, ghost refresh, interior); after every batch the owned
-    planes must equal the oracle's. `options`: (name, value) pairs set after the slab is configured and before the rules."""
+    planes must equal the oracle's. `options`: (name, value) pairs set after the slab is configured and before the rules.
+    `after_batch(n)` is called once the batch of n is committed and compared (for what a test asks of the engine per batch)."""
     G = traj.G
     what = f"G {G} slab z0 {z0} nz {nz} K {K} {'phased' if phased else 'whole'}"
     eng.configure_slab(G, z0, nz, K, layout)
@@ -254,6 +327,8 @@ def run_lone_slab(eng, traj, r, z0, nz, K, batches, phased, layout=LAYOUT_PACKED
             _equal(_read_region(eng, SLAB_RECV_HIGH), high, at + ": recv_high after the interior phase", G, layout, z0 + nz)
         done += n
         _equal(eng.read_state(), owned_planes(G, layout, now, z0, nz), at + ": owned planes", G, layout, z0)
+        if after_batch is not None:
+            after_batch(n)
         if not phased:
             write_ghosts(eng, G, layout, now, z0, nz, K)
 

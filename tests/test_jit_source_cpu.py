@@ -167,10 +167,12 @@ def test_resident_kernel_source_compiles_with_hiprtc():
     assert b"ca3d_jit_resident_stagger" not in code and b"ca3d_jit_resident256_deep" not in code  # removed in round 5 (lost twice)
 
 
-@pytest.mark.parametrize("pz", [20, 24, 34, 36])
+@pytest.mark.parametrize("pz", range(4, 37, 2))
 def test_resident_slab_kernel_fits_its_registers_and_lds(pz):
-    """The slab form of the resident kernel for a rank's share of 1024^3 over eight (20 / 24 planes per tile layer) and over four
-    ranks (34 / 36: the form that reads the rows beside a thread's own inside its main pass). A launch is only resident as a whole at
+    """The slab form of the resident kernel at every depth the launcher selects it for (resident_slab_planes: an even number of planes
+    per tile layer, 4 .. 36), each a kernel of its own: a rank's share of 1024^3 over eight (20 / 24) and over four ranks (34 / 36), up
+    to 16 the form that holds the rows beside a thread's own in registers, above it the one that reads them inside its main pass
+    (tests/test_gpu_resident_slab_depths.py runs them all). A launch is only resident as a whole at
     four waves per SIMD (1024 threads per CU): no more than 128 registers, nothing spilled to scratch, the one LDS image inside
     the CU's 160 KB — read from the code object's metadata."""
     import re

@@ -145,6 +145,75 @@ def test_harness_notices_a_wrong_plane():
         sl.run_lone_slab(Leaky(), traj, r, 2, 30, 5, (5, 3), False)
 
 
+# ---- the resident slab kernel's geometries (tests/test_gpu_resident_slab_depths.py runs them at 1024): 352 is the smallest multiple of
+# 32 above the longest array (288 planes) + the largest z0 of a slab that is no top slab + the longest trajectory
+RES_G = 352
+RES_RULE = "vn_b24_s135"
+
+
+@pytest.fixture(scope="module")
+def res_traj():
+    yield sl.trajectory(RES_G, RES_RULE, rules(RES_RULE), seed=RES_G)
+    for key in [k for k in sl._TRAJECTORIES if k[0] == RES_G]:
+        del sl._TRAJECTORIES[key]
+
+
+@pytest.mark.parametrize("PZ", range(4, 37, 2))
+def test_resident_slab_geometries_put_the_dead_face_everywhere(PZ):
+    """Every depth: the constraints of a geometry (asserted where they are made) and the positions of the dead face a wrong kernel
+    would show at — at 1024, where the GPU test runs, and at the grid of the stand-in below."""
+    for G in (1024, RES_G):
+        at = sl.assert_resident_slab_coverage(G, PZ)
+        assert {"bottom", "low_inside", "low_last", "top", "top_first"} <= {label for label, _, _ in at}
+        by_label = {g[0]: g for g in sl.resident_slab_geometries(G, PZ)}
+        assert sl.resident_slab_thin(*by_label["thin"][2:]) and not any(label in ("middle", "thin") for label, _, _ in at)
+    # a thread's second y-face entry: the last plane of a layer in the low ghost, and plane 32 / 33 of the last layer in the high ghost
+    assert sorted((label, p) for label, _, p in at if p >= 32) == {34: [("low_last", 33), ("straddle", 32)], 36: [("low_last", 35), ("straddle", 33)]}.get(PZ, [])
+
+
+@pytest.mark.parametrize("PZ", [4, 20, 36])
+def test_harness_on_the_resident_slab_geometries(res_traj, PZ):
+    r = rules(RES_RULE)
+    eng = OracleEngine()
+    for label, z0, nz, K, batches in sl.resident_slab_geometries(RES_G, PZ):
+        for phased in (False, True) if sl.resident_slab_thin(nz, K, batches) else (False,):
+            seen = []
+            sl.run_lone_slab(eng, res_traj, r, z0, nz, K, batches, phased, after_batch=seen.append)
+            assert tuple(seen) == batches and eng.steps == sum(batches), label
+
+
+class NoDeadFace(OracleEngine):
+    """The resident slab kernel without its dead-face masks: every plane of the array in every sub-step (the outermost go stale one per
+    sub-step: planes beyond the array read as zeros), and no plane has a dead face below it."""
+
+    def _run(self, n, zones):
+        for s in range(1, n + 1):
+            src = self.bufs[(self.cur + s - 1) & 1]
+            padded = np.concatenate([np.zeros(self.pw, np.uint32), src, np.zeros(self.pw, np.uint32)])
+            out = ol.packed_step_planes(self.G, padded, 1, 1, self.L + 1, self.rules)  # global z = 1 .. L + 1 < G: none is 0
+            self.bufs[(self.cur + s) & 1][:] = out[self.pw:-self.pw]
+
+
+@pytest.mark.parametrize("PZ", [4, 20, 34, 36])
+def test_a_missing_dead_face_shows_exactly_where_it_is_counted(res_traj, PZ):
+    """`resident_slab_dead_planes` counts a geometry when a kernel without the mask must leave a wrong owned plane: the stand-in
+    without any dead face fails on exactly those, and passes the others (`middle`, `thin`: no such plane in the array). A straddling
+    high ghost whose copy of plane 0 lies 7 planes out is not counted in a batch of 8, and does not show."""
+    r = rules(RES_RULE)
+    geometries = sl.resident_slab_geometries(RES_G, PZ)
+    if PZ >= 34:
+        label, z0, nz, K, batches = geometries[-1]
+        geometries.append(("straddle_too_far", RES_G - nz - 7, nz, K, batches))  # 7 planes above the last owned one: 9 sub-steps away
+    counted = {label for label, _, _ in sl.resident_slab_dead_planes(RES_G, PZ, geometries)}
+    assert "straddle_too_far" not in counted
+    for label, z0, nz, K, batches in geometries:
+        if label in counted:
+            with pytest.raises(AssertionError, match="owned planes"):
+                sl.run_lone_slab(NoDeadFace(), res_traj, r, z0, nz, K, batches, False)
+        else:
+            sl.run_lone_slab(NoDeadFace(), res_traj, r, z0, nz, K, batches, False)
+
+
 def test_launch_lengths_follow_the_product_split():
     """`launches` (what the GPU tests assert their residues on) against the ranges written out by hand."""
     # nz 33, K 4, batch of 4: whole sub-steps update [s, 41 - s); phased: low [s, 12 - s), high [29 + s, 41 - s), interior between
