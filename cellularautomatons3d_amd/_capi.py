@@ -193,6 +193,8 @@ SYMBOLS = [
     ("ca3d_ensemble_get_neighbourhood", C.c_int, [_H, C.POINTER(C.c_int)]),
     ("ca3d_ensemble_configure_clustered", C.c_int, [_H, C.c_uint32, C.c_uint32]),
     ("ca3d_ensemble_get_clustered", C.c_int, [_H, C.POINTER(C.c_int)]),
+    ("ca3d_ensemble_set_boundary", C.c_int, [_H, C.c_int]),
+    ("ca3d_ensemble_get_boundary", C.c_int, [_H, C.POINTER(C.c_int)]),
     ("ca3d_ensemble_set_rule_tables_clustered", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint32]),
     ("ca3d_ensemble_set_rules", C.c_int, [_H, C.c_uint32, _i32p, C.c_uint32, _i32p, C.c_uint32, _i32p, C.c_uint32, _u32p, _u32p]),
     ("ca3d_ensemble_upload_state", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.c_size_t]),

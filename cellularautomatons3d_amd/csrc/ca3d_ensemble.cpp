@@ -4,6 +4,8 @@
 // over B workgroups is B universes, each with its own rule table pair, its own step counter, its own summary record and — in
 // ca3d_ensemble_step_until / ca3d_ensemble_step_until_cycle / ca3d_ensemble_step_until_moving / ca3d_ensemble_step_until_trace — its own moment to stop. The host side is bookkeeping: the per-universe arrays, the rule canonicalisation
 // (the engine's own, rules.cpp), and cutting long calls into launches of at most kEnsembleMaxSteps steps.
+// ca3d_ensemble_set_boundary chooses what the steps queued from then on see behind a universe's faces (ca_ensemble_boundary.hip holds the
+// torus and closed-cube forms of the kernels); it is a field of the handle that launch_of copies into every launch.
 // ca3d_ensemble_render_sheet draws a range of universes as the tiles of one contact sheet (render_sheet.hip).
 // ca3d_ensemble_census lists the connected objects of a range of universes (ca_census.hip).
 // ca3d_ensemble_isolate makes objects a census named the only thing in universes of their own (ca_isolate.hip).
@@ -27,6 +29,7 @@ struct ca3d_ensemble
 	uint32_t n = 0; // universes; 0: not configured
 	int neighbourhood = CA3D_ENSEMBLE_VON_NEUMANN; // of every universe: the kernel, and ensemble_rule_words() words of `rules` each
 	bool clustered = false;                        // Moore with edges and corners table pairs of their own (ca3d_ensemble_configure_clustered)
+	int boundary = CA3D_ENSEMBLE_BOUNDARY_REFERENCE; // of the launches queued from now on (ca3d_ensemble_set_boundary); a configure resets it
 	uint32_t *state = nullptr, *prev = nullptr, *rules = nullptr, *steps_done = nullptr, *reason = nullptr;
 	ca3d_summary *records = nullptr;
 	// ca3d_ensemble_step_until_cycle: every universe's anchor state (n x 32 KiB) and its anchor step / anchor hash / period / unused
@@ -154,6 +157,7 @@ EnsembleLaunch launch_of(const ca3d_ensemble *e)
 	l.rules = e->rules;
 	l.neighbourhood = e->neighbourhood;
 	l.clustered = e->clustered;
+	l.boundary = e->boundary;
 	l.records = e->records;
 	l.steps_done = e->steps_done; l.reason = e->reason;
 	l.anchor = e->anchor; l.cycle = e->cycle;
@@ -225,6 +229,7 @@ int configure_ensemble(ca3d_ensemble *e, uint32_t grid_size, uint32_t n_universe
 	e->n = n_universes;
 	e->neighbourhood = neighbourhood;
 	e->clustered = clustered;
+	e->boundary = CA3D_ENSEMBLE_BOUNDARY_REFERENCE;
 	e->has_rules.assign(n_universes, 0);
 	e->has_state.assign(n_universes, 0);
 	e->missing_rules = e->missing_state = n_universes;
@@ -578,6 +583,28 @@ int ca3d_ensemble_get_neighbourhood(ca3d_ensemble_t *e, int *out) CA3D_API_TRY
 	if (!e || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
 	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called");
 	*out = e->neighbourhood;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+// (host state only: the launches already queued carry the boundary they were queued under in their kernel)
+int ca3d_ensemble_set_boundary(ca3d_ensemble_t *e, int boundary) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called");
+	if (boundary != CA3D_ENSEMBLE_BOUNDARY_REFERENCE && boundary != CA3D_ENSEMBLE_BOUNDARY_TORUS && boundary != CA3D_ENSEMBLE_BOUNDARY_CLOSED)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown ensemble boundary %d (CA3D_ENSEMBLE_BOUNDARY_REFERENCE = 0, CA3D_ENSEMBLE_BOUNDARY_TORUS = 1, CA3D_ENSEMBLE_BOUNDARY_CLOSED = 2)",
+		            boundary);
+	e->boundary = boundary;
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_get_boundary(ca3d_ensemble_t *e, int *out) CA3D_API_TRY
+{
+	if (!e || !out) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL argument");
+	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called");
+	*out = e->boundary;
 	return CA3D_OK;
 }
 CA3D_API_CATCH
@@ -1142,6 +1169,10 @@ int ca3d_ensemble_canon_period(ca3d_ensemble_t *e, uint32_t first, uint32_t coun
 		if (periods[k] > longest) longest = periods[k];
 	}
 	if (keys && keys_stride < longest) return fail(CA3D_ERR_INVALID_ARGUMENT, "keys_stride is %u: less than the largest period, %u", keys_stride, longest);
+	if (e->boundary != CA3D_ENSEMBLE_BOUNDARY_REFERENCE)
+		return fail(CA3D_ERR_UNSUPPORTED, "this ensemble's boundary is %s: ca3d_ensemble_canon_period steps inside its own kernel with the reference boundary only "
+		                                  "(ca3d_ensemble_set_boundary(e, CA3D_ENSEMBLE_BOUNDARY_REFERENCE), or step and ca3d_ensemble_canon phase by phase)",
+		            e->boundary == CA3D_ENSEMBLE_BOUNDARY_TORUS ? "CA3D_ENSEMBLE_BOUNDARY_TORUS" : "CA3D_ENSEMBLE_BOUNDARY_CLOSED");
 	if ((rc = require_state(e, first, count))) return rc;
 	for (uint32_t u = first; u < first + count; u++)
 		if (!e->has_rules[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_set_rules has not been called for universe %u", u);

@@ -206,6 +206,7 @@ struct EnsembleLaunch
 	                          // clustered: [B][6] born, survive of the main (27 bits), edges (13) and corners (9) rule-sets
 	int neighbourhood;        // CA3D_ENSEMBLE_VON_NEUMANN / CA3D_ENSEMBLE_MOORE: which kernel, and how `rules` reads
 	bool clustered;           // Moore only: three table pairs a universe (ca_ensemble_clustered64)
+	int boundary;             // CA3D_ENSEMBLE_BOUNDARY_*: what lies behind a universe's faces in this launch's steps (0: the reference's)
 	ca3d_summary *records;    // [B] what the last launch left of each universe
 	uint32_t *steps_done;     // [B] steps taken in the current step-until call (written when stop_mask != 0)
 	uint32_t *reason;         // [B] stop bits that fired in the current call; a universe whose word is set leaves at once
@@ -223,6 +224,9 @@ struct EnsembleLaunch
 	bool reset;               // after an upload: records are rebuilt with step 0 and no previous state (steps == 0)
 };
 hipError_t launch_ensemble(const EnsembleLaunch &l, hipStream_t stream);
+// ca_ensemble_boundary.hip: the kernel of a kind (0 von Neumann, 1 Moore, 2 clustered) and form (0 plain, 1 *_cycle, 2 *_trace, 3 *_moving)
+// under CA3D_ENSEMBLE_BOUNDARY_TORUS or _CLOSED, for ca_ensemble.hip's kernel_of alone; null for anything else
+const void *ensemble_boundary_kernel(int boundary, int kind, int form);
 int ensemble_workgroups_per_cu(int neighbourhood, bool clustered = false); // what the runtime says of that kind's kernel (0: it cannot tell)
 constexpr uint32_t ensemble_rule_words(int neighbourhood, bool clustered = false) // per universe
 {

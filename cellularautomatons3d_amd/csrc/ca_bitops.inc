@@ -27,6 +27,7 @@ __device__ __forceinline__ void ha(u32 a, u32 b, u32 &s, u32 &k) { s = a ^ b; k 
 constexpr int kDppWaveShl1 = 0x130; // lane i <- lane i + 1
 constexpr int kDppWaveRol1 = 0x134; // lane i <- lane (i + 1) % 64
 constexpr int kDppWaveShr1 = 0x138; // lane i <- lane i - 1
+constexpr int kDppWaveRor1 = 0x13C; // lane i <- lane (i + 63) % 64
 template <int CTRL>
 __device__ __forceinline__ u32 dpp_mov(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true); }
 

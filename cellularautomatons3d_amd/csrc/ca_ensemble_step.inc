@@ -1,14 +1,54 @@
 // The step policies of the ensemble kernels: one step of a 64^3 universe held in eight registers a thread (lane = row y, wave w = planes
 // 4 w .. 4 w + 3, a row's two words in one thread), with the rule as data. A policy (VnStep, MooreStep, ClusteredStep) owns the rule's
 // registers (`load`), the size of its LDS exchange (`kXchWords`, two step parities) and one step (`step`, ONE barrier, reached by all
-// 1024 threads). Shared by ca_ensemble.hip, whose text this is, and ca_canon_period.hip. Device code only; include inside
-// namespace ca3d { namespace { ... } }, after ca_bitops.inc, with u32, kWaves and kPT defined.
+// 1024 threads). Shared by ca_ensemble.hip and ca_ensemble_boundary.hip (through ca_ensemble_run.inc) and ca_canon_period.hip. Device
+// code only; include inside namespace ca3d { namespace { ... } }, after ca_bitops.inc, with u32, kWaves and kPT defined.
+//
+// A policy is a template over the universe's BOUNDARY (include/ca3d.h, ca3d_ensemble_set_boundary), which sits in three places of a step:
+// the operand that enters a row's end word (x), the DPP control that brings the neighbouring row (y), the exchange slot that brings the
+// neighbouring wave's plane (z). Faces<B> below is all of it; VnStep, MooreStep and ClusteredStep are the kBoundaryReference forms.
 #pragma once
+
+constexpr int kBoundaryReference = 0, kBoundaryTorus = 1, kBoundaryClosed = 2; // = CA3D_ENSEMBLE_BOUNDARY_*
+
+template <int B>
+struct Faces
+{
+	static_assert(B == kBoundaryReference || B == kBoundaryTorus || B == kBoundaryClosed, "unknown boundary");
+	static constexpr bool kMinusWraps = B == kBoundaryTorus, kPlusWraps = B != kBoundaryClosed; // reference: - faces dead, + faces wrap
+	// cell x - 1 of word h of a row (`other`: the row's other word): word 1's comes from word 0, word 0's from word 1 (x == -1 wraps) or
+	// from nowhere (dead)
+	static __device__ __forceinline__ u32 left(u32 w, u32 other, u32 h)
+	{
+		if constexpr (kMinusWraps) return from_left(w, other);
+		else return from_left(w, h ? other : 0u);
+	}
+	// cell x + 1: word 0's comes from word 1, word 1's from word 0 (x == 64 wraps) or from nowhere
+	static __device__ __forceinline__ u32 right(u32 w, u32 other, u32 h)
+	{
+		if constexpr (kPlusWraps) return from_right(other, w);
+		else return from_right(h ? 0u : other, w);
+	}
+	// row y - 1 (row 63, or zero, into row 0) and row y + 1 (row 0, or zero, into row 63)
+	static __device__ __forceinline__ u32 row_below(u32 v) { return dpp_mov<kMinusWraps ? kDppWaveRor1 : kDppWaveShr1>(v); }
+	static __device__ __forceinline__ u32 row_above(u32 v) { return dpp_mov<kPlusWraps ? kDppWaveRol1 : kDppWaveShl1>(v); }
+	// whether a wave's plane z - 1 / z + 1 exists (else it is dead), and the wave whose last / first plane it then is. Ask first: without
+	// a plane below the answer is no wave of the 16, and a slot of it lies outside the exchange (the wave above is always one of them)
+	static __device__ __forceinline__ bool has_below(u32 wave) { return kMinusWraps || wave; }
+	static __device__ __forceinline__ bool has_above(u32 wave) { return kPlusWraps || wave + 1u < kWaves; }
+	static __device__ __forceinline__ u32 wave_below(u32 wave)
+	{
+		if constexpr (kMinusWraps) return (wave - 1u) & (kWaves - 1u);
+		else return wave - 1u;
+	}
+	static __device__ __forceinline__ u32 wave_above(u32 wave) { return (wave + 1u) & (kWaves - 1u); }
+};
 
 __device__ __forceinline__ u32 mux(u32 sel, u32 one, u32 zero) { return next_state(sel, one, zero); } // sel ? one : zero, bit by bit
 
 // ---- von Neumann: the table pair in one word, lut_s | lut_b << 8 (7 bits each)
-struct VnStep
+template <int B>
+struct VnStepT
 {
 	static constexpr u32 kXchWords = 2u * kWaves * 2u * 2u * 64u; // [step parity][wave][first / last plane][word][row]: 32 KiB
 	// leaf[c] = all-ones where a DEAD cell with c live neighbours is born, leaf[7 + c] where a LIVE one survives
@@ -50,10 +90,8 @@ struct VnStep
 			for (u32 h = 0; h < 2u; h++)
 			{
 				const u32 w = s[p][h], other = s[p][h ^ 1u];
-				const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
-				const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
-				const u32 ym = dpp_mov<kDppWaveShr1>(w);    // row y - 1 (zero into row 0)
-				const u32 yp = dpp_mov<kDppWaveRol1>(w);    // row y + 1 (row 0 into row 63)
+				const u32 l = Faces<B>::left(w, other, h), r = Faces<B>::right(w, other, h);
+				const u32 ym = Faces<B>::row_below(w), yp = Faces<B>::row_above(w);
 				o[p][h] = rule(w, l, r, ym, yp, bl[h], ab[h]);
 			}
 		};
@@ -65,24 +103,26 @@ struct VnStep
 #pragma unroll
 		for (u32 h = 0; h < 2u; h++)
 		{
-			below[h] = wave ? xch[slot(buf, wave - 1u, 1u, h, row)] : 0u;       // z == -1 is dead
-			above[h] = xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)]; // z == 64 is plane 0
+			below[h] = Faces<B>::has_below(wave) ? xch[slot(buf, Faces<B>::wave_below(wave), 1u, h, row)] : 0u; // z == -1: plane 63, or dead
+			above[h] = Faces<B>::has_above(wave) ? xch[slot(buf, Faces<B>::wave_above(wave), 0u, h, row)] : 0u; // z == 64: plane 0, or dead
 		}
 		plane(0u, below, s[1]);
 		plane(kPT - 1u, s[kPT - 2], above);
 	}
 };
+struct VnStep : VnStepT<kBoundaryReference> {}; // (a type of its own name: what is named after it, a kernel's LDS arrays, keeps its name)
 
 // ---- Moore: two words per universe, born | survive, bit c (0 .. 26) = at c live neighbours of 26
 // The count is separable, the cell itself included: T = sum over the 3 x 3 x 3 cube, 0 .. 27. x: (left, self, right) of a word -> 2 bit
 // planes; y: plus the x-sums of rows y - 1 and y + 1 (DPP) -> 4 bit planes, the PLANE SUM 0 .. 9; z: plus the plane sums of planes z - 1
-// and z + 1 -> 5 bit planes. Every axis applies its own boundary (- dead, + wraps) to what the axis before it produced, which is the
-// reference's per-axis rule on edges and corners too. A dead cell looks up born[T], a live one survive[T - 1]: the survive table is
-// shifted by one when it is loaded and both are indexed by T.
+// and z + 1 -> 5 bit planes. Every axis applies its own boundary (reference: - dead, + wraps) to what the axis before it produced, which
+// is the reference's per-axis rule on edges and corners too, and a torus or a closed cube when every axis wraps or none does. A dead cell
+// looks up born[T], a live one survive[T - 1]: the survive table is shifted by one when it is loaded and both are indexed by T.
 // The plane sums of a wave's first and last plane go through the LDS exchange (8 words a thread and plane, two ds_write_b128 /
 // ds_read_b128 each) instead of the raw words with the sums recomputed: 4 writes and 8 reads of 16 bytes a step against 4 + 4 of 4 bytes
 // and the x and y sums of four more words, 64 vector instructions (DESIGN 12.1).
-struct MooreStep
+template <int B>
+struct MooreStepT
 {
 	static constexpr u32 kXchWords = 2u * kWaves * 2u * 2u * 64u * 4u; // [step parity][wave][first / last plane][word][row][sum plane]: 128 KiB
 	// The update is a multiplexer tree over (alive, T4 .. T0) with 28 + 28 workgroup-uniform leaves. A select reads ONE scalar operand, so
@@ -107,12 +147,11 @@ struct MooreStep
 	// x and y of one word: the plane sum
 	static __device__ __forceinline__ Sum4 plane_sum(u32 w, u32 other, u32 h)
 	{
-		const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
-		const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
+		const u32 l = Faces<B>::left(w, other, h), r = Faces<B>::right(w, other, h);
 		u32 x0, x1;
 		fa(l, w, r, x0, x1);
-		const u32 m0 = dpp_mov<kDppWaveShr1>(x0), m1 = dpp_mov<kDppWaveShr1>(x1); // row y - 1 (zero into row 0)
-		const u32 p0 = dpp_mov<kDppWaveRol1>(x0), p1 = dpp_mov<kDppWaveRol1>(x1); // row y + 1 (row 0 into row 63)
+		const u32 m0 = Faces<B>::row_below(x0), m1 = Faces<B>::row_below(x1);
+		const u32 p0 = Faces<B>::row_above(x0), p1 = Faces<B>::row_above(x1);
 		Sum4 q;
 		u32 c0, s1, c1, k;
 		fa(x0, m0, p0, q.b[0], c0);
@@ -178,13 +217,25 @@ struct MooreStep
 #pragma unroll
 		for (u32 h = 0; h < 2u; h++)
 		{
-			Sum4 below = get(wave ? wave - 1u : 0u, 1u, h);
-			if (!wave) below = Sum4{{0u, 0u, 0u, 0u}}; // z == -1 is dead
+			// A plane that does not exist is read from a slot inside the exchange and zeroed. (The - side is written on `wave` itself and
+			// the + side keeps both sums as temporaries of the call: through Faces' helpers the reference kernels come out with
+			// instructions in another order, DESIGN 12.12)
+			Sum4 below = get(Faces<B>::kMinusWraps ? Faces<B>::wave_below(wave) : wave ? wave - 1u : 0u, 1u, h); // z == -1: plane 63, or
+			if (!Faces<B>::kMinusWraps && !wave) below = Sum4{{0u, 0u, 0u, 0u}};                                   // dead
 			o[0][h] = rule(s[0][h], below, get(wave, 0u, h), q[0][h]);
-			o[kPT - 1][h] = rule(s[kPT - 1][h], q[kPT - 3][h], get(wave, 1u, h), get((wave + 1u) & (kWaves - 1u), 0u, h)); // z == 64 is plane 0
+			if constexpr (Faces<B>::kPlusWraps)
+				o[kPT - 1][h] = rule(s[kPT - 1][h], q[kPT - 3][h], get(wave, 1u, h), get(Faces<B>::wave_above(wave), 0u, h)); // z == 64 is plane 0
+			else
+			{
+				// (read ahead of the wave's own sums: with the two reads the other way round the closed kernels spill)
+				Sum4 above = get(Faces<B>::wave_above(wave), 0u, h);
+				if (!Faces<B>::has_above(wave)) above = Sum4{{0u, 0u, 0u, 0u}}; // z == 64 is dead
+				o[kPT - 1][h] = rule(s[kPT - 1][h], q[kPT - 3][h], get(wave, 1u, h), above);
+			}
 		}
 	}
 };
+struct MooreStep : MooreStepT<kBoundaryReference> {};
 
 // ---- clustered: six words per universe, born | survive of the main (Moore, counts 0 .. 26), edges (0 .. 12) and corners (0 .. 8) rule-sets
 // A cell is alive afterwards if ANY of the three lookups says so (oracle/ca_oracle.c, lit_next). A Moore total does not separate the
@@ -195,7 +246,8 @@ struct MooreStep
 // Every axis applies its own boundary to what the axis before it produced (x: alignbit, y: DPP, z: the exchange), as in MooreStep.
 // The RAW words of a wave's first and last plane go through the von Neumann exchange (32 KiB); a thread then slides a window of three
 // planes' sets over the six planes it sees, one word of a row at a time: 21 registers of sets alive, not 6 x 7 x 2.
-struct ClusteredStep
+template <int B>
+struct ClusteredStepT
 {
 	static constexpr u32 kXchWords = VnStep::kXchWords;
 	// all-zeros / all-ones per table bit: the born leaves in vector registers, the survive leaves in scalar ones (a select reads ONE scalar)
@@ -225,13 +277,11 @@ struct ClusteredStep
 	// x and y of one word
 	static __device__ __forceinline__ Set plane_set(u32 w, u32 other, u32 h)
 	{
-		const u32 l = from_left(w, h ? other : 0u); // cell x - 1: word 0's comes from nowhere (dead), word 1's from word 0
-		const u32 r = from_right(other, w);         // cell x + 1: word 0's from word 1, word 1's from word 0 (x == 64 wraps)
+		const u32 l = Faces<B>::left(w, other, h), r = Faces<B>::right(w, other, h);
 		Set q;
 		q.c = w;
-		// row y - 1 (zero into row 0), row y + 1 (row 0 into row 63)
-		sum4(l, r, dpp_mov<kDppWaveShr1>(w), dpp_mov<kDppWaveRol1>(w), q.d);
-		sum4(dpp_mov<kDppWaveShr1>(l), dpp_mov<kDppWaveShr1>(r), dpp_mov<kDppWaveRol1>(l), dpp_mov<kDppWaveRol1>(r), q.as);
+		sum4(l, r, Faces<B>::row_below(w), Faces<B>::row_above(w), q.d);
+		sum4(Faces<B>::row_below(l), Faces<B>::row_below(r), Faces<B>::row_above(l), Faces<B>::row_above(r), q.as);
 		return q;
 	}
 	// a multiplexer tree over N leaves (counts 0 .. N - 1) and the count's bit planes p[0] ..; a node without a partner moves up as it is
@@ -288,8 +338,8 @@ struct ClusteredStep
 #pragma unroll
 		for (u32 h = 0; h < 2u; h++)
 		{
-			below[h] = wave ? xch[VnStep::slot(buf, wave - 1u, 1u, h, row)] : 0u;       // z == -1 is dead
-			above[h] = xch[VnStep::slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)]; // z == 64 is plane 0
+			below[h] = Faces<B>::has_below(wave) ? xch[VnStep::slot(buf, Faces<B>::wave_below(wave), 1u, h, row)] : 0u; // z == -1: plane 63, or dead
+			above[h] = Faces<B>::has_above(wave) ? xch[VnStep::slot(buf, Faces<B>::wave_above(wave), 0u, h, row)] : 0u; // z == 64: plane 0, or dead
 		}
 #pragma unroll
 		for (u32 h = 0; h < 2u; h++)
@@ -306,3 +356,4 @@ struct ClusteredStep
 		}
 	}
 };
+struct ClusteredStep : ClusteredStepT<kBoundaryReference> {};

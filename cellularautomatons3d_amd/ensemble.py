@@ -19,6 +19,7 @@ _i32p = C.POINTER(C.c_int32)
 
 ALL = ENSEMBLE_ALL
 NEIGHBOURHOODS = ("von neumann", "moore")  # index = enum ca3d_ensemble_neighbourhood
+BOUNDARIES = ("reference", "torus", "closed")  # index = enum ca3d_ensemble_boundary
 
 
 class Ensemble:
@@ -51,7 +52,8 @@ class Ensemble:
 
     def configure(self, n: int, grid_size: int = 64, neighbourhood: str = "von neumann", clustered: bool = False) -> None:
         """`neighbourhood`: "von neumann" or "moore" — of every universe; the rules set afterwards must be of that kind.
-        `clustered` (Moore only): every universe carries edges and corners table pairs beside its main one, the reference's clustered rule."""
+        `clustered` (Moore only): every universe carries edges and corners table pairs beside its main one, the reference's clustered rule.
+        Every configure goes back to the "reference" boundary; `set_boundary` chooses another afterwards."""
         if neighbourhood not in NEIGHBOURHOODS:
             raise ValueError(f"unknown ensemble neighbourhood {neighbourhood!r}: one of {NEIGHBOURHOODS}")
         if clustered and neighbourhood != "moore":
@@ -61,6 +63,21 @@ class Ensemble:
         else:
             _capi.check(self._lib.ca3d_ensemble_configure_neighbourhood(self._h, grid_size, n, NEIGHBOURHOODS.index(neighbourhood)))
         self.n, self.grid_size = n, grid_size
+
+    def set_boundary(self, name: str) -> None:
+        """`ca3d_ensemble_set_boundary`: what the steps queued from now on see behind a universe's six faces — "reference" (- faces
+        dead, + faces wrap: the default), "torus" (all wrap) or "closed" (all dead); `host.ensemble_step` is the definition. Moves nothing
+        and waits for nothing; `canon_period` is refused while the mode is not "reference"."""
+        if name not in BOUNDARIES:
+            raise ValueError(f"unknown ensemble boundary {name!r}: one of {BOUNDARIES}")
+        _capi.check(self._lib.ca3d_ensemble_set_boundary(self._h, BOUNDARIES.index(name)))
+
+    @property
+    def boundary(self) -> str:
+        """The boundary the next step runs under (`Ca3dError` -2 before `configure`)."""
+        out = C.c_int()
+        _capi.check(self._lib.ca3d_ensemble_get_boundary(self._h, C.byref(out)))
+        return BOUNDARIES[out.value]
 
     @property
     def neighbourhood(self) -> str:

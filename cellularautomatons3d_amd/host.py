@@ -489,6 +489,77 @@ def census(words, max_components: int = 64) -> Tuple[np.ndarray, int, int]:
     return out, n, int(np.count_nonzero(rest))
 
 
+# ------------------------------------------------------------------------------------------- ensemble step
+# The definition of one step of an ensemble universe under each boundary (include/ca3d.h, ca3d_ensemble_set_boundary) in executable
+# form: what the ca_ensemble_* kernels must compute. "reference" is the reference's own boundary (- faces dead, + faces wrap).
+
+ENSEMBLE_KINDS = ("von neumann", "moore", "clustered")
+ENSEMBLE_BOUNDARIES = ("reference", "torus", "closed")  # index = enum ca3d_ensemble_boundary
+
+
+def _neighbour(a: np.ndarray, axis: int, d: int, boundary: str) -> np.ndarray:
+    """The array whose entry at p is a's entry at p + d along `axis` (d = -1 or +1): np.roll is a wrapping face, a zeroed slice after
+    the roll a dead one."""
+    out = np.roll(a, -d, axis=axis)
+    wraps = boundary == "torus" or (boundary == "reference" and d > 0)
+    if not wraps:
+        edge = [slice(None)] * a.ndim
+        edge[axis] = -1 if d > 0 else 0
+        out[tuple(edge)] = 0
+    return out
+
+
+def _table(mask: int, n: int) -> np.ndarray:
+    return ((int(mask) >> np.arange(n)) & 1).astype(np.uint8)
+
+
+def ensemble_step(words, kind: str, tables, boundary: str = "reference") -> np.ndarray:
+    """One step of ONE packed 64^3 universe (8192 words) -> its packed successor, in plain numpy on the unpacked [z, y, x] array.
+
+    `kind`: "von neumann" (counts 0 .. 6 over the six face neighbours), "moore" (0 .. 26) or "clustered". `tables`: the masks
+    `Ensemble.set_rule_tables` / `set_clustered_tables` take — (born, survive), bit c = at count c; clustered: (born[3], survive[3]) for
+    the main (Moore, 0 .. 26), edges (0 .. 12) and corners (0 .. 8) rule-sets, whose three lookups are ORed; a live cell looks up
+    survive at its count, a dead one born. `boundary`: "reference", "torus" or "closed".
+    Every axis applies its boundary to what the axis before it produced — x, then y, then z — so an edge or corner neighbour exists
+    exactly when each of its three coordinates does; the counts are formed separably for that reason."""
+    if kind not in ENSEMBLE_KINDS:
+        raise ValueError(f"unknown ensemble kind {kind!r}: one of {ENSEMBLE_KINDS}")
+    if boundary not in ENSEMBLE_BOUNDARIES:
+        raise ValueError(f"unknown ensemble boundary {boundary!r}: one of {ENSEMBLE_BOUNDARIES}")
+    G = 64
+    w = np.ascontiguousarray(words, dtype="<u4").ravel()
+    if w.size != words_per_buffer(G):
+        raise ValueError("a universe holds 8192 words")
+    a = np.unpackbits(w.view(np.uint8), bitorder="little").reshape(G, G, G)  # [z, y, x]: the flat index is x + 64 y + 4096 z
+    Z, Y, X = 0, 1, 2
+
+    def both(v, axis):  # the two neighbours along one axis, summed
+        return _neighbour(v, axis, -1, boundary) + _neighbour(v, axis, +1, boundary)
+
+    alive = a.astype(bool)
+    born, survive = tables
+    if kind == "von neumann":
+        count = both(a, X) + both(a, Y) + both(a, Z)
+        nxt = np.where(alive, _table(survive, 7)[count], _table(born, 7)[count])
+    elif kind == "moore":
+        s = a
+        for axis in (X, Y, Z):
+            s = s + both(s, axis)
+        count = s - a  # the 3 x 3 x 3 sum without the cell itself
+        nxt = np.where(alive, _table(survive, 27)[count], _table(born, 27)[count])
+    else:
+        left, right = _neighbour(a, X, -1, boundary), _neighbour(a, X, +1, boundary)
+        faces_in_plane = left + right + both(a, Y)            # the 4 face neighbours in the cell's own plane
+        diagonals_in_plane = both(left, Y) + both(right, Y)   # the 4 in-plane diagonals
+        faces = faces_in_plane + both(a, Z)                   # 0 .. 6
+        edges = diagonals_in_plane + both(faces_in_plane, Z)  # 0 .. 12
+        corners = both(diagonals_in_plane, Z)                 # 0 .. 8
+        nxt = np.zeros_like(a)
+        for count, n, b, s in ((faces + edges + corners, 27, born[0], survive[0]), (edges, 13, born[1], survive[1]), (corners, 9, born[2], survive[2])):
+            nxt |= np.where(alive, _table(s, n)[count], _table(b, n)[count])
+    return np.packbits(nxt.astype(np.uint8).ravel(), bitorder="little").view("<u4").copy()
+
+
 # ------------------------------------------------------------------------------------------------- isolate
 # The definition of ca3d_ensemble_isolate (include/ca3d.h) in executable form, for one universe.
 

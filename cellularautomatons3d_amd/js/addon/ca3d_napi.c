@@ -1085,6 +1085,39 @@ static napi_value js_ensemble_clustered(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* ensembleSetBoundary(handle, boundary): 0 reference, 1 torus, 2 closed (ca3d_ensemble_set_boundary) */
+static napi_value js_ensemble_set_boundary(napi_env env, napi_callback_info info)
+{
+	napi_value argv[2];
+	if (!get_args(env, info, 2, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	int32_t boundary = 0;
+	if (!e) return NULL;
+	if (napi_get_value_int32(env, argv[1], &boundary) != napi_ok)
+	{
+		napi_throw_type_error(env, NULL, "boundary: a number");
+		return NULL;
+	}
+	int rc = ca3d_ensemble_set_boundary(e, (int)boundary);
+	if (rc) return throw_ca3d(env, rc);
+	return undefined(env);
+}
+
+/* ensembleBoundary(handle) -> 0 | 1 | 2 */
+static napi_value js_ensemble_boundary(napi_env env, napi_callback_info info)
+{
+	napi_value argv[1];
+	if (!get_args(env, info, 1, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	if (!e) return NULL;
+	int b = 0;
+	int rc = ca3d_ensemble_get_boundary(e, &b);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_int32(env, b, &v);
+	return v;
+}
+
 /* ensembleSetClusteredTables(handle, first, count, Uint32Array born masks, Uint32Array survive masks) — 3 words (main, edges, corners) a
  * rule, 1 or count rules each */
 static napi_value js_ensemble_set_clustered_tables(napi_env env, napi_callback_info info)
@@ -1663,6 +1696,7 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleSetRuleTables", js_ensemble_set_rule_tables},
 	    {"ensembleConfigureNeighbourhood", js_ensemble_configure_neighbourhood}, {"ensembleNeighbourhood", js_ensemble_neighbourhood},
 	    {"ensembleConfigureClustered", js_ensemble_configure_clustered}, {"ensembleClustered", js_ensemble_clustered},
+	    {"ensembleSetBoundary", js_ensemble_set_boundary}, {"ensembleBoundary", js_ensemble_boundary},
 	    {"ensembleSetClusteredTables", js_ensemble_set_clustered_tables},
 	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats},
 	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}, {"ensembleCompose", js_ensemble_compose},

@@ -426,6 +426,7 @@ class EngineGroup
 // own moment to stop (include/ca3d.h). Synchronous.
 const ENSEMBLE_ALL = 0xFFFFFFFF, ENSEMBLE_WORDS = 8192;
 const ENSEMBLE_NEIGHBOURHOODS = ["von neumann", "moore"]; // index = enum ca3d_ensemble_neighbourhood
+const ENSEMBLE_BOUNDARIES = ["reference", "torus", "closed"]; // index = enum ca3d_ensemble_boundary
 class Ensemble
 {
 	constructor(device)
@@ -436,16 +437,30 @@ class Ensemble
 	}
 	close() { if (this._e) { this._a.ensembleDestroy(this._e); this._e = null; } }
 	/** neighbourhood: "von neumann" (default) or "moore" — of every universe; the rules set afterwards must be of that kind.
-	 *  clustered (Moore only): every universe carries edges and corners table pairs beside its main one */
-	configure(n, gridSize, neighbourhood, clustered = false)
+	 *  clustered (Moore only): every universe carries edges and corners table pairs beside its main one
+	 *  options.boundary: what setBoundary takes; a configure without it goes back to "reference" */
+	configure(n, gridSize, neighbourhood, clustered = false, options = {})
 	{
+		const boundary = options.boundary === undefined ? "reference" : options.boundary;
+		if (ENSEMBLE_BOUNDARIES.indexOf(boundary) < 0) throw new Error(`unknown ensemble boundary ${JSON.stringify(boundary)}: one of ${ENSEMBLE_BOUNDARIES.join(", ")}`);
 		const nb = ENSEMBLE_NEIGHBOURHOODS.indexOf(neighbourhood === undefined ? "von neumann" : neighbourhood);
 		if (nb < 0) throw new Error(`unknown ensemble neighbourhood ${JSON.stringify(neighbourhood)}: "von neumann" or "moore"`);
 		if (clustered && ENSEMBLE_NEIGHBOURHOODS[nb] !== "moore") throw new Error(`a clustered ensemble's main list is Moore (got neighbourhood ${JSON.stringify(neighbourhood)})`);
 		if (clustered) this._a.ensembleConfigureClustered(this._e, gridSize === undefined ? 64 : gridSize, n);
 		else this._a.ensembleConfigureNeighbourhood(this._e, gridSize === undefined ? 64 : gridSize, n, nb);
 		this.n = n;
+		if (boundary !== "reference") this.setBoundary(boundary);
 	}
+	/** ca3d_ensemble_set_boundary: what the steps queued from now on see behind a universe's six faces — "reference" (- faces dead, + faces
+	 *  wrap: the default), "torus" (all wrap) or "closed" (all dead). Moves nothing; canonPeriod is refused while it is not "reference" */
+	setBoundary(name)
+	{
+		const b = ENSEMBLE_BOUNDARIES.indexOf(name);
+		if (b < 0) throw new Error(`unknown ensemble boundary ${JSON.stringify(name)}: one of ${ENSEMBLE_BOUNDARIES.join(", ")}`);
+		this._a.ensembleSetBoundary(this._e, b);
+	}
+	/** the boundary the next step runs under, as its string (throws before configure) */
+	get boundary() { return ENSEMBLE_BOUNDARIES[this._a.ensembleBoundary(this._e)]; }
 	/** the configured neighbourhood as its string (throws before configure) */
 	get neighbourhood() { return ENSEMBLE_NEIGHBOURHOODS[this._a.ensembleNeighbourhood(this._e)]; }
 	/** whether the ensemble was configured clustered (throws before configure) */
@@ -700,7 +715,7 @@ class Ensemble
 }
 
 module.exports = {
-	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, STOP_MOVING, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
+	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, ENSEMBLE_BOUNDARIES, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, STOP_MOVING, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
 	initialState, dispatchShape, traceSamples, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
 };

@@ -412,6 +412,35 @@ int ca3d_ensemble_configure_clustered(ca3d_ensemble_t *e, uint32_t grid_size, ui
 int ca3d_ensemble_get_clustered(ca3d_ensemble_t *e, int *out);
 int ca3d_ensemble_set_rule_tables_clustered(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *born_masks,
                                             const uint32_t *survive_masks, uint32_t n_rules);
+/* The BOUNDARY of every universe of an ensemble: what a step sees behind the six faces of the 64^3 cube.
+ *   CA3D_ENSEMBLE_BOUNDARY_REFERENCE  the reference's, and the default: the - faces are dead, the + faces wrap (cell 64 is cell 0, cell -1
+ *                                     is no cell), per axis — what every engine path computes and what an ensemble always computed;
+ *   CA3D_ENSEMBLE_BOUNDARY_TORUS      all six faces wrap: coordinates are taken modulo 64 on every axis;
+ *   CA3D_ENSEMBLE_BOUNDARY_CLOSED     all six faces are dead: a cell outside the cube is never alive.
+ * Every axis applies its own boundary to what the axis before it produced, so edge and corner neighbours of a Moore or clustered rule
+ * follow the same words (kernels ca_ensemble_<kind>64[_cycle|_trace|_moving]_torus / _closed, beside the reference's twelve). In plain
+ * numpy: host.ensemble_step of the Python package.
+ * ca3d_ensemble_set_boundary may be called any time after a configure and applies to the launches queued after it; the steps already
+ * queued keep the boundary they were queued under. It moves no state, rebuilds no record and waits for nothing. Every
+ * ca3d_ensemble_configure* resets the mode to CA3D_ENSEMBLE_BOUNDARY_REFERENCE. An unknown value: CA3D_ERR_INVALID_ARGUMENT; either call
+ * before any configure: CA3D_ERR_NOT_CONFIGURED.
+ * ca3d_ensemble_step, _step_until, _step_until_cycle, _step_until_moving and _step_until_trace honour the mode, through every launch a
+ * long call is cut into. EXTINCT, STILL, PERIODIC, records and samples are defined on the state alone and mean what they always meant.
+ * MOVING keeps its definition too — anchor and state both clear of every face, d = box_min(C) - box_min(A) != 0, C equal to A translated
+ * by d: in a torus a ship that crossed a seam between anchor and check point is therefore reported with a shift CONGRUENT to its true
+ * displacement modulo 64 per axis (a ship that left through x = 63 and went 8 cells reports dx = -56).
+ * Census, isolate, compose, canon, the sheet, seeding, upload and read never step and are allowed in every mode (the census keeps its
+ * closed cube: no face joins objects); CA3D_ISOLATE_COPY_RULES and CA3D_COMPOSE_COPY_RULES ignore the boundary of either ensemble.
+ * ca3d_ensemble_canon_period steps inside its own kernel with the reference boundary: on an ensemble whose mode is not
+ * CA3D_ENSEMBLE_BOUNDARY_REFERENCE it returns CA3D_ERR_UNSUPPORTED and touches nothing. */
+enum ca3d_ensemble_boundary
+{
+	CA3D_ENSEMBLE_BOUNDARY_REFERENCE = 0,
+	CA3D_ENSEMBLE_BOUNDARY_TORUS = 1,
+	CA3D_ENSEMBLE_BOUNDARY_CLOSED = 2
+};
+int ca3d_ensemble_set_boundary(ca3d_ensemble_t *e, int boundary);
+int ca3d_ensemble_get_boundary(ca3d_ensemble_t *e, int *out);
 int ca3d_ensemble_set_rules(ca3d_ensemble_t *e, uint32_t universe,
                             const int32_t *main_offsets, uint32_t n_main,
                             const int32_t *edges_offsets, uint32_t n_edges,

@@ -103,6 +103,12 @@ host.canon_period of the CPU oracle's phases in sampled universes, and canon_pha
 the call's everywhere. Reported: medians of --repeats measurements. No ratio is required. Written to
 profiles/ensemble_canon_period_64.json unless --out says otherwise.
 
+With --boundary: the plain step kernel of each new boundary mode (Ensemble.set_boundary: "torus", "closed") against the reference
+boundary's kernel on the same universes, for all three kinds (von Neumann, Moore, clustered) at B = 256 and 1024: Ensemble.step(--steps)
+from the same uploaded fills, the modes alternating inside one process, hipEvent times. Before timing, the state of sampled universes
+after 3 steps must equal host.ensemble_step's under every mode. Reported: medians of --repeats measurements and the ratio to the
+reference's. No ratio is required. Written to profiles/ensemble_boundary_64.json unless --out says otherwise.
+
 Needs an MI355X; without one the engines cannot be created and the tool fails.
 """
 import argparse
@@ -156,6 +162,70 @@ def timed(fn, sync, min_seconds):
         fn()
     sync()
     return (time.perf_counter() - t0) / reps
+
+
+def boundary_rows(args):
+    """Ensemble.step under "torus" and "closed" against "reference": one row per (kernel, B)."""
+    from cellularautomatons3d_amd.ensemble import BOUNDARIES
+
+    def masks(s, bits):
+        return sum(1 << v for v in host.rules_components_to_values(s)) & ((1 << bits) - 1)
+
+    ens = Ensemble(0)
+    rows = []
+    for kind in ("von neumann", "moore", "clustered"):
+        clustered = kind == "clustered"
+        nb = "moore" if clustered else kind
+        if clustered:
+            keys = ("born", "survive", "born_edges", "survive_edges", "born_corners", "survive_corners")
+            tables = ([masks(CLUSTERED[keys[2 * i]], b) for i, b in enumerate((27, 13, 9))], [masks(CLUSTERED[keys[2 * i + 1]], b) for i, b in enumerate((27, 13, 9))])
+        else:
+            tables = (masks(RULES[nb][0], 27 if nb == "moore" else 7), masks(RULES[nb][1], 27 if nb == "moore" else 7))
+        for B in args.universes:
+            words = fills(B)
+            ens.configure(B, neighbourhood=nb, clustered=clustered)
+            if clustered:
+                ens.set_clustered_tables(0, tables[0], tables[1])
+            else:
+                ens.set_rule_tables(0, tables[0], tables[1])
+            sample = sorted({0, B // 2, B - 1})
+            for mode in BOUNDARIES:
+                ens.set_boundary(mode)
+                ens.upload_state(0, words)
+                ens.step(3)
+                got = ens.read_state()
+                for u in sample:
+                    want = words[u]
+                    for _ in range(3):
+                        want = host.ensemble_step(want, kind, tables, mode)
+                    if not np.array_equal(got[u], want):
+                        raise SystemExit(f"{kind} B={B} {mode}: universe {u} differs from host.ensemble_step after 3 steps")
+
+            def call(mode):
+                """One step call from the uploaded fills -> event ms."""
+                ens.set_boundary(mode)
+                ens.upload_state(0, words)
+                ens.step(args.steps)
+                ens.synchronize()
+                return ens.stats().gpu_ms
+
+            for mode in BOUNDARIES:
+                call(mode)  # warm-up: every kernel has run once
+            times = {mode: [] for mode in BOUNDARIES}
+            for _ in range(args.repeats):
+                for mode in BOUNDARIES:
+                    times[mode].append(call(mode))
+            med = {mode: statistics.median(t) for mode, t in times.items()}
+            row = {"kernel": kind, "universes": B, "steps": args.steps, "states_verified": len(sample)}
+            for mode in BOUNDARIES:
+                row[mode] = {"event_us": med[mode] * 1e3, "event_us_min_max": [min(times[mode]) * 1e3, max(times[mode]) * 1e3],
+                             "cell_steps_per_s": B * CELLS * args.steps / (med[mode] * 1e-3)}
+            row["torus_over_reference_event"] = med["torus"] / med["reference"]
+            row["closed_over_reference_event"] = med["closed"] / med["reference"]
+            rows.append(row)
+            print(json.dumps(row))
+    ens.close()
+    return rows
 
 
 def cycle_rows(args):
@@ -844,11 +914,12 @@ def main():
     ap.add_argument("--compose", action="store_true", help="measure compose against the read_state + host.compose + upload_state loop instead (B = 256)")
     ap.add_argument("--canon", action="store_true", help="measure canon against the read_state + host.canon loop instead (B = 256)")
     ap.add_argument("--canon-period", action="store_true", help="measure canon_period against canon_phases instead (B = 256)")
+    ap.add_argument("--boundary", action="store_true", help="measure step under the torus and closed boundaries against the reference boundary instead (all three kinds; B = 256 1024)")
     ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose, --canon: destinations / universes the CPU loop is run on")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.boundary else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -864,6 +935,26 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.boundary:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_boundary_64.json")
+        rows = boundary_rows(args)
+        result = {
+            "what": "B universes of 64^3 (random fills, seeds 1 .. B) stepped by ONE Ensemble.step call under each boundary mode (set_boundary): the plain kernels "
+                    "ca_ensemble_<kind>64_torus and ca_ensemble_<kind>64_closed against ca_ensemble_<kind>64 on the same universes, for von Neumann, Moore and "
+                    "clustered ensembles under this tool's rules",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "timing": f"event_us: hipEvent time around the call's launches (ca3d_ensemble_get_stats); medians of {args.repeats} measurements, the three modes "
+                      "alternating in one process, the fills uploaded again before each, after every mode's state equalled host.ensemble_step in the sampled "
+                      "universes after 3 steps",
+            "not_measured": "the *_cycle, *_trace and *_moving forms, other B, other rules",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.canon_period:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_canon_period_64.json")
         rows = canon_period_rows(args)
