@@ -76,6 +76,8 @@ class IsolatedStruct(C.Structure):
 #: placement of `ca3d_ensemble_isolate` (the low byte of its flags), and its one flag bit
 ISOLATE_PLACEMENTS = {"keep": 0, "centre": 1, "origin": 2}
 ISOLATE_COPY_RULES = 0x100
+#: enum CA3D_CONNECT_*: the connectivity of `ca3d_ensemble_census_connected` / `ca3d_ensemble_isolate_connected`
+CONNECTIVITIES = {"closed": 0, "torus": 1}
 
 
 class ComposePartStruct(C.Structure):
@@ -212,6 +214,10 @@ SYMBOLS = [
     ("ca3d_ensemble_census", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ComponentStruct), _u32p, _u32p, C.POINTER(C.c_float)]),
     ("ca3d_ensemble_isolate", C.c_int, [_H, C.c_uint32, _H, C.c_uint32, C.POINTER(IsolateJobStruct), C.c_uint32, C.POINTER(IsolatedStruct),
                                         C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_census_connected", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ComponentStruct), _u32p, _u32p,
+                                                 C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_isolate_connected", C.c_int, [_H, C.c_uint32, _H, C.c_uint32, C.POINTER(IsolateJobStruct), C.c_uint32, C.c_uint32,
+                                                  C.POINTER(IsolatedStruct), C.POINTER(C.c_float)]),
     ("ca3d_ensemble_compose", C.c_int, [_H, C.c_uint32, C.c_uint32, _H, C.POINTER(ComposePartStruct), _u32p, C.c_uint32,
                                         C.POINTER(ComposedStruct), C.POINTER(C.c_float)]),
     ("ca3d_ensemble_canon", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(CanonStruct), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),

@@ -944,8 +944,16 @@ CA3D_API_CATCH
 int ca3d_ensemble_census(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t max_components, ca3d_component *out, uint32_t *n_components,
                          uint32_t *remaining, float *gpu_ms) CA3D_API_TRY
 {
+	return ca3d_ensemble_census_connected(e, first, count, max_components, CA3D_CONNECT_CLOSED, out, n_components, remaining, gpu_ms);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_census_connected(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t max_components, uint32_t connectivity,
+                                   ca3d_component *out, uint32_t *n_components, uint32_t *remaining, float *gpu_ms) CA3D_API_TRY
+{
 	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
 	if (!out || !n_components || !remaining) return fail(CA3D_ERR_INVALID_ARGUMENT, "out, n_components or remaining is NULL");
+	if (connectivity > CA3D_CONNECT_TORUS) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown connectivity %u (CA3D_CONNECT_CLOSED = 0, CA3D_CONNECT_TORUS = 1)", connectivity);
 	int rc = check_range(e, first, count);
 	if (rc) return rc;
 	if (max_components == 0 || max_components > kCensusMaxComponents)
@@ -958,6 +966,7 @@ int ca3d_ensemble_census(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uin
 	l.state = e->state;
 	l.first = first; l.count = count;
 	l.max_components = max_components;
+	l.connectivity = connectivity;
 	l.out = reinterpret_cast<ca3d_component *>(e->census);
 	l.n_components = reinterpret_cast<uint32_t *>(e->census + rec_bytes);
 	l.remaining = l.n_components + count;
@@ -976,8 +985,16 @@ CA3D_API_CATCH
 int ca3d_ensemble_isolate(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensemble_t *src, uint32_t n_jobs, const ca3d_isolate_job *jobs, uint32_t flags,
                           ca3d_isolated *out, float *gpu_ms) CA3D_API_TRY
 {
+	return ca3d_ensemble_isolate_connected(dst, dst_first, src, n_jobs, jobs, flags, CA3D_CONNECT_CLOSED, out, gpu_ms);
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_isolate_connected(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensemble_t *src, uint32_t n_jobs, const ca3d_isolate_job *jobs,
+                                    uint32_t flags, uint32_t connectivity, ca3d_isolated *out, float *gpu_ms) CA3D_API_TRY
+{
 	if (!dst || !src) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
 	if (!jobs) return fail(CA3D_ERR_INVALID_ARGUMENT, "jobs is NULL");
+	if (connectivity > CA3D_CONNECT_TORUS) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown connectivity %u (CA3D_CONNECT_CLOSED = 0, CA3D_CONNECT_TORUS = 1)", connectivity);
 	if (!dst->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called for the destination ensemble");
 	if (!src->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called for the source ensemble");
 	if (n_jobs == 0 || dst_first >= dst->n || n_jobs > dst->n - dst_first)
@@ -1013,6 +1030,7 @@ int ca3d_ensemble_isolate(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensembl
 	l.dst_first = dst_first; l.n_jobs = n_jobs;
 	l.placement = placement;
 	l.rule_words = copy_rules ? rule_words(dst) : 0u;
+	l.connectivity = connectivity;
 	if (src != dst)
 	{
 		// behind what is queued on the source's stream now

@@ -242,8 +242,10 @@ struct CensusLaunch
 	uint32_t max_components; // 1 .. kCensusMaxComponents
 	ca3d_component *out;     // device, [count][max_components]: every slot is written
 	uint32_t *n_components, *remaining; // device, [count]
+	uint32_t connectivity;   // CA3D_CONNECT_CLOSED: ca_ensemble_census64; CA3D_CONNECT_TORUS: ca_ensemble_census64_torus (ca_objects_torus.hip)
 };
-hipError_t launch_census(const CensusLaunch &l, hipStream_t stream);
+hipError_t launch_census(const CensusLaunch &l, hipStream_t stream);       // picks the kernel by l.connectivity
+hipError_t launch_census_torus(const CensusLaunch &l, hipStream_t stream); // ca_objects_torus.hip
 // ca_isolate.hip: job k makes the connected component of source universe jobs[k].universe that holds jobs[k].cell the only thing in
 // destination universe dst_first + k (ca3d_ensemble_isolate), translated as `placement` says, in both buffers; one workgroup of
 // ca_ensemble_isolate64 a job. The caller has checked every universe, cell and range, and that no source universe is a destination.
@@ -258,8 +260,10 @@ struct IsolateLaunch
 	uint32_t dst_first, n_jobs;
 	uint32_t placement;             // CA3D_ISOLATE_KEEP / CENTRE / ORIGIN
 	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
+	uint32_t connectivity;          // CA3D_CONNECT_CLOSED: ca_ensemble_isolate64; CA3D_CONNECT_TORUS: ca_ensemble_isolate64_torus (ca_objects_torus.hip)
 };
-hipError_t launch_isolate(const IsolateLaunch &l, hipStream_t stream);
+hipError_t launch_isolate(const IsolateLaunch &l, hipStream_t stream);       // picks the kernel by l.connectivity
+hipError_t launch_isolate_torus(const IsolateLaunch &l, hipStream_t stream); // ca_objects_torus.hip
 // ca_compose.hip: destination universe dst_first + k becomes the union of parts part_begin[k] .. part_begin[k + 1] - 1, each the whole
 // state of a source universe turned and shifted (ca3d_ensemble_compose), in both buffers; one workgroup of ca_ensemble_compose64 a
 // destination. The caller has checked every universe, orientation, `at` and range, and that no source universe is a destination.

@@ -6,7 +6,7 @@
 // component being filled.
 //
 // The row loads, the seed and the flood loop are WRITTEN OUT below, not called: they are ca_flood.inc's load_universe, seed_cell and
-// flood, line for line, and a change to one is a change to the other. Called, they compute the same with the same instructions, but the
+// flood (its closed form, Torus = false), line for line, and a change to one is a change to the other. Called, they compute the same with the same instructions, but the
 // compiler allocates this kernel's registers differently and the census measured 1.3 to 4.5 % slower on an MI355X.
 //
 // One round of the loop: SEED (the lowest live cell of R in the order z, y, x: thread -> wave -> LDS -> workgroup), FLOOD, RECORD
@@ -207,6 +207,8 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_census64(CensusArgs a
 
 hipError_t launch_census(const CensusLaunch &l, hipStream_t stream)
 {
+	if (l.connectivity == CA3D_CONNECT_TORUS) return launch_census_torus(l, stream);
+	if (l.connectivity != CA3D_CONNECT_CLOSED) return hipErrorInvalidValue;
 	if (l.count == 0 || l.max_components == 0 || l.max_components > kCensusMaxComponents) return hipErrorInvalidValue;
 	static_assert(sizeof(ca3d_component) == 32, "ca3d_component is two 16-byte stores");
 	CensusArgs a;

@@ -8,6 +8,9 @@
 // step's neighbour access with ORs in place of the count: v_alignbit along x, wave-wide DPP along y, the double-buffered LDS exchange
 // (laid out like VnStep's) along z. ALL SIX FACES ARE CLOSED — not the step's boundary: word 1's right neighbour, row 63's y + 1 and
 // plane 63's z + 1 shift in zero where the step wraps.
+// flood<true> is the same fill on the torus Z_64^3 (ca_objects_torus.hip; DESIGN.md 12.13): it differs in three operands — word 0's x - 1
+// and word 1's x + 1 take the row's other word, the y shifts are wave rotations, and wave 0 / 15 read the planes of wave 15 / 0 — and in
+// nothing else; extent serves both, and torus_span reads a cyclic box from its masks.
 //
 // What every kernel built on this may rely on, and must keep:
 //  - all 1024 threads reach every __syncthreads(): flood and extent hold barriers, so a kernel must call them from all 1024 threads,
@@ -57,6 +60,8 @@ __device__ __forceinline__ void seed_cell(u32 (&F)[kPT][2], u32 cell, u32 wave, 
 // k carries the waves' "changed in iteration k - 1" bits in the exchange buffer of its parity, so the barrier of the exchange is the
 // barrier of the test: ONE barrier an iteration. xch and flg are dead on return: the iteration that ends the flood reads none of xch,
 // and every wave has passed that iteration's barrier only after all had finished the reads of the one before.
+// Torus: every face joins the opposite one (see the head of this file); the closed form is flood(...), the default.
+template <bool Torus = false>
 __device__ __forceinline__ void flood(const u32 (&R)[kPT][2], u32 (&F)[kPT][2], u32 *xch, u32 *flg, u32 wave, u32 row)
 {
 	u32 changed = 1u; // wave-uniform
@@ -70,11 +75,11 @@ __device__ __forceinline__ void flood(const u32 (&R)[kPT][2], u32 (&F)[kPT][2], 
 			for (u32 h = 0; h < 2u; h++)
 			{
 				const u32 w = F[p][h], other = F[p][h ^ 1u];
-				const u32 l = from_left(w, h ? other : 0u);  // cell x - 1: word 0's comes from nowhere, word 1's from word 0
-				const u32 r = from_right(h ? 0u : other, w); // cell x + 1: word 0's from word 1, word 1's from nowhere (closed: no wrap)
+				const u32 l = from_left(w, Torus || h ? other : 0u);  // cell x - 1: word 0's comes from nowhere, word 1's from word 0
+				const u32 r = from_right(Torus || !h ? other : 0u, w); // cell x + 1: word 0's from word 1, word 1's from nowhere (closed: no wrap)
 				const u32 x = w | l | r;
-				// row y - 1 (zero into row 0), row y + 1 (zero into row 63: wave_shl, not the step's wave_rol)
-				Y[p][h] = x | dpp_mov<kDppWaveShr1>(x) | dpp_mov<kDppWaveShl1>(x);
+				// row y - 1 (zero into row 0), row y + 1 (zero into row 63: wave_shl, not the step's wave_rol); the torus rotates
+				Y[p][h] = x | dpp_mov<Torus ? kDppWaveRor1 : kDppWaveShr1>(x) | dpp_mov<Torus ? kDppWaveRol1 : kDppWaveShl1>(x);
 			}
 		xch[slot(buf, wave, 0u, 0u, row)] = Y[0][0];
 		xch[slot(buf, wave, 0u, 1u, row)] = Y[0][1];
@@ -93,8 +98,8 @@ __device__ __forceinline__ void flood(const u32 (&R)[kPT][2], u32 (&F)[kPT][2], 
 #pragma unroll
 		for (u32 h = 0; h < 2u; h++)
 		{
-			below[h] = wave ? xch[slot(buf, wave - 1u, 1u, h, row)] : 0u;                                    // z == -1: closed
-			above[h] = wave + 1u < kWaves ? xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)] : 0u; // z == 64: closed (the step wraps here)
+			below[h] = Torus || wave ? xch[slot(buf, Torus ? (wave - 1u) & (kWaves - 1u) : wave - 1u, 1u, h, row)] : 0u; // z == -1: closed
+			above[h] = Torus || wave + 1u < kWaves ? xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)] : 0u; // z == 64: closed (the step wraps here)
 		}
 		u32 ch = 0;
 #pragma unroll
@@ -154,4 +159,20 @@ __device__ __forceinline__ Extent extent(const u32 (&F)[kPT][2], u32 *part, u32 
 	e.ym = (u64)lane0(row16_or(pb.x)) << 32 | lane0(row16_or(pa.w));
 	e.zm = (u64)lane0(row16_or(pb.z)) << 32 | lane0(row16_or(pb.y));
 	return e;
+}
+
+// The torus box of one axis from its occupancy mask m (bit c: coordinate c holds a cell; m != 0): the shortest cyclic interval that
+// covers the set. A connected component's coordinates form ONE cyclic run, so the start is the one set bit whose predecessor is clear
+// and the length the number of set bits; a full ring starts at 0.
+struct TorusSpan
+{
+	u32 lo, e; // start 0 .. 63, length 1 .. 64: the interval is lo .. lo + e - 1 modulo 64
+};
+__device__ __forceinline__ TorusSpan torus_span(u64 m)
+{
+	const u64 pred = m << 1 | m >> 63; // rotl64(m, 1): bit c = coordinate c - 1 is occupied
+	TorusSpan s;
+	s.lo = m == ~0ull ? 0u : (u32)__builtin_ctzll(m & ~pred);
+	s.e = (u32)__popcll(m);
+	return s;
 }

@@ -110,6 +110,8 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_isolate64(IsolateArgs
 
 hipError_t launch_isolate(const IsolateLaunch &l, hipStream_t stream)
 {
+	if (l.connectivity == CA3D_CONNECT_TORUS) return launch_isolate_torus(l, stream);
+	if (l.connectivity != CA3D_CONNECT_CLOSED) return hipErrorInvalidValue;
 	if (l.n_jobs == 0 || l.placement > CA3D_ISOLATE_ORIGIN || l.rule_words > 6u) return hipErrorInvalidValue;
 	static_assert(sizeof(ca3d_isolated) == 16 && sizeof(ca3d_isolate_job) == 8, "a result is one 16-byte store");
 	IsolateArgs a;

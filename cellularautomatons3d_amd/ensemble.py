@@ -223,19 +223,33 @@ class Ensemble:
         _capi.check(self._lib.ca3d_ensemble_summarize(self._h, first, count, recs))
         return [_summary(r, None) for r in recs]
 
-    def census(self, first: int = 0, count: Optional[int] = None, max_components: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def _connectivity(self, name: str) -> int:
+        """CA3D_CONNECT_* of "closed", "torus" or "boundary" (torus when this ensemble's boundary is "torus", closed otherwise)."""
+        if name == "boundary":
+            name = "torus" if self.boundary == "torus" else "closed"
+        if name not in _capi.CONNECTIVITIES:
+            raise ValueError(f"unknown connectivity {name!r}: one of {tuple(_capi.CONNECTIVITIES) + ('boundary',)}")
+        return _capi.CONNECTIVITIES[name]
+
+    def census(self, first: int = 0, count: Optional[int] = None, max_components: int = 64,
+               connectivity: str = "closed") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """`ca3d_ensemble_census`: the connected objects (26-neighbourhood inside the closed cube) of universes first .. first + count - 1
         (default: all from `first`), found on the device in one launch behind the queued steps
         -> (components [count, max_components] of `host.COMPONENT_DTYPE`, n_components u32[count], remaining u32[count]).
         Components come in the order of their first cells; slots past n_components[u] are zero; remaining[u] counts the live cells in no
         listed component (0: the list is complete). `host.census` is the same on the CPU, `host.unpack_box` opens box_min / box_max.
-        The call only reads; `census_gpu_ms()` tells what the launch took."""
+        The call only reads; `census_gpu_ms()` tells what the launch took.
+        `connectivity` (`ca3d_ensemble_census_connected`): "closed" as above; "torus": cells are adjacent modulo 64, an object on a
+        face is one object, box_min starts its cyclic box and box_max = box_min + extent - 1 is not reduced (>= 64 through a seam);
+        "boundary": torus when this ensemble's boundary is "torus", closed otherwise."""
+        connect = self._connectivity(connectivity)
         count = self.n - first if count is None else count
         comps = np.zeros((max(count, 0), max(max_components, 0)), dtype=host.COMPONENT_DTYPE)
         n, rest = (np.zeros(max(count, 0), dtype=np.uint32) for _ in range(2))
         ms = C.c_float(0.0)
-        _capi.check(self._lib.ca3d_ensemble_census(self._h, first, count, max_components, comps.ctypes.data_as(C.POINTER(_capi.ComponentStruct)),
-                                                   n.ctypes.data_as(_u32p), rest.ctypes.data_as(_u32p), C.byref(ms)))
+        _capi.check(self._lib.ca3d_ensemble_census_connected(self._h, first, count, max_components, connect,
+                                                             comps.ctypes.data_as(C.POINTER(_capi.ComponentStruct)),
+                                                             n.ctypes.data_as(_u32p), rest.ctypes.data_as(_u32p), C.byref(ms)))
         self._census_ms = float(ms.value)
         return comps, n, rest
 
@@ -244,15 +258,19 @@ class Ensemble:
         return getattr(self, "_census_ms", None)
 
     def isolate(self, jobs, dst_first: int = 0, src: Optional["Ensemble"] = None, placement: str = "centre",
-                copy_rules: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+                copy_rules: bool = True, connectivity: str = "closed") -> Tuple[np.ndarray, np.ndarray]:
         """`ca3d_ensemble_isolate`: universe dst_first + k of THIS ensemble becomes the connected object of universe jobs[k][0] of `src`
         (default: this ensemble) that holds the cell jobs[k][1] (x + 64 y + 4096 z, any cell of the object — a census' first_cell
         will do), alone, translated as `placement` says ("keep", "centre", "origin"), at step 0, found and written on the device in
         one launch -> (population u32[n], shift i32[n, 3]). `copy_rules`: the destination universe takes its source universe's rule
         (both ensembles of one kind). `jobs`: [n, 2]. `host.isolate` is the same on the CPU for one universe; `isolate_gpu_ms()`
-        tells what the launch took."""
+        tells what the launch took.
+        `connectivity` (`ca3d_ensemble_isolate_connected`): "closed" — the object is the closed census'; "torus" — the torus census',
+        moved modulo 64 so that it arrives in one piece; "boundary": torus when the SOURCE ensemble's boundary is "torus", closed
+        otherwise."""
         if placement not in _capi.ISOLATE_PLACEMENTS:
             raise ValueError(f"unknown placement {placement!r}: one of {tuple(_capi.ISOLATE_PLACEMENTS)}")
+        connect = (self if src is None else src)._connectivity(connectivity)
         j = np.ascontiguousarray(_as_u32(jobs))
         if j.ndim != 2 or j.shape[1] != 2:
             raise ValueError("jobs is an [n, 2] array of (universe, cell)")
@@ -260,9 +278,9 @@ class Ensemble:
         out = np.zeros((n, 4), dtype=np.int32)
         ms = C.c_float(0.0)
         flags = _capi.ISOLATE_PLACEMENTS[placement] | (_capi.ISOLATE_COPY_RULES if copy_rules else 0)
-        _capi.check(self._lib.ca3d_ensemble_isolate(self._h, dst_first, (self if src is None else src)._h, n,
-                                                    j.ctypes.data_as(C.POINTER(_capi.IsolateJobStruct)), flags,
-                                                    out.ctypes.data_as(C.POINTER(_capi.IsolatedStruct)), C.byref(ms)))
+        _capi.check(self._lib.ca3d_ensemble_isolate_connected(self._h, dst_first, (self if src is None else src)._h, n,
+                                                              j.ctypes.data_as(C.POINTER(_capi.IsolateJobStruct)), flags, connect,
+                                                              out.ctypes.data_as(C.POINTER(_capi.IsolatedStruct)), C.byref(ms)))
         self._isolate_ms = float(ms.value)
         return out[:, 0].astype(np.uint32), out[:, 1:].copy()
 

@@ -439,13 +439,71 @@ def _dilate_closed(f: np.ndarray) -> np.ndarray:
     return f
 
 
-def census(words, max_components: int = 64) -> Tuple[np.ndarray, int, int]:
+#: enum CA3D_CONNECT_* (include/ca3d.h): index = value
+CONNECTIVITIES = ("closed", "torus")
+
+
+def _dilate_window(f: np.ndarray, wrap) -> np.ndarray:
+    """`_dilate_closed`, except that an axis with wrap[axis] set is a ring: its two ends are neighbours."""
+    for axis in range(3):
+        if wrap[axis]:
+            f = f | np.roll(f, 1, axis=axis) | np.roll(f, -1, axis=axis)
+            continue
+        g = f.copy()
+        lo = [slice(None)] * 3
+        hi = [slice(None)] * 3
+        lo[axis], hi[axis] = slice(0, -1), slice(1, None)
+        g[tuple(hi)] |= f[tuple(lo)]
+        g[tuple(lo)] |= f[tuple(hi)]
+        f = g
+    return f
+
+
+def _torus_component(live: np.ndarray, z: int, y: int, x: int) -> np.ndarray:
+    """The component of the live cell (z, y, x) of the boolean cube `live` [z, y, x] under the 26-neighbourhood of Z_64^3 -> boolean
+    cube. The cube is rolled so that the seed sits at the centre; the fill then works in the closed fill's growing window, which
+    before every dilation holds the filled cells with a margin of one, and an axis becomes a ring once the window spans it."""
+    G = 64
+    c = G // 2
+    rolled = np.roll(live, (c - z, c - y, c - x), axis=(0, 1, 2))
+    f = np.zeros((G, G, G), dtype=bool)
+    f[c, c, c] = True
+    lo, hi = [c, c, c], [c + 1, c + 1, c + 1]
+    size = 1
+    while True:
+        lo = [max(v - 1, 0) for v in lo]
+        hi = [min(v + 1, G) for v in hi]
+        win = tuple(slice(a, b) for a, b in zip(lo, hi))
+        f[win] = _dilate_window(f[win], [a == 0 and b == G for a, b in zip(lo, hi)]) & rolled[win]
+        grown = int(np.count_nonzero(f[win]))
+        if grown == size:
+            break
+        size = grown
+    return np.roll(f, (z - c, y - c, x - c), axis=(0, 1, 2))
+
+
+def torus_span(coords) -> Tuple[int, int]:
+    """(start, extent) of the shortest cyclic interval {start, ..., start + extent - 1 mod 64} that covers the coordinates `coords`
+    (a non-empty subset of Z_64) and starts at one of them; ties go to the smallest start. All 64 give (0, 64)."""
+    S = np.unique(np.asarray(coords, dtype=np.int64) % 64)
+    extents = [int(((S - s) % 64).max()) + 1 for s in S]  # S is sorted: the first minimum is the smallest start
+    k = int(np.argmin(extents))
+    return int(S[k]), extents[k]
+
+
+def census(words, max_components: int = 64, connectivity: str = "closed") -> Tuple[np.ndarray, int, int]:
     """`ca3d_ensemble_census` for ONE packed 64^3 universe, in plain numpy: the connected components of its live cells under the
     26-neighbourhood inside the closed cube (no face wraps), ordered by their first cells (smallest x + 64 y + 4096 z)
     -> (components [max_components] of COMPONENT_DTYPE, n_components, remaining). The first min(C, max_components) components are
     listed, the slots behind them are zero, `remaining` is the number of live cells in no listed component. A component's digest is
-    `state_summary(64, translated)["digest"]` of the state that holds only it, translated by -box_min."""
+    `state_summary(64, translated)["digest"]` of the state that holds only it, translated by -box_min.
+
+    `connectivity="torus"` is `ca3d_ensemble_census_connected` with CA3D_CONNECT_TORUS: cells are adjacent when they differ by at most
+    1 modulo 64 on every axis; per axis box_min is the start of the shortest cyclic interval that covers the component's coordinates
+    (`torus_span`), box_max = box_min + extent - 1 is NOT reduced (>= 64 through a seam), and the translation by -box_min is cyclic."""
     G = 64
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"unknown connectivity {connectivity!r}: one of {CONNECTIVITIES}")
     if not 1 <= int(max_components) <= 1024:
         raise ValueError("max_components is 1 .. 1024")
     w = np.ascontiguousarray(words, dtype="<u4").ravel()
@@ -460,6 +518,21 @@ def census(words, max_components: int = 64) -> Tuple[np.ndarray, int, int]:
             break
         first = int(live[0])
         z, y, x = first >> 12, (first >> 6) & 63, first & 63
+        if connectivity == "torus":
+            f = _torus_component(rest, z, y, x)
+            zs, ys, xs = np.nonzero(f)
+            (bx, ex), (by, ey), (bz, ez) = torus_span(xs), torus_span(ys), torus_span(zs)
+            moved = np.zeros((G, G, G), dtype=np.uint8)
+            moved[(zs - bz) % G, (ys - by) % G, (xs - bx) % G] = 1
+            rec = out[n]
+            rec["population"] = zs.size
+            rec["first_cell"] = first
+            rec["box_min"] = bx | by << 8 | bz << 16
+            rec["box_max"] = (bx + ex - 1) | (by + ey - 1) << 8 | (bz + ez - 1) << 16
+            rec["digest"] = state_summary(G, np.packbits(moved.ravel(), bitorder="little").view("<u4"))["digest"]
+            rest &= ~f
+            n += 1
+            continue
         z0, z1, y0, y1, x0, x1 = z, z + 1, y, y + 1, x, x + 1  # the fill works in a window that grows with the component
         f = np.zeros((G, G, G), dtype=bool)
         f[z, y, x] = True
@@ -566,14 +639,20 @@ def ensemble_step(words, kind: str, tables, boundary: str = "reference") -> np.n
 ISOLATE_PLACEMENTS = ("keep", "centre", "origin")
 
 
-def isolate(words, cell: int, placement: str = "centre") -> Tuple[np.ndarray, int, Tuple[int, int, int]]:
+def isolate(words, cell: int, placement: str = "centre", connectivity: str = "closed") -> Tuple[np.ndarray, int, Tuple[int, int, int]]:
     """`ca3d_ensemble_isolate` for ONE packed 64^3 universe, in plain numpy: the connected component (26-neighbourhood inside the
     closed cube, no face wraps: the census') that holds `cell` = x + 64 y + 4096 z, alone, translated by the shift of `placement` —
     "keep": 0; "origin": -box_min; "centre": (64 - extent) // 2 - box_min per axis -> (words u32[8192], population, (dx, dy, dz)).
-    Any cell of the component selects it; a dead cell gives zeros, population 0 and a zero shift."""
+    Any cell of the component selects it; a dead cell gives zeros, population 0 and a zero shift.
+
+    `connectivity="torus"` is `ca3d_ensemble_isolate_connected` with CA3D_CONNECT_TORUS: the component is the torus census', box_min
+    and extent are its cyclic box's (`torus_span`), the shift is the same formula and is applied modulo 64, so the object arrives in
+    one piece; the shift returned is the formula's value."""
     G = 64
     if placement not in ISOLATE_PLACEMENTS:
         raise ValueError(f"unknown placement {placement!r}: one of {ISOLATE_PLACEMENTS}")
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"unknown connectivity {connectivity!r}: one of {CONNECTIVITIES}")
     cell = int(cell)
     if not 0 <= cell < G * G * G:
         raise ValueError("a cell is x + 64 y + 4096 z, below 2^18")
@@ -584,6 +663,16 @@ def isolate(words, cell: int, placement: str = "centre") -> Tuple[np.ndarray, in
     z, y, x = cell >> 12, (cell >> 6) & 63, cell & 63
     if not live[z, y, x]:
         return np.zeros(words_per_buffer(G), dtype=np.uint32), 0, (0, 0, 0)
+    if connectivity == "torus":
+        zs, ys, xs = np.nonzero(_torus_component(live, z, y, x))
+        shift = []
+        for v in (xs, ys, zs):
+            lo, extent = torus_span(v)
+            shift.append(0 if placement == "keep" else -lo if placement == "origin" else (G - extent) // 2 - lo)
+        dx, dy, dz = shift
+        moved = np.zeros((G, G, G), dtype=np.uint8)
+        moved[(zs + dz) % G, (ys + dy) % G, (xs + dx) % G] = 1
+        return np.packbits(moved.ravel(), bitorder="little").view("<u4").astype(np.uint32), int(zs.size), (dx, dy, dz)
     z0, z1, y0, y1, x0, x1 = z, z + 1, y, y + 1, x, x + 1  # the fill works in a window that grows with the component (census)
     f = np.zeros((G, G, G), dtype=bool)
     f[z, y, x] = True

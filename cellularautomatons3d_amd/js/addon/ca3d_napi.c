@@ -1314,20 +1314,43 @@ static napi_value js_ensemble_summaries(napi_env env, napi_callback_info info)
 	return out;
 }
 
+/* An optional trailing connectivity (CA3D_CONNECT_*): argv[at] when the call has it and it is not undefined, CA3D_CONNECT_CLOSED otherwise.
+ * argv holds at + 1 values, the absent ones undefined (napi_get_cb_info). */
+static int get_connectivity(napi_env env, napi_value *argv, size_t at, uint32_t *out)
+{
+	napi_valuetype t = napi_undefined;
+	*out = CA3D_CONNECT_CLOSED;
+	if (napi_typeof(env, argv[at], &t) != napi_ok) return 0;
+	return t == napi_undefined ? 1 : get_u32(env, argv[at], out);
+}
+
+/* the first `want` of want + 1 arguments are required: argv holds want + 1 values, the last undefined when the call left it out */
+static int get_args_and_one(napi_env env, napi_callback_info info, size_t want, napi_value *argv)
+{
+	size_t argc = want + 1u;
+	if (napi_get_cb_info(env, info, &argc, argv, NULL, NULL) != napi_ok || argc < want)
+	{
+		napi_throw_type_error(env, NULL, "wrong number of arguments");
+		return 0;
+	}
+	return 1;
+}
+
 /* ensembleCensus(handle, first, count, maxComponents, Uint32Array(count * maxComponents * 8) records, Uint32Array(count) nComponents,
- *                Uint32Array(count) remaining) -> gpuMs: the connected objects of universes [first, first + count) (ca3d_ensemble_census);
+ *                Uint32Array(count) remaining[, connectivity]) -> gpuMs: the connected objects of universes [first, first + count)
+ * (ca3d_ensemble_census_connected; without a connectivity CA3D_CONNECT_CLOSED, ca3d_ensemble_census);
  * a record is ca3d_component's eight words: population, firstCell, boxMin, boxMax, digest low, digest high, 0, 0 (js/ca3d.js opens them) */
 static napi_value js_ensemble_census(napi_env env, napi_callback_info info)
 {
-	napi_value argv[7];
-	if (!get_args(env, info, 7, argv)) return NULL;
+	napi_value argv[8];
+	if (!get_args_and_one(env, info, 7, argv)) return NULL;
 	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
-	uint32_t first, count, max_components;
+	uint32_t first, count, max_components, connectivity;
 	void *recs, *n, *rest;
 	size_t nrecs, nn, nrest;
 	if (!e || !get_u32(env, argv[1], &first) || !get_u32(env, argv[2], &count) || !get_u32(env, argv[3], &max_components) ||
 	    !get_typed(env, argv[4], napi_uint32_array, 0, &recs, &nrecs) || !get_typed(env, argv[5], napi_uint32_array, 0, &n, &nn) ||
-	    !get_typed(env, argv[6], napi_uint32_array, 0, &rest, &nrest))
+	    !get_typed(env, argv[6], napi_uint32_array, 0, &rest, &nrest) || !get_connectivity(env, argv, 7, &connectivity))
 		return NULL;
 	/* sizes the library refuses anyway leave nothing to check the arrays against: it names the reason */
 	const int sizable = count && max_components && max_components <= 1024u;
@@ -1338,28 +1361,30 @@ static napi_value js_ensemble_census(napi_env env, napi_callback_info info)
 	}
 	_Static_assert(sizeof(ca3d_component) == 32, "a record crosses as eight words");
 	float ms = 0.f;
-	int rc = ca3d_ensemble_census(e, first, count, max_components, (ca3d_component *)recs, (uint32_t *)n, (uint32_t *)rest, &ms);
+	int rc = ca3d_ensemble_census_connected(e, first, count, max_components, connectivity, (ca3d_component *)recs, (uint32_t *)n, (uint32_t *)rest, &ms);
 	if (rc) return throw_ca3d(env, rc);
 	napi_value v;
 	napi_create_double(env, (double)ms, &v);
 	return v;
 }
 
-/* ensembleIsolate(dstHandle, dstFirst, srcHandle, Uint32Array(2 * nJobs) jobs (universe, cell pairs), flags, Int32Array(4 * nJobs) out)
+/* ensembleIsolate(dstHandle, dstFirst, srcHandle, Uint32Array(2 * nJobs) jobs (universe, cell pairs), flags, Int32Array(4 * nJobs) out
+ *                 [, connectivity])
  * -> gpuMs: job k makes the object of src's universe jobs[2 k] that holds the cell jobs[2 k + 1] the only thing in dst's universe
- * dstFirst + k (ca3d_ensemble_isolate); out[4 k ..] is ca3d_isolated's four words: population, dx, dy, dz */
+ * dstFirst + k (ca3d_ensemble_isolate_connected; without a connectivity CA3D_CONNECT_CLOSED, ca3d_ensemble_isolate); out[4 k ..] is
+ * ca3d_isolated's four words: population, dx, dy, dz */
 static napi_value js_ensemble_isolate(napi_env env, napi_callback_info info)
 {
-	napi_value argv[6];
-	if (!get_args(env, info, 6, argv)) return NULL;
+	napi_value argv[7];
+	if (!get_args_and_one(env, info, 6, argv)) return NULL;
 	ca3d_ensemble_t *dst = get_ensemble(env, argv[0]);
 	if (!dst) return NULL;
 	ca3d_ensemble_t *src = get_ensemble(env, argv[2]);
-	uint32_t dst_first, flags;
+	uint32_t dst_first, flags, connectivity;
 	void *jobs, *out;
 	size_t njobs, nout;
 	if (!src || !get_u32(env, argv[1], &dst_first) || !get_typed(env, argv[3], napi_uint32_array, 0, &jobs, &njobs) || !get_u32(env, argv[4], &flags) ||
-	    !get_typed(env, argv[5], napi_int32_array, 0, &out, &nout))
+	    !get_typed(env, argv[5], napi_int32_array, 0, &out, &nout) || !get_connectivity(env, argv, 6, &connectivity))
 		return NULL;
 	if (njobs % 2u || nout != 2u * njobs || njobs / 2u > 0xFFFFFFFFu)
 	{
@@ -1369,7 +1394,8 @@ static napi_value js_ensemble_isolate(napi_env env, napi_callback_info info)
 	_Static_assert(sizeof(ca3d_isolate_job) == 8 && sizeof(ca3d_isolated) == 16, "a job crosses as two words, a result as four");
 	float ms = 0.f;
 	/* (no job: the library refuses the call and names the reason; it reads neither array) */
-	int rc = ca3d_ensemble_isolate(dst, dst_first, src, (uint32_t)(njobs / 2u), (const ca3d_isolate_job *)jobs, flags, (ca3d_isolated *)out, &ms);
+	int rc = ca3d_ensemble_isolate_connected(dst, dst_first, src, (uint32_t)(njobs / 2u), (const ca3d_isolate_job *)jobs, flags, connectivity,
+	                                         (ca3d_isolated *)out, &ms);
 	if (rc) return throw_ca3d(env, rc);
 	napi_value v;
 	napi_create_double(env, (double)ms, &v);

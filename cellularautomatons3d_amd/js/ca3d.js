@@ -427,6 +427,16 @@ class EngineGroup
 const ENSEMBLE_ALL = 0xFFFFFFFF, ENSEMBLE_WORDS = 8192;
 const ENSEMBLE_NEIGHBOURHOODS = ["von neumann", "moore"]; // index = enum ca3d_ensemble_neighbourhood
 const ENSEMBLE_BOUNDARIES = ["reference", "torus", "closed"]; // index = enum ca3d_ensemble_boundary
+const CONNECTIVITIES = ["closed", "torus"]; // index = CA3D_CONNECT_CLOSED / TORUS (Ensemble.census, Ensemble.isolate)
+// "closed", "torus", or "boundary": torus when `ensemble`'s boundary is "torus", closed otherwise -> CA3D_CONNECT_*
+function connectivityOf(ensemble, name)
+{
+	if (name === undefined || name === null) return 0;
+	if (name === "boundary") name = ensemble.boundary === "torus" ? "torus" : "closed";
+	const c = CONNECTIVITIES.indexOf(name);
+	if (c < 0) throw new Error(`unknown connectivity ${JSON.stringify(name)}: one of ${CONNECTIVITIES.join(", ")}, boundary`);
+	return c;
+}
 class Ensemble
 {
 	constructor(device)
@@ -558,9 +568,13 @@ class Ensemble
 	 *  -> {components, nComponents: Uint32Array(count), remaining: Uint32Array(count), gpuMs}. components[k] lists universe first + k's
 	 *  first min(C, maxComponents) objects in the order of their first cells, each {population, firstCell (x + 64 y + 4096 z), boxMin
 	 *  [x, y, z], boxMax, digest (BigInt: the state digest of the object translated to the origin)}; remaining[k]: live cells in no
-	 *  listed object, 0 when the list is complete. maxComponents: 1 .. 1024, default 64. The call only reads. */
-	census(first, count, maxComponents)
+	 *  listed object, 0 when the list is complete. maxComponents: 1 .. 1024, default 64. The call only reads.
+	 *  opts.connectivity (ca3d_ensemble_census_connected): "closed" (the default), "torus" — cells are adjacent modulo 64, an object on a
+	 *  face is one object, boxMin starts its cyclic box and boxMax = boxMin + extent - 1 is not reduced (>= 64 through a seam) — or
+	 *  "boundary": torus when this ensemble's boundary is "torus", closed otherwise. */
+	census(first, count, maxComponents, opts)
 	{
+		const connectivity = connectivityOf(this, (opts || {}).connectivity);
 		first = first || 0;
 		count = count === undefined ? this.n - first : count;
 		maxComponents = maxComponents === undefined ? 64 : maxComponents;
@@ -568,7 +582,7 @@ class Ensemble
 		const sizable = count > 0 && maxComponents >= 1 && maxComponents <= 1024;
 		const words = new Uint32Array(sizable ? count * maxComponents * 8 : 0);
 		const nComponents = new Uint32Array(sizable ? count : 0), remaining = new Uint32Array(sizable ? count : 0);
-		const gpuMs = this._a.ensembleCensus(this._e, first, count, maxComponents, words, nComponents, remaining);
+		const gpuMs = this._a.ensembleCensus(this._e, first, count, maxComponents, words, nComponents, remaining, connectivity);
 		const box = (w) => [w & 0xFF, (w >>> 8) & 0xFF, (w >>> 16) & 0xFF];
 		const components = [];
 		for (let k = 0; k < count; k++)
@@ -588,17 +602,20 @@ class Ensemble
 	 *  will do), alone, translated as opts.placement says ("keep", "centre" — the default —, "origin"), at step 0, found and written on
 	 *  the device in one launch -> {population: Uint32Array(n), shift: Int32Array(3 n) (dx, dy, dz a job), gpuMs}. opts.copyRules
 	 *  (default true): the destination universe takes its source universe's rule (both ensembles of one kind). opts.dstFirst: 0.
-	 *  jobs: an array of [universe, cell] pairs, or a Uint32Array of such pairs. */
+	 *  jobs: an array of [universe, cell] pairs, or a Uint32Array of such pairs. opts.connectivity (ca3d_ensemble_isolate_connected):
+	 *  "closed" (the default), "torus" — the object is the torus census', moved modulo 64 so that it arrives in one piece — or
+	 *  "boundary": torus when the source ensemble's boundary is "torus", closed otherwise. */
 	isolate(jobs, opts)
 	{
-		const o = Object.assign({ dstFirst: 0, src: null, placement: "centre", copyRules: true }, opts || {});
+		const o = Object.assign({ dstFirst: 0, src: null, placement: "centre", copyRules: true, connectivity: "closed" }, opts || {});
+		const connectivity = connectivityOf(o.src || this, o.connectivity);
 		const placement = ISOLATE_PLACEMENTS.indexOf(o.placement);
 		if (placement < 0) throw new Error(`unknown placement ${JSON.stringify(o.placement)}: "keep", "centre" or "origin"`);
 		const flat = jobs instanceof Uint32Array ? jobs : Uint32Array.from(jobs.flat());
 		if (flat.length % 2) throw new RangeError("jobs: [universe, cell] pairs");
 		const n = flat.length / 2;
 		const out = new Int32Array(4 * n);
-		const gpuMs = this._a.ensembleIsolate(this._e, o.dstFirst, (o.src || this)._e, flat, placement | (o.copyRules ? ISOLATE_COPY_RULES : 0), out);
+		const gpuMs = this._a.ensembleIsolate(this._e, o.dstFirst, (o.src || this)._e, flat, placement | (o.copyRules ? ISOLATE_COPY_RULES : 0), out, connectivity);
 		const population = new Uint32Array(n), shift = new Int32Array(3 * n);
 		for (let k = 0; k < n; k++)
 		{
@@ -715,7 +732,7 @@ class Ensemble
 }
 
 module.exports = {
-	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, ENSEMBLE_BOUNDARIES, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, STOP_MOVING, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
+	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, ENSEMBLE_BOUNDARIES, CONNECTIVITIES, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, STOP_MOVING, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
 	initialState, dispatchShape, traceSamples, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
 };

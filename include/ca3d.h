@@ -429,8 +429,10 @@ int ca3d_ensemble_set_rule_tables_clustered(ca3d_ensemble_t *e, uint32_t first, 
  * MOVING keeps its definition too — anchor and state both clear of every face, d = box_min(C) - box_min(A) != 0, C equal to A translated
  * by d: in a torus a ship that crossed a seam between anchor and check point is therefore reported with a shift CONGRUENT to its true
  * displacement modulo 64 per axis (a ship that left through x = 63 and went 8 cells reports dx = -56).
- * Census, isolate, compose, canon, the sheet, seeding, upload and read never step and are allowed in every mode (the census keeps its
- * closed cube: no face joins objects); CA3D_ISOLATE_COPY_RULES and CA3D_COMPOSE_COPY_RULES ignore the boundary of either ensemble.
+ * Census, isolate, compose, canon, the sheet, seeding, upload and read never step and are allowed in every mode (ca3d_ensemble_census
+ * and ca3d_ensemble_isolate keep their closed cube in every mode, as do the *_connected calls with CA3D_CONNECT_CLOSED: no face joins
+ * objects; CA3D_CONNECT_TORUS is asked for by the caller, never implied by the mode); CA3D_ISOLATE_COPY_RULES and
+ * CA3D_COMPOSE_COPY_RULES ignore the boundary of either ensemble.
  * ca3d_ensemble_canon_period steps inside its own kernel with the reference boundary: on an ensemble whose mode is not
  * CA3D_ENSEMBLE_BOUNDARY_REFERENCE it returns CA3D_ERR_UNSUPPORTED and touches nothing. */
 enum ca3d_ensemble_boundary
@@ -607,6 +609,45 @@ enum
 #define CA3D_ISOLATE_COPY_RULES 0x100u
 int ca3d_ensemble_isolate(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensemble_t *src, uint32_t n_jobs, const ca3d_isolate_job *jobs, uint32_t flags,
                           ca3d_isolated *out /* [n_jobs], may be NULL */, float *gpu_ms /* may be NULL */);
+/*
+ * Census and isolate with the connectivity named (no reference counterpart): on a torus ensemble (CA3D_ENSEMBLE_BOUNDARY_TORUS) an
+ * object that lies on a face is one object, not two fragments. `connectivity` is a parameter of these two calls, not a flag and not
+ * implied by the ensemble's boundary mode. An unknown value: CA3D_ERR_INVALID_ARGUMENT, nothing is touched, the message names the value.
+ *
+ * CA3D_CONNECT_CLOSED: the two calls ARE ca3d_ensemble_census and ca3d_ensemble_isolate — the same kernels, the same bytes out; those
+ *   two entry points are calls of these with CA3D_CONNECT_CLOSED.
+ * CA3D_CONNECT_TORUS (kernels ca_ensemble_census64_torus / ca_ensemble_isolate64_torus, csrc/ca_objects_torus.hip; host.census and
+ *   host.isolate with connectivity="torus" restate them):
+ *   Adjacency: two live cells are adjacent when they differ by at most 1 MODULO 64 on every axis, the 26-neighbourhood of Z_64^3.
+ *     Components, first_cell (the smallest x + 64 y + 4096 z of the component), the order of the list, n_components, remaining and the
+ *     zeroed slots are defined as for ca3d_ensemble_census.
+ *   The box, per axis, with S the set of coordinates (a subset of Z_64) the component occupies: box_min is the start s in S of the
+ *     shortest cyclic interval {s, ..., s + e - 1 mod 64} that covers S, ties going to the smallest s; box_max = box_min + e - 1, NOT
+ *     reduced: it is >= 64 on an axis exactly when the box runs through that axis' seam, the cell is at box_max & 63, and the 8-bit
+ *     fields hold up to 126. S = all 64 gives box_min = 0, box_max = 63. (A connected component's S is a single cyclic run, adjacent
+ *     cells differing by at most 1 on the axis: the start is the one coordinate of S whose predecessor is not in S, and e = |S|.)
+ *   The digest is the ca3d_summary digest of the 64^3 state that holds only the component, translated CYCLICALLY by -box_min: equal
+ *     shapes have equal digests wherever they lie, across seams too, and a shape clear of the faces has the digest the closed census
+ *     gives it. This fails only for a component that spans a whole ring (e = 64 on an axis): along that axis nothing is translated,
+ *     so two such components that differ by a translation along the ring have different digests.
+ *   Isolate takes the torus component that holds the job's cell. The shift is ca3d_ensemble_isolate's formula on the torus box —
+ *     KEEP 0, ORIGIN -min, CENTRE (64 - e) / 2 - min, within -63 .. 31 as there — applied MODULO 64: the destination holds the object
+ *     in one piece, unwrapped unless it spans a ring, and nothing is clipped. out[k].shift is the formula's value. A dead cell gives
+ *     an empty universe and a zero shift. With ORIGIN the state's ca3d_summary digest is the torus census record's digest.
+ * Everything else — both buffers written, records rebuilt at step 0, CA3D_ISOLATE_COPY_RULES, unknown flag bits refused, ordering across
+ * streams, staging, gpu_ms, every other refusal — is ca3d_ensemble_census' and ca3d_ensemble_isolate's.
+ */
+enum
+{
+	CA3D_CONNECT_CLOSED = 0,
+	CA3D_CONNECT_TORUS = 1
+};
+int ca3d_ensemble_census_connected(ca3d_ensemble_t *e, uint32_t first, uint32_t count, uint32_t max_components, uint32_t connectivity,
+                                   ca3d_component *out /* [count][max_components] */, uint32_t *n_components /* [count] */,
+                                   uint32_t *remaining /* [count] */, float *gpu_ms /* may be NULL */);
+int ca3d_ensemble_isolate_connected(ca3d_ensemble_t *dst, uint32_t dst_first, ca3d_ensemble_t *src, uint32_t n_jobs, const ca3d_isolate_job *jobs,
+                                    uint32_t flags, uint32_t connectivity, ca3d_isolated *out /* [n_jobs], may be NULL */,
+                                    float *gpu_ms /* may be NULL */);
 /*
  * Compose (no reference counterpart): the inverse of isolate. A destination universe becomes the union of several pieces, each the
  * WHOLE current state of a source universe — usually an isolated object — turned by one of the 48 symmetries of the cube and put where

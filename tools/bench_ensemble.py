@@ -61,6 +61,13 @@ digests included, in sampled ones. Reported: medians of --repeats measurements o
 the call, of read_state alone, and of read_state + labelling. No ratio is required. Written to profiles/ensemble_census_64.json unless
 --out says otherwise.
 
+--census-torus measures the torus forms of census and isolate (ca3d_ensemble_census_connected / ca3d_ensemble_isolate_connected with
+CA3D_CONNECT_TORUS, kernels ca_ensemble_census64_torus / ca_ensemble_isolate64_torus) against the closed forms on the same universes in
+the same run: the ash of --census produced under the torus boundary, B = 256 and 1024, the census launch and the isolate launch of all
+census objects under each connectivity, the two alternating. Both are checked against host.census / host.isolate in three sampled
+universes first. Reported: medians of --repeats hipEvent times, their ratios, and the object counts under the two connectivities. No ratio
+is required. Written to profiles/ensemble_census_torus_64.json unless --out says otherwise.
+
 --isolate measures the isolate (ca3d_ensemble_isolate, kernel ca_ensemble_isolate64: objects a census named, each made the only thing
 in a universe of its own, centred, with its source's rule) on the ash workload of --census (Moore B6 / S5-7, and_rounds 1, seeds 1 .. B,
 step_until_cycle(512)): a census at max_components 1024, then EVERY object of the B = 256 universes isolated into a second ensemble in
@@ -627,6 +634,69 @@ def isolate_rows(args):
     return rows, cutter
 
 
+def census_torus_rows(args):
+    """census and isolate under CA3D_CONNECT_TORUS against the same launches under CA3D_CONNECT_CLOSED on the same universes: one row
+    per B."""
+    M = 1024
+    born, survive, rounds = CENSUS_ASH["ash B6/S5-7"]
+    ens, nursery = Ensemble(0), Ensemble(0)
+    rows = []
+    for B in args.universes:
+        ens.configure(B, neighbourhood="moore")
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        ens.seed_states(0, np.arange(1, B + 1), rounds)
+        ens.set_boundary("torus")
+        done, reason, _ = ens.step_until_cycle(512)
+        sample = sorted({0, B // 2, B - 1})
+        found, jobs = {}, {}
+        for how in host.CONNECTIVITIES:
+            comps, n, rest = ens.census(max_components=M, connectivity=how)
+            if rest.any():
+                raise SystemExit(f"B {B}, {how}: a census of {M} objects a universe is not complete")
+            for u in sample:
+                c, k, r = host.census(ens.read_state(u, 1)[0], M, how)
+                if (int(n[u]), int(rest[u])) != (k, r) or comps[u].tobytes() != c.tobytes():
+                    raise SystemExit(f"B {B}, {how}: the census of universe {u} is not host.census'")
+            found[how] = (comps, n)
+            jobs[how] = np.array([(u, int(c["first_cell"])) for u in range(B) for c in comps[u, :n[u]]], dtype=np.uint32).reshape(-1, 2)
+        nursery.configure(max(len(j) for j in jobs.values()), neighbourhood="moore")
+        for how in host.CONNECTIVITIES:
+            comps, n = found[how]
+            starts = np.concatenate([[0], np.cumsum(n)])
+            pop, shift = nursery.isolate(jobs[how], 0, ens, "centre", True, connectivity=how)
+            for u in sample:
+                words = ens.read_state(u, 1)[0]
+                got = nursery.read_state(int(starts[u]), int(n[u]))
+                for k in range(int(n[u])):
+                    j = int(starts[u]) + k
+                    w, p, d = host.isolate(words, int(jobs[how][j, 1]), "centre", how)
+                    if not np.array_equal(got[k], w) or (int(pop[j]), tuple(int(v) for v in shift[j])) != (p, d):
+                        raise SystemExit(f"B {B}, {how}: object {k} of universe {u} is not host.isolate's")
+        census_ms, isolate_ms = {h: [] for h in host.CONNECTIVITIES}, {h: [] for h in host.CONNECTIVITIES}
+        for _ in range(args.repeats):  # the two alternate
+            for how in host.CONNECTIVITIES:
+                ens.census(max_components=M, connectivity=how)
+                census_ms[how].append(ens.census_gpu_ms())
+                nursery.isolate(jobs[how], 0, ens, "centre", True, connectivity=how)
+                isolate_ms[how].append(nursery.isolate_gpu_ms())
+        med = statistics.median
+        row = {"workload": "ash B6/S5-7 under the torus boundary", "universes": B, "max_components": M, "placement": "centre", "copy_rules": True,
+               "stepping": {"max_steps": 512, "stopped": int(np.count_nonzero(reason)), "median_steps_done": float(np.median(done))},
+               "objects": {h: int(len(jobs[h])) for h in host.CONNECTIVITIES},
+               "objects_the_closed_census_splits": int(len(jobs["closed"]) - len(jobs["torus"])),
+               "universes_where_the_counts_differ": int(np.count_nonzero(found["closed"][1] != found["torus"][1])),
+               "verified_against_host_in": sample,
+               "census_gpu_ms": {h: med(census_ms[h]) for h in host.CONNECTIVITIES}, "census_gpu_ms_all": census_ms,
+               "isolate_gpu_ms": {h: med(isolate_ms[h]) for h in host.CONNECTIVITIES}, "isolate_gpu_ms_all": isolate_ms,
+               "census_torus_over_closed": med(census_ms["torus"]) / med(census_ms["closed"]),
+               "isolate_torus_over_closed": med(isolate_ms["torus"]) / med(isolate_ms["closed"])}
+        rows.append(row)
+        print(json.dumps(row))
+    ens.close()
+    nursery.close()
+    return rows
+
+
 def compose_rows(args):
     """compose against the read_state + host.compose + upload_state loop: one row per B and mix of orientations. -> rows"""
     M = 1024
@@ -910,6 +980,7 @@ def main():
     ap.add_argument("--trace", action="store_true", help="measure step_trace against the step + summaries loop and plain stepping instead (both neighbourhoods; default B = 256 1024)")
     ap.add_argument("--sheet", action="store_true", help="measure render_sheet against the upload + render loop instead (B = 256 1024)")
     ap.add_argument("--census", action="store_true", help="measure census against read_state + labelling on the CPU instead (B = 256 1024)")
+    ap.add_argument("--census-torus", action="store_true", help="measure census and isolate under the torus connectivity against the closed one instead (B = 256 1024)")
     ap.add_argument("--isolate", action="store_true", help="measure isolate against the read_state + cut + upload_state loop instead (B = 256)")
     ap.add_argument("--compose", action="store_true", help="measure compose against the read_state + host.compose + upload_state loop instead (B = 256)")
     ap.add_argument("--canon", action="store_true", help="measure canon against the read_state + host.canon loop instead (B = 256)")
@@ -919,7 +990,7 @@ def main():
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.boundary else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.census_torus or args.boundary else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -948,6 +1019,25 @@ def main():
                       "universes after 3 steps",
             "not_measured": "the *_cycle, *_trace and *_moving forms, other B, other rules",
             "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
+    if args.census_torus:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_census_torus_64.json")
+        result = {
+            "what": "B universes of 64^3 of ash produced under the torus boundary (seed_states, seeds 1 .. B, and_rounds 1, Moore B6/S5-7, set_boundary torus, "
+                    "step_until_cycle(512)): Ensemble.census(max_components 1024) and Ensemble.isolate of every census object (centred, with its rule) under "
+                    "connectivity torus against the same two launches under connectivity closed on the same universes; each connectivity isolates its own "
+                    "census' objects",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"torus": ["ca_ensemble_census64_torus", "ca_ensemble_isolate64_torus"], "closed": ["ca_ensemble_census64", "ca_ensemble_isolate64"]},
+            "timing": f"hipEvent time around the launch; medians of {args.repeats} measurements, the two connectivities alternating in one process, after both "
+                      "censuses equalled host.census byte for byte and every isolated object host.isolate in the sampled universes",
+            "rows": census_torus_rows(args),
         }
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
