@@ -309,6 +309,43 @@ def test_more_universes_than_compute_units_over_a_range(ens):
     call_and_check(ens, wants[93:98], periods[93:98], first=100)
 
 
+def test_canon_and_canon_period_share_the_staging_array(ens):
+    """`canon` and `canon_period` stage in one array of the handle. On one handle of 8 universes — the glider's four phases, two small
+    shapes and two crafted states — a `canon` of one universe (the smallest array), a `canon_period` of all with keys (grows it), a
+    `canon` of all with digests (grows it again) and a `canon_period` of one (reuses it): every result is `host.canon`'s /
+    `host.canon_period`'s."""
+    t = ship("a")
+    pool = [(("glider phase", k), t[k]) for k in range(4)]
+    pool += [(("small", n), kc.shape_words(n)) for n in ("block", "rod")] + [(("crafted", n), cc.state(n)) for n in ("shapes", "corners")]
+    hold(ens, [s for _, s in pool])
+    rules = moore_rules(*SHIP)
+    periods = np.array([4, 4, 4, 4, 1, 2, 3, 2], dtype=np.uint32)
+    want_canon = [kc.reference(k, s) for k, s in pool]
+    want_period = [reference(k, s, rules, int(p)) for (k, s), p in zip(pool, periods)]
+
+    def same_period_record(got, k):
+        for f in FIELDS:
+            assert int(got[f]) == int(want_period[k][0][f]), (k, f, int(got[f]), int(want_period[k][0][f]))
+
+    one = ens.canon(0, 1)
+    assert one.shape == (1,)
+    for f in ("key", "symmetry", "orientation", "population", "box_min", "box_max"):
+        assert int(one[0][f]) == int(want_canon[0][0][f]), f
+    rec, keys = ens.canon_period(periods, 0, 8, keys=True)
+    assert rec.shape == (8,) and keys.shape == (8, 4)
+    for k in range(8):
+        same_period_record(rec[k], k)
+        p = int(periods[k])
+        np.testing.assert_array_equal(keys[k, :p], want_period[k][1], err_msg=f"universe {k}: keys")
+        assert not keys[k, p:].any(), k
+    rec, dig = ens.canon(0, 8, digests=True)
+    for k in range(8):
+        kc.assert_record(rec[k], dig[k], want_canon[k], pool[k][0])
+    alone = ens.canon_period(periods[:1], 0, 1)
+    assert alone.shape == (1,)
+    same_period_record(alone[0], 0)
+
+
 def test_ordering(ens):
     """A step queued and not waited for lies in front of the call: the result is that of the stepped states."""
     first = host.random_fill(W, seed=9, and_rounds=1)
