@@ -12,6 +12,7 @@ import pytest
 import oracle_lib as ol
 from cellularautomatons3d_amd import host
 from gpu_common import rules, set_rules
+from render_compare import compare as _compare  # shared with test_gpu_render_turned.py
 
 pytestmark = pytest.mark.gpu
 
@@ -25,47 +26,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def _compare(eng, cells, G, u, W, H, spp, rows=None, min_ok=0.999):
-    eng.configure(G)
-    set_rules(eng, rules("default"))
-    eng.upload_state(cells)
-    # the plain kernel (one pixel per lane, samples in order), the in-wave scheduled one and the ray-stream passes (the default; also with
-    # every decision of their interval filter checked against the slab test: a contradiction fails the call) must agree bit for bit
-    eng.set_option("render_sched", 0)
-    pres0, light0, depth0 = eng.render(u, W, H, spp)
-    st0 = eng.render_stats()
-    eng.set_option("render_sched", 1)
-    for stream, check in ((0, 0), (1, 1), (1, 0)):
-        eng.set_option("render_stream", stream)
-        eng.set_option("render_stream_check", check)
-        pres, light, depth = eng.render(u, W, H, spp)
-        st1 = eng.render_stats()
-        np.testing.assert_array_equal(pres, pres0)
-        np.testing.assert_array_equal(light.view(np.uint16), light0.view(np.uint16))
-        np.testing.assert_array_equal(depth.view(np.uint16), depth0.view(np.uint16))
-        assert (st0.shadow_rays, st0.primary_cell_visits, st0.shadow_cell_visits) == (st1.shadow_rays, st1.primary_cell_visits, st1.shadow_cell_visits)
-    olight, odepth, opres, oshadow = ol.render(cells, G, u, W, H, spp, rows)
-    y0, y1 = rows if rows else (0, H)
-    sl = slice(y0, y1)
-    l = light[sl].astype(np.float32)
-    d = depth[sl].astype(np.float32)
-    od16 = odepth[sl].astype(np.float16).astype(np.float32)
-    ulp = np.maximum(np.spacing(od16.astype(np.float16)).astype(np.float32), 1e-4)
-    ok_rgb = np.abs(l[..., :3] - olight[sl][..., :3]).max(-1) <= 2e-3
-    ok_depth = np.abs(d[..., 0] - od16[..., 0]) <= ulp[..., 0]
-    want8 = np.rint(np.clip(opres[sl], 0, 1) * 255.0)
-    ok_pres = np.abs(pres[sl].astype(np.float32) - want8).max(-1) <= 1.0
-    frac = (ok_rgb & ok_depth & ok_pres).mean()
-    assert frac >= min_ok, (frac, ok_rgb.mean(), ok_depth.mean(), ok_pres.mean())
-    assert (light[sl][..., 3] == 1.0).all() and (depth[sl][..., 1] == 1.0).all()
-    assert olight[sl][..., :3].max() > 0.05  # the scene is not empty
-    if rows is None:
-        st = eng.render_stats()
-        assert st.primary_rays == W * H * spp
-        assert abs(int(st.shadow_rays) - oshadow) <= max(4, int(0.001 * oshadow))
-    return frac
 
 
 @pytest.mark.parametrize("pose", ["default", "oblique"])
