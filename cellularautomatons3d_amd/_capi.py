@@ -104,6 +104,15 @@ class CanonPeriodStruct(C.Structure):
                 ("population", C.c_uint32), ("flags_shift", C.c_uint32)]
 
 
+class EnvelopeStruct(C.Structure):
+    """ca3d_envelope (include/ca3d.h): what `ca3d_ensemble_envelope` says of one universe, 48 bytes (`host.ENVELOPE_DTYPE`)."""
+    _fields_ = [("period", C.c_uint32), ("flags", C.c_uint32), ("heat", C.c_uint32), ("population_sum", C.c_uint32),
+                ("envelope_population", C.c_uint32), ("stator_population", C.c_uint32), ("envelope_min", C.c_uint8 * 4),
+                ("envelope_max", C.c_uint8 * 4), ("rotor_min", C.c_uint8 * 4), ("rotor_max", C.c_uint8 * 4), ("reserved", C.c_uint32 * 2)]
+
+
+#: the one flag bit of `ca3d_ensemble_envelope` beside its image bits (`host.ENVELOPE_IMAGES`)
+ENVELOPE_COPY_RULES = 0x100
 #: the flag bits of `ca3d_ensemble_compose`, and the most parts a call takes
 COMPOSE_OVER = 0x1
 COMPOSE_COPY_RULES = 0x100
@@ -223,6 +232,8 @@ SYMBOLS = [
     ("ca3d_ensemble_canon", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(CanonStruct), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("ca3d_ensemble_canon_period", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.POINTER(CanonPeriodStruct), C.POINTER(C.c_uint64), C.c_uint32,
                                              C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_envelope", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _H, C.c_uint32, C.c_uint32, C.POINTER(EnvelopeStruct),
+                                         C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

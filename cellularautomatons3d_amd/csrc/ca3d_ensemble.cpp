@@ -12,9 +12,10 @@
 // ca3d_ensemble_compose stages whole universes, turned and shifted, into universes of their union (ca_compose.hip).
 // ca3d_ensemble_canon names universes up to the 48 symmetries of the cube and translation (ca_canon.hip).
 // ca3d_ensemble_canon_period does so over a period of each universe's own steps, inside the kernel (ca_canon_period.hip).
+// ca3d_ensemble_envelope takes envelope, stator, rotor and heat over such a period, and may write them as universes (ca_envelope.hip).
 // What these calls share is written once, in the unnamed namespace: a staging array on the handle (Scratch) and the event pair around a
 // launch (Timer), both had from `reserve`; reset_records and mark_state / mark_rules for universes that were just written; and, for
-// isolate and compose, the checks on two handles, the wait on the source's stream and the end of the call (finish_destinations).
+// isolate, compose and envelope, the checks on two handles, the wait on the source's stream and the end of the call (finish_destinations).
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -97,6 +98,12 @@ struct ca3d_ensemble
 	// uploaded periods, [count] words — and has an event pair of its own
 	Scratch canon;
 	Timer canon_time, canon_period_time;
+	// ca3d_ensemble_envelope, on the handle the launch runs on (the destination, or the source when there is none): the records of the
+	// call under way, [count] of 48 bytes, then the uploaded periods, [count] words; the event that orders the launch behind the
+	// source's stream
+	Scratch envelope;
+	Timer envelope_time;
+	hipEvent_t envelope_src = nullptr;
 };
 
 namespace
@@ -121,7 +128,7 @@ void free_arrays(ca3d_ensemble *e)
 	e->sheet_counters = nullptr;
 	e->sheet_px = 0;
 	e->sheet_drawn = false;
-	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon})
+	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon, &e->envelope})
 	{
 		if (s->array) hipFree(s->array);
 		*s = Scratch{};
@@ -586,10 +593,10 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	hipSetDevice(e->device);
 	if (e->stream) hipStreamSynchronize(e->stream);
 	free_arrays(e);
-	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time})
+	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time, e->envelope_time})
 		for (hipEvent_t ev : {t.start, t.stop})
 			if (ev) hipEventDestroy(ev);
-	for (hipEvent_t ev : {e->ev_seed, e->isolate_src, e->compose_src})
+	for (hipEvent_t ev : {e->ev_seed, e->isolate_src, e->compose_src, e->envelope_src})
 		if (ev) hipEventDestroy(ev);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
@@ -1188,6 +1195,80 @@ int ca3d_ensemble_canon_period(ca3d_ensemble_t *e, uint32_t first, uint32_t coun
 	if (keys) HIP_TRY(hipMemcpyAsync(keys, l.keys, key_bytes, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->canon_period_time.start, e->canon_period_time.stop));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_envelope(ca3d_ensemble_t *src, uint32_t first, uint32_t count, const uint32_t *periods, ca3d_ensemble_t *dst, uint32_t dst_first, uint32_t flags,
+                           ca3d_envelope *out, float *gpu_ms) CA3D_API_TRY
+{
+	if (!src) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!periods) return fail(CA3D_ERR_INVALID_ARGUMENT, "periods is NULL");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	int rc = check_range(src, first, count);
+	if (rc) return rc;
+	for (uint32_t k = 0; k < count; k++)
+		if (periods[k] == 0 || periods[k] > CA3D_CANON_MAX_PERIOD)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "periods[%u] is %u: a period is 1 .. %u", k, periods[k], (unsigned)CA3D_CANON_MAX_PERIOD);
+	const uint32_t images = flags & (CA3D_ENVELOPE_IMAGE_ENVELOPE | CA3D_ENVELOPE_IMAGE_STATOR | CA3D_ENVELOPE_IMAGE_ROTOR);
+	const bool copy_rules = (flags & CA3D_ENVELOPE_COPY_RULES) != 0u;
+	if (flags & ~(images | CA3D_ENVELOPE_COPY_RULES)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in flags %#x", flags);
+	if (images && !dst) return fail(CA3D_ERR_INVALID_ARGUMENT, "flags %#x ask for images, and dst is NULL", flags);
+	if (!images && dst) return fail(CA3D_ERR_INVALID_ARGUMENT, "dst is given, and flags %#x ask for no image (CA3D_ENVELOPE_IMAGE_ENVELOPE = 1, _STATOR = 2, _ROTOR = 4)", flags);
+	if (!images && copy_rules) return fail(CA3D_ERR_INVALID_ARGUMENT, "CA3D_ENVELOPE_COPY_RULES in flags %#x that ask for no image: there is no destination to copy a rule to", flags);
+	// source k writes its images into destinations dst_first + k per + i (a count that does not fit a word is past every ensemble's end)
+	const uint64_t wanted = (uint64_t)count * (uint32_t)__builtin_popcount(images);
+	const uint32_t n_dst = wanted > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)wanted;
+	if (dst)
+	{
+		if ((rc = check_destinations(dst, src, dst_first, n_dst, "images into"))) return rc;
+		// the source range and the destinations are two intervals of the same ensemble: the first universe they share
+		const uint32_t shared = first > dst_first ? first : dst_first;
+		if (src == dst && shared - first < count && shared - dst_first < n_dst)
+			return check_source(dst, src, dst_first, n_dst, "source", shared - first, shared, false);
+		if ((rc = check_same_device_and_kind(dst, src, false, "CA3D_ENVELOPE_COPY_RULES"))) return rc; // the device
+	}
+	if ((rc = require_state(src, first, count))) return rc;
+	for (uint32_t u = first; u < first + count; u++)
+		if (!src->has_rules[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_set_rules has not been called for universe %u", u);
+	if (dst && (rc = check_same_device_and_kind(dst, src, copy_rules, "CA3D_ENVELOPE_COPY_RULES"))) return rc; // the kind
+	ca3d_ensemble *run = dst ? dst : src; // the handle whose stream takes the launch
+	HIP_TRY(hipSetDevice(run->device));
+	const size_t rec_bytes = (size_t)count * sizeof(ca3d_envelope), period_bytes = (size_t)count * sizeof(uint32_t), bytes = rec_bytes + period_bytes;
+	if ((rc = reserve(run, run->envelope, bytes, &run->envelope_time, &run->envelope_src, "%zu bytes of envelope records", bytes))) return rc;
+	EnvelopeLaunch l{};
+	l.state = src->state;
+	l.rules = src->rules;
+	l.neighbourhood = src->neighbourhood;
+	l.clustered = src->clustered;
+	l.boundary = src->boundary;
+	l.first = first; l.count = count;
+	l.out = run->envelope.at<ca3d_envelope>();
+	uint32_t *periods_dev = run->envelope.at<uint32_t>(rec_bytes);
+	l.periods = periods_dev;
+	l.images = images;
+	if (dst)
+	{
+		l.dst_state = dst->state; l.dst_prev = dst->prev;
+		l.dst_rules = dst->rules;
+		l.dst_first = dst_first;
+		l.rule_words = copy_rules ? rule_words(dst) : 0u;
+	}
+	if ((rc = wait_for_source(run, src, run->envelope_src))) return rc;
+	// (from pageable memory: the copy has left the caller's array when the call returns)
+	HIP_TRY(hipMemcpyAsync(periods_dev, periods, period_bytes, hipMemcpyHostToDevice, run->stream));
+	HIP_TRY(hipEventRecord(run->envelope_time.start, run->stream));
+	HIP_TRY(launch_envelope(l, run->stream));
+	HIP_TRY(hipEventRecord(run->envelope_time.stop, run->stream));
+	if (dst)
+	{
+		if ((rc = finish_destinations(dst, dst_first, n_dst, dst->envelope, dst->envelope_time, out, rec_bytes, gpu_ms))) return rc;
+		if (copy_rules) mark_rules(dst, dst_first, n_dst);
+		return CA3D_OK;
+	}
+	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, src->stream));
+	HIP_TRY(hipStreamSynchronize(src->stream));
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, src->envelope_time.start, src->envelope_time.stop));
 	return CA3D_OK;
 }
 CA3D_API_CATCH

@@ -309,6 +309,28 @@ struct CanonPeriodLaunch
 	uint32_t keys_stride;
 };
 hipError_t launch_canon_period(const CanonPeriodLaunch &l, hipStream_t stream);
+// ca_envelope.hip: envelope, stator, rotor and heat over periods[k] steps of universe first + k, for universes [first, first + count) of
+// a source ensemble's state and rule arrays (ca3d_ensemble_envelope), one workgroup each of ca_ensemble_envelope_{vn,moore,clustered}64
+// [_torus|_closed] by the source's kind and boundary; out and periods are indexed by universe - first. With n = popcount(images) != 0,
+// source k writes its images in bit order into both buffers of destination universes dst_first + k n + i. The caller has checked every
+// range and period, and that no source universe is a destination. The source's states and rules are only read.
+struct EnvelopeLaunch
+{
+	const uint32_t *state;          // [Bs][8192], the source ensemble's current states
+	const uint32_t *rules;          // [Bs][ensemble_rule_words()]
+	int neighbourhood;              // CA3D_ENSEMBLE_*, of the source
+	bool clustered;
+	int boundary;                   // CA3D_ENSEMBLE_BOUNDARY_*, of the source
+	uint32_t first, count;
+	const uint32_t *periods;        // device, [count]
+	ca3d_envelope *out;             // device, [count]: every entry is written
+	uint32_t images;                // CA3D_ENVELOPE_IMAGE_* bits; 0: nothing below is used
+	uint32_t *dst_state, *dst_prev; // [Bd][8192], the destination ensemble's two buffers
+	uint32_t *dst_rules;            // [Bd][rule_words]
+	uint32_t dst_first;
+	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
+};
+hipError_t launch_envelope(const EnvelopeLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

@@ -371,6 +371,41 @@ class Ensemble:
         """hipEvent time of the last `canon_period` launch of this object, in milliseconds (None before the first)."""
         return getattr(self, "_canon_period_ms", None)
 
+    def envelope(self, periods, first: int = 0, dst: Optional["Ensemble"] = None, dst_first: int = 0, images=(),
+                 copy_rules: bool = False) -> np.ndarray:
+        """`ca3d_ensemble_envelope`: HOW universe first + k oscillates over periods[k] steps of its own, taken INSIDE one launch behind
+        the queued steps under this ensemble's rule and boundary; this ensemble is left exactly as it is -> records of
+        `host.ENVELOPE_DTYPE`: `envelope_population` (cells that ever live), `stator_population` (cells that always live), `heat`
+        (cells changed, summed over the steps), `population_sum`, the inclusive boxes of the envelope and of the rotor (envelope
+        without stator; zero for an empty set), and `flags`: bit 0 (`host.ENVELOPE_RETURNS`) says that after periods[k] steps the
+        state is back word for word. `host.envelope_derived` gives rotor population, volatility and heat per step. `periods` is one
+        number for every universe from `first` on, or one per universe, each 1 .. `host.CANON_MAX_PERIOD`.
+        `images`: any of "envelope", "stator", "rotor"; with n of them universe dst_first + k * n + i of `dst` (this ensemble or
+        another one on the same device; required with images, None without) becomes the i-th selected image of source k, in that order,
+        at step 0. `copy_rules`: each destination takes its source universe's rule (both ensembles of one kind). `host.envelope` is
+        the same on the CPU for one universe; `envelope_gpu_ms()` tells what the launch took."""
+        p = _as_u32(periods).ravel()
+        if np.ndim(periods) == 0:
+            p = np.full(max(self.n - first, 0), p[0], dtype=np.uint32)
+        p = np.ascontiguousarray(p)
+        flags = 0
+        for name in ([images] if isinstance(images, str) else images):
+            if name not in host.ENVELOPE_IMAGES:
+                raise ValueError(f"unknown image {name!r}: one of {tuple(host.ENVELOPE_IMAGES)}")
+            flags |= host.ENVELOPE_IMAGES[name]
+        if copy_rules:
+            flags |= _capi.ENVELOPE_COPY_RULES
+        rec = np.zeros(p.size, dtype=host.ENVELOPE_DTYPE)
+        ms = C.c_float(0.0)
+        _capi.check(self._lib.ca3d_ensemble_envelope(self._h, first, p.size, p.ctypes.data_as(_u32p), None if dst is None else dst._h,
+                                                     dst_first, flags, rec.ctypes.data_as(C.POINTER(_capi.EnvelopeStruct)), C.byref(ms)))
+        self._envelope_ms = float(ms.value)
+        return rec
+
+    def envelope_gpu_ms(self) -> float:
+        """hipEvent time of the last `envelope` launch of this object, in milliseconds (None before the first)."""
+        return getattr(self, "_envelope_ms", None)
+
     def canon_phases(self, periods, first: int = 0, count: Optional[int] = None,
                      max_period: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """`canon` over a whole period, for universes already classified as oscillators or ships (`step_until_cycle`,

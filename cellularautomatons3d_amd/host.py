@@ -942,6 +942,78 @@ def canon_period(states) -> Tuple[np.ndarray, np.ndarray]:
     return rec, keys
 
 
+# ------------------------------------------------------------------------------------------ envelope over a period
+# The definition of ca3d_ensemble_envelope (include/ca3d.h) in executable form, for one universe.
+
+#: ca3d_envelope (include/ca3d.h), 48 bytes; a box corner is x, y, z and a zero byte
+ENVELOPE_DTYPE = np.dtype([("period", "<u4"), ("flags", "<u4"), ("heat", "<u4"), ("population_sum", "<u4"), ("envelope_population", "<u4"),
+                           ("stator_population", "<u4"), ("envelope_min", "u1", 4), ("envelope_max", "u1", 4), ("rotor_min", "u1", 4),
+                           ("rotor_max", "u1", 4), ("reserved", "<u4", 2)])
+#: bit 0 of `flags`; the image bits of the call's flags, in the order the images are written
+ENVELOPE_RETURNS = 1
+ENVELOPE_IMAGES = {"envelope": 1, "stator": 2, "rotor": 4}
+
+
+def _packed_popcount(words) -> int:
+    return int(np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8)).sum())
+
+
+def _packed_box(words) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """(box_min, box_max) of a packed 64^3 state as (x, y, z), inclusive; ((0, 0, 0), (0, 0, 0)) for an empty one."""
+    cells = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").ravel().view(np.uint8), bitorder="little").reshape(64, 64, 64)
+    xs, ys, zs = (np.flatnonzero(cells.any(axis=a)) for a in ((0, 1), (0, 2), (1, 2)))
+    if xs.size == 0:
+        return (0, 0, 0), (0, 0, 0)
+    return (int(xs[0]), int(ys[0]), int(zs[0])), (int(xs[-1]), int(ys[-1]), int(zs[-1]))
+
+
+def envelope_of_phases(states) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """`ca3d_ensemble_envelope` of ONE universe whose phases the caller has stepped: `states` is [P + 1, 8192], S_0 .. S_P
+    -> (record of ENVELOPE_DTYPE, envelope, stator, rotor), the three images as packed states."""
+    s = np.ascontiguousarray(states, dtype="<u4")
+    if s.ndim != 2 or s.shape[0] < 2 or s.shape[1] != words_per_buffer(64):
+        raise ValueError("states is [P + 1, 8192] with P >= 1: the phases S_0 .. S_P")
+    p = s.shape[0] - 1
+    if p > CANON_MAX_PERIOD:
+        raise ValueError(f"a period is at most {CANON_MAX_PERIOD}")
+    env, sta = np.bitwise_or.reduce(s[:p], axis=0), np.bitwise_and.reduce(s[:p], axis=0)
+    rot = env & ~sta
+    rec = np.zeros((), dtype=ENVELOPE_DTYPE)
+    rec["period"] = p
+    rec["flags"] = ENVELOPE_RETURNS if np.array_equal(s[p], s[0]) else 0
+    rec["heat"] = sum(_packed_popcount(s[t] ^ s[t + 1]) for t in range(p))
+    rec["population_sum"] = sum(_packed_popcount(s[t]) for t in range(p))
+    rec["envelope_population"], rec["stator_population"] = _packed_popcount(env), _packed_popcount(sta)
+    for name, image in (("envelope", env), ("rotor", rot)):
+        lo, hi = _packed_box(image)
+        rec[name + "_min"][:3], rec[name + "_max"][:3] = lo, hi
+    return rec, env, sta, rot
+
+
+def envelope(state, kind: str, tables, period: int, boundary: str = "reference") -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """`ca3d_ensemble_envelope` for ONE packed 64^3 universe, in plain numpy over `ensemble_step`: the universe is followed over
+    `period` steps (1 .. CANON_MAX_PERIOD) of the rule `kind`, `tables` under `boundary`, as `ensemble_step` takes them
+    -> (record of ENVELOPE_DTYPE, envelope, stator, rotor). With S_t the state after t steps: the envelope is the OR of S_0 ..
+    S_(period-1), the stator their AND, the rotor envelope & ~stator; `heat` sums popcount(S_t ^ S_(t+1)) over t < period,
+    `population_sum` popcount(S_t); the boxes are inclusive, zero for an empty set; ENVELOPE_RETURNS (bit 0 of flags) is set exactly
+    when S_period equals S_0 word for word. rotor_population, volatility and heat per step: `envelope_derived`."""
+    if not 1 <= int(period) <= CANON_MAX_PERIOD:
+        raise ValueError(f"a period is 1 .. {CANON_MAX_PERIOD}")
+    s = [np.ascontiguousarray(state, dtype="<u4").ravel()]
+    for _ in range(int(period)):
+        s.append(ensemble_step(s[-1], kind, tables, boundary))
+    return envelope_of_phases(np.stack(s))
+
+
+def envelope_derived(records) -> dict:
+    """What follows from ENVELOPE_DTYPE records without another look at the states: `rotor_population` = envelope - stator,
+    `volatility` = rotor / envelope (0 for an empty envelope), `heat_per_step` = heat / period, `returns` (bool)."""
+    r = np.asarray(records)
+    env, rot = r["envelope_population"].astype(np.float64), (r["envelope_population"] - r["stator_population"]).astype(np.uint32)
+    return {"rotor_population": rot, "volatility": np.divide(rot, env, out=np.zeros_like(env), where=env != 0),
+            "heat_per_step": r["heat"] / np.maximum(r["period"], 1), "returns": (r["flags"] & ENVELOPE_RETURNS) != 0}
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

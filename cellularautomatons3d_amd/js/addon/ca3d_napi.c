@@ -1502,6 +1502,45 @@ static napi_value js_ensemble_canon_period(napi_env env, napi_callback_info info
 	return v;
 }
 
+/* ensembleEnvelope(srcHandle, first, Uint32Array(count) periods, dstHandle or null, dstFirst, flags, Uint32Array(count * 12) records)
+ * -> gpuMs: envelope, stator, rotor and heat of universes [first, first + count) over periods[k] steps of their own, taken inside the
+ * kernel, the images flags selects written into dst's universes from dstFirst (ca3d_ensemble_envelope); a record is ca3d_envelope's
+ * twelve words: period, flags, heat, populationSum, envelopePopulation, statorPopulation, envelopeMin, envelopeMax, rotorMin, rotorMax
+ * (x | y << 8 | z << 16 each), 0, 0 (js/ca3d.js opens them) */
+static napi_value js_ensemble_envelope(napi_env env, napi_callback_info info)
+{
+	napi_value argv[7];
+	if (!get_args(env, info, 7, argv)) return NULL;
+	ca3d_ensemble_t *src = get_ensemble(env, argv[0]);
+	if (!src) return NULL;
+	ca3d_ensemble_t *dst = NULL;
+	napi_valuetype t;
+	napi_typeof(env, argv[3], &t);
+	if (t != napi_null && t != napi_undefined && !(dst = get_ensemble(env, argv[3]))) return NULL;
+	uint32_t first, dst_first, flags;
+	void *periods, *recs;
+	size_t count, nrecs;
+	if (!get_u32(env, argv[1], &first) || !get_typed(env, argv[2], napi_uint32_array, 0, &periods, &count) || !get_u32(env, argv[4], &dst_first) ||
+	    !get_u32(env, argv[5], &flags) || !get_typed(env, argv[6], napi_uint32_array, 0, &recs, &nrecs))
+		return NULL;
+	if (count > 0xFFFFFFFFu || nrecs != count * 12u)
+	{
+		napi_throw_range_error(env, NULL, "records must hold twelve words a universe");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_envelope) == 48, "a record crosses as twelve words");
+	float ms = 0.f;
+	/* (count 0: the library refuses the call and names the reason; it reads and writes no array, and an empty typed array may have no
+	 * address at all) */
+	uint32_t none[12];
+	if (!count) periods = recs = none;
+	int rc = ca3d_ensemble_envelope(src, first, (uint32_t)count, (const uint32_t *)periods, dst, dst_first, flags, (ca3d_envelope *)recs, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1727,7 +1766,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleRenderSheet", js_ensemble_render_sheet}, {"ensembleSheetStats", js_ensemble_sheet_stats},
 	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}, {"ensembleCompose", js_ensemble_compose},
 	    {"ensembleCanon", js_ensemble_canon},
-	    {"ensembleCanonPeriod", js_ensemble_canon_period}};
+	    {"ensembleCanonPeriod", js_ensemble_canon_period},
+	    {"ensembleEnvelope", js_ensemble_envelope}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

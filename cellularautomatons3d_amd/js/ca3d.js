@@ -233,6 +233,8 @@ const ISOLATE_PLACEMENTS = ["keep", "centre", "origin"]; // index = CA3D_ISOLATE
 const ISOLATE_COPY_RULES = 0x100;
 const COMPOSE_OVER = 0x1, COMPOSE_COPY_RULES = 0x100; // CA3D_COMPOSE_OVER / CA3D_COMPOSE_COPY_RULES (Ensemble.compose)
 const CANON_CLOSED = 0x1, CANON_MAX_PERIOD = 4096; // CA3D_CANON_CLOSED / CA3D_CANON_MAX_PERIOD (Ensemble.canonPeriod)
+// CA3D_ENVELOPE_RETURNS, the image bits in the order the images are written, CA3D_ENVELOPE_COPY_RULES (Ensemble.envelope)
+const ENVELOPE_RETURNS = 0x1, ENVELOPE_IMAGES = { envelope: 1, stator: 2, rotor: 4 }, ENVELOPE_COPY_RULES = 0x100;
 
 class Engine
 {
@@ -708,6 +710,38 @@ class Ensemble
 			if (kwords) keys.push(Array.from({ length: periods[k] }, (_, t) => big(kwords, 2 * (stride * k + t))));
 		}
 		return kwords ? { records, keys, gpuMs } : { records, gpuMs };
+	}
+	/** Envelope over a period (ca3d_ensemble_envelope): HOW universe opts.first + k oscillates over periods[k] steps of its own, taken
+	 *  INSIDE one launch behind the queued steps under this ensemble's rule and boundary; this ensemble is left exactly as it is.
+	 *  periods: one number for every universe from opts.first on, or an array with one period per universe, each 1 .. 4096
+	 *  -> {records, gpuMs}, records[k] = {period, returns (after `period` steps the state is back word for word), heat (cells changed,
+	 *  summed over the steps), populationSum, envelopePopulation (cells that ever live), statorPopulation (cells that always live),
+	 *  rotorPopulation, envelopeMin, envelopeMax, rotorMin, rotorMax ([x, y, z], inclusive; zeros for an empty set)}.
+	 *  opts.images: any of "envelope", "stator", "rotor"; with n of them universe opts.dstFirst + k n + i of opts.dst (this ensemble
+	 *  or another one on the same device; required with images) becomes the i-th of them, in that order, at step 0. opts.copyRules
+	 *  (default false): each destination takes its source universe's rule (both ensembles of one kind). */
+	envelope(periods, opts)
+	{
+		const o = Object.assign({ first: 0, dst: null, dstFirst: 0, images: [], copyRules: false }, opts || {});
+		const count = Math.max(this.n - o.first, 0);
+		const p = typeof periods === "number" ? new Uint32Array(count).fill(periods) : Uint32Array.from(periods);
+		let flags = o.copyRules ? ENVELOPE_COPY_RULES : 0;
+		for (const name of o.images)
+		{
+			if (!(name in ENVELOPE_IMAGES)) throw new Error(`unknown image ${JSON.stringify(name)}: "envelope", "stator" or "rotor"`);
+			flags |= ENVELOPE_IMAGES[name];
+		}
+		const words = new Uint32Array(p.length * 12);
+		const gpuMs = this._a.ensembleEnvelope(this._e, o.first, p, o.dst ? o.dst._e : null, o.dstFirst, flags, words);
+		const box = (w) => [w & 0xFF, (w >>> 8) & 0xFF, (w >>> 16) & 0xFF];
+		const records = [];
+		for (let k = 0; k < p.length; k++)
+		{
+			const r = words.subarray(12 * k, 12 * k + 12);
+			records.push({ period: r[0], returns: (r[1] & ENVELOPE_RETURNS) !== 0, heat: r[2], populationSum: r[3], envelopePopulation: r[4],
+				statorPopulation: r[5], rotorPopulation: r[4] - r[5], envelopeMin: box(r[6]), envelopeMax: box(r[7]), rotorMin: box(r[8]), rotorMax: box(r[9]) });
+		}
+		return { records, gpuMs };
 	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at

@@ -434,7 +434,8 @@ int ca3d_ensemble_set_rule_tables_clustered(ca3d_ensemble_t *e, uint32_t first, 
  * objects; CA3D_CONNECT_TORUS is asked for by the caller, never implied by the mode); CA3D_ISOLATE_COPY_RULES and
  * CA3D_COMPOSE_COPY_RULES ignore the boundary of either ensemble.
  * ca3d_ensemble_canon_period steps inside its own kernel with the reference boundary: on an ensemble whose mode is not
- * CA3D_ENSEMBLE_BOUNDARY_REFERENCE it returns CA3D_ERR_UNSUPPORTED and touches nothing. */
+ * CA3D_ENSEMBLE_BOUNDARY_REFERENCE it returns CA3D_ERR_UNSUPPORTED and touches nothing. ca3d_ensemble_envelope steps inside its own
+ * kernel too and honours the source ensemble's mode, all three. */
 enum ca3d_ensemble_boundary
 {
 	CA3D_ENSEMBLE_BOUNDARY_REFERENCE = 0,
@@ -795,6 +796,65 @@ typedef struct ca3d_canon_period
 int ca3d_ensemble_canon_period(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *periods /* [count] */,
                                ca3d_canon_period *out /* [count] */, uint64_t *keys /* [count][keys_stride], may be NULL */,
                                uint32_t keys_stride, float *gpu_ms /* may be NULL */);
+/*
+ * Envelope over a period (no reference counterpart): HOW a universe oscillates — which cells ever live, which always live, which
+ * change, and how much changes a step. One launch of ca_ensemble_envelope_{vn,moore,clustered}64[_torus|_closed]
+ * (csrc/ca_envelope.hip, by the source ensemble's kind and its CURRENT boundary mode, one workgroup a universe) for universes
+ * first .. first + count - 1 of `src`. Universe first + k is followed over periods[k] steps of its own INSIDE the kernel; nothing is
+ * written back to `src`. host.envelope restates it in plain numpy over host.ensemble_step.
+ *
+ * The definition. For universe first + k let P = periods[k], 1 <= P <= CA3D_CANON_MAX_PERIOD, S_0 its current state and S_t what the
+ *   ensemble's own step makes of it after t steps: the universe's rule and the ensemble's current boundary mode (reference, torus or
+ *   closed), exactly as ca3d_ensemble_step does.
+ *   E = S_0 | ... | S_(P-1) is the envelope, A = S_0 & ... & S_(P-1) the stator, E & ~A the rotor.
+ *   heat = sum over t = 0 .. P - 1 of popcount(S_t ^ S_(t+1)); S_P is computed for it. At most 2^18 * 2^12 = 2^30.
+ *   population_sum = sum over t < P of popcount(S_t). envelope_population = popcount(E), stator_population = popcount(A).
+ *   envelope_min / envelope_max and rotor_min / rotor_max are the inclusive bounding boxes of E and of the rotor, x, y, z and a zero
+ *     byte; an empty set has min = max = 0.
+ *   flags bit 0, CA3D_ENVELOPE_RETURNS, is set exactly when S_P equals S_0 WORD FOR WORD: no translation and no digests are involved.
+ *     An oscillator whose period divides P returns; a ship gives its swept volume and no RETURNS.
+ *   period echoes P. The two reserved words are zero.
+ *   The rest follows on the host: rotor_population = envelope_population - stator_population, volatility = rotor / envelope,
+ *   heat / period.
+ *
+ * Images. `flags` selects any subset of CA3D_ENVELOPE_IMAGE_ENVELOPE, _STATOR and _ROTOR. With n images selected, source k writes
+ *   them in bit order (envelope, stator, rotor) into universes dst_first + k * n + i of `dst`, which is `src` itself or a second
+ *   ensemble on the same device: both ping-pong buffers are written and the records rebuilt at step 0, as ca3d_ensemble_isolate
+ *   does. CA3D_ENVELOPE_COPY_RULES copies the source universe's rule words to each of its destinations as CA3D_ISOLATE_COPY_RULES
+ *   does: `src` and `dst` must then be of one kind. The boundary of `dst` is not looked at. With no image bit set `dst` must be NULL.
+ *
+ * Ordering. The launch runs behind what is queued on both ensembles' streams, on the destination's when there is one. `src` is only
+ * read: states, records, step counters, anchors, steps_done and stats are unchanged. It needs a rule on every universe of the range.
+ * The call waits for its own result. gpu_ms (nullable) receives the hipEvent time around the launch. Records and periods are staged in
+ * a device array of the call's own on the handle the launch runs on.
+ *
+ * Errors: NULL `src`, periods or out — CA3D_ERR_INVALID_ARGUMENT without touching a device; `src` (or `dst`) not configured —
+ * CA3D_ERR_NOT_CONFIGURED; count == 0, first + count > n, a period of 0 or above CA3D_CANON_MAX_PERIOD, unknown bits in flags, image
+ * bits without `dst` or `dst` without image bits, destinations past dst's n, a source universe among the destinations of the same
+ * ensemble, different devices — CA3D_ERR_INVALID_ARGUMENT; a universe of the range without a state, or without a rule —
+ * CA3D_ERR_NOT_CONFIGURED, the message names the first such universe; CA3D_ENVELOPE_COPY_RULES across kinds — CA3D_ERR_UNSUPPORTED. A
+ * refused call touches none of the caller's arrays and nothing on the device.
+ */
+#define CA3D_ENVELOPE_RETURNS 1u /* ca3d_envelope.flags bit 0 */
+#define CA3D_ENVELOPE_IMAGE_ENVELOPE 1u
+#define CA3D_ENVELOPE_IMAGE_STATOR 2u
+#define CA3D_ENVELOPE_IMAGE_ROTOR 4u
+#define CA3D_ENVELOPE_COPY_RULES 0x100u
+typedef struct ca3d_envelope
+{
+	uint32_t period;              /* echoed */
+	uint32_t flags;               /* bit 0 CA3D_ENVELOPE_RETURNS */
+	uint32_t heat;                /* cells changed, summed over the P steps */
+	uint32_t population_sum;      /* of S_0 .. S_(P-1) */
+	uint32_t envelope_population;
+	uint32_t stator_population;
+	uint8_t envelope_min[4], envelope_max[4]; /* x, y, z, 0: inclusive; both zero for an empty set */
+	uint8_t rotor_min[4], rotor_max[4];
+	uint32_t reserved[2];         /* zero */
+} ca3d_envelope;                  /* 48 bytes */
+int ca3d_ensemble_envelope(ca3d_ensemble_t *src, uint32_t first, uint32_t count, const uint32_t *periods /* [count] */,
+                           ca3d_ensemble_t *dst /* NULL without images */, uint32_t dst_first, uint32_t flags,
+                           ca3d_envelope *out /* [count] */, float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

@@ -110,6 +110,14 @@ host.canon_period of the CPU oracle's phases in sampled universes, and canon_pha
 the call's everywhere. Reported: medians of --repeats measurements. No ratio is required. Written to
 profiles/ensemble_canon_period_64.json unless --out says otherwise.
 
+--envelope measures the envelope over a period (ca3d_ensemble_envelope, kernel ca_ensemble_envelope_moore64: envelope, stator, rotor
+and heat over a period stepped INSIDE the launch) against the loop it replaces — per phase read_state + step(1), numpy OR / AND and
+popcounts on the host — run on a copy of the same universes in the same process: the nursery of --canon with periods all 4, and B dense
+soups (and_rounds 1, the ash's rule) with periods all 4. For each: the launch's hipEvent time and the host clock around the call; the
+loop's host clock and the summed hipEvent time of its step launches. Before timing, the records must equal host.envelope in sampled
+universes, and every loop's heat, envelope and stator populations must equal the call's everywhere. Reported: medians of --repeats
+measurements. No ratio is required. Written to profiles/ensemble_envelope_64.json unless --out says otherwise.
+
 With --boundary: the plain step kernel of each new boundary mode (Ensemble.set_boundary: "torus", "closed") against the reference
 boundary's kernel on the same universes, for all three kinds (von Neumann, Moore, clustered) at B = 256 and 1024: Ensemble.step(--steps)
 from the same uploaded fills, the modes alternating inside one process, hipEvent times. Before timing, the state of sampled universes
@@ -966,6 +974,92 @@ def canon_period_rows(args):
     return rows
 
 
+def envelope_rows(args):
+    """envelope against the loop it replaces — read_state + step(1) per phase with numpy OR / AND / popcount on the host, run on a copy of
+    the universes in the same process: per B the ash nursery with periods all 4 and B dense soups with period 4. -> rows"""
+    M = 1024
+    born, survive, rounds = CENSUS_ASH["ash B6/S5-7"]
+    tables = tuple(sum(1 << v for v in host.rules_components_to_values(s)) & ((1 << 27) - 1) for s in (born, survive))
+    ens, nursery, copy = Ensemble(0), Ensemble(0), Ensemble(0)
+    rows = []
+    bits = np.array([bin(v).count("1") for v in range(256)], dtype=np.uint8)
+
+    def popcounts(a):
+        """popcount of every row of a [n, words] array, through a table of the 256 bytes"""
+        return bits[np.ascontiguousarray(a).view(np.uint8)].sum(axis=1, dtype=np.uint64)
+
+    def measure(e, n, period, label, B):
+        """One row: envelope over universes 0 .. n - 1 of `e` with one period, verified against host.envelope in a sample, then timed
+        beside the loop on `copy`, which holds the same universes and is uploaded again before every loop."""
+        periods = np.full(n, period, dtype=np.uint32)
+        rec = e.envelope(periods)
+        first = e.read_state()
+        sample = sorted({0, 1, n // 3, n // 2, n - 1} | set(range(min(100, n - 1), min(108, n))))
+        for k in sample:
+            if rec[k].tobytes() != host.envelope(first[k], "moore", tables, period)[0].tobytes():
+                raise SystemExit(f"B {B}, {label}: universe {k} is not host.envelope's")
+        copy.configure(n, neighbourhood="moore")
+        copy.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        gpu, wall, loop_wall, loop_gpu = [], [], [], []
+        for _ in range(args.repeats):
+            e.synchronize()
+            t0 = time.perf_counter()
+            now = e.envelope(periods)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            gpu.append(e.envelope_gpu_ms())
+            if now.tobytes() != rec.tobytes():
+                raise SystemExit(f"B {B}, {label}: two calls differ")
+            copy.upload_state(0, first)
+            copy.synchronize()
+            t0 = time.perf_counter()
+            s_ms = 0.0
+            prev = copy.read_state()
+            env, sta = prev.copy(), prev.copy()
+            heat = np.zeros(n, dtype=np.uint64)
+            for t in range(period):
+                copy.step(1)
+                cur = copy.read_state()
+                s_ms += copy.stats().gpu_ms
+                heat += popcounts(prev ^ cur)
+                if t + 1 < period:
+                    env |= cur
+                    sta &= cur
+                prev = cur
+            loop_wall.append((time.perf_counter() - t0) * 1e3)
+            loop_gpu.append(s_ms)
+            if not (np.array_equal(heat, rec["heat"]) and np.array_equal(popcounts(env), rec["envelope_population"]) and np.array_equal(popcounts(sta), rec["stator_population"])):
+                raise SystemExit(f"B {B}, {label}: the loop found something else than the call")
+        med = statistics.median
+        row = {"workload": label, "universes": B, "envelope_universes": n, "period": period, "verified_against_host_envelope_in": len(sample),
+               "returns": int((rec["flags"] & 1).sum()), "with_a_rotor": int((rec["envelope_population"] > rec["stator_population"]).sum()),
+               "heat_per_step_median": float(np.median(rec["heat"] / period)),
+               "envelope_gpu_ms": med(gpu), "envelope_gpu_ms_all": gpu, "envelope_gpu_us_per_universe": med(gpu) * 1e3 / n,
+               "envelope_wall_ms": med(wall), "envelope_wall_ms_all": wall,
+               "loop_wall_ms": med(loop_wall), "loop_wall_ms_all": loop_wall, "loop_step_gpu_ms_summed": med(loop_gpu),
+               "wall_ratio_loop_over_envelope": med(loop_wall) / med(wall)}
+        rows.append(row)
+        print(json.dumps(row))
+
+    for B in args.universes:
+        ens.configure(B, neighbourhood="moore")
+        ens.set_rule_strings(_capi.ENSEMBLE_ALL, neighbourhood="moore", born=born, survive=survive)
+        ens.seed_states(0, np.arange(1, B + 1), rounds)
+        ens.step_until_cycle(512)
+        comps, n, rest = ens.census(max_components=M)
+        if rest.any():
+            raise SystemExit(f"B {B}: a census of {M} objects a universe is not complete")
+        jobs = np.array([(u, int(c["first_cell"])) for u in range(B) for c in comps[u, :n[u]]], dtype=np.uint32).reshape(-1, 2)
+        J = len(jobs)
+        nursery.configure(J, neighbourhood="moore")
+        nursery.isolate(jobs, 0, ens, "centre", True)
+        measure(nursery, J, 4, "ash B6/S5-7: every object of a census, isolated (centred) into a nursery", B)
+        ens.seed_states(0, np.arange(1, B + 1), 1)
+        measure(ens, B, 4, "soups, and_rounds 1 (65 536 cells, box 64^3), B6/S5-7", B)
+    for e in (ens, nursery, copy):
+        e.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -985,12 +1079,13 @@ def main():
     ap.add_argument("--compose", action="store_true", help="measure compose against the read_state + host.compose + upload_state loop instead (B = 256)")
     ap.add_argument("--canon", action="store_true", help="measure canon against the read_state + host.canon loop instead (B = 256)")
     ap.add_argument("--canon-period", action="store_true", help="measure canon_period against canon_phases instead (B = 256)")
+    ap.add_argument("--envelope", action="store_true", help="measure envelope against the read_state + step(1) loop with numpy OR / AND / popcount instead (B = 256)")
     ap.add_argument("--boundary", action="store_true", help="measure step under the torus and closed boundaries against the reference boundary instead (all three kinds; B = 256 1024)")
     ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose, --canon: destinations / universes the CPU loop is run on")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.census_torus or args.boundary else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period or args.envelope else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.census_torus or args.boundary else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -1038,6 +1133,30 @@ def main():
             "timing": f"hipEvent time around the launch; medians of {args.repeats} measurements, the two connectivities alternating in one process, after both "
                       "censuses equalled host.census byte for byte and every isolated object host.isolate in the sampled universes",
             "rows": census_torus_rows(args),
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
+    if args.envelope:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_envelope_64.json")
+        rows = envelope_rows(args)
+        result = {
+            "what": "B universes of 64^3 of ash (seed_states, seeds 1 .. B, and_rounds 1, Moore B6/S5-7, step_until_cycle(512)), a census at max_components 1024, every "
+                    "object isolated (centred) into a nursery, then ONE Ensemble.envelope call over the nursery with periods all 4 — one launch of "
+                    "ca_ensemble_envelope_moore64, the records copied to the host, no images; and the same call over B dense soups (and_rounds 1) under the same rule "
+                    "— vs. the loop it replaces on a copy of the same universes in the same process: per phase read_state + step(1), numpy OR / AND and byte-table "
+                    "popcounts on the host",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "kernels": {"envelope": "ca_ensemble_envelope_moore64", "loop_step": "ca_ensemble_moore64"},
+            "timing": f"envelope_gpu_ms: hipEvent time around the launch; envelope_wall_ms and loop_wall_ms: host clock around the call and around the loop "
+                      f"(the copy uploaded before it, outside the clock); loop_step_gpu_ms_summed: the hipEvent times of the loop's step launches; medians of "
+                      f"{args.repeats} alternating measurements, after the records equalled host.envelope in the sampled universes; the loop's heat, envelope and "
+                      "stator populations equalled the call's in every universe",
+            "not_measured": "von Neumann and clustered ensembles, the torus and closed kernels, images written to a destination, periods other than 4, larger B",
+            "rows": rows,
         }
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
