@@ -2,7 +2,8 @@
 
 A graded state is dense enough at one end to reach every count a cell can have (a random fill at density 1/2 holds one or two cells
 of a 64^3 grid with 24 or more live neighbours), and the two rule families give every table bit an answer of its own. `class_counts`
-is a plain numpy restatement of the three neighbour classes; test_graded_cpu.py pins it to the oracle."""
+is a plain numpy restatement of the three neighbour classes and `plane_counts` of the two in-plane neighbourhoods; test_graded_cpu.py pins
+both to the oracle."""
 from collections import namedtuple
 
 import numpy as np
@@ -13,9 +14,16 @@ AXES = {"x": 2, "y": 1, "z": 0}  # the axis of a [z, y, x] cell array
 # (axis, reverse) by name: the dense end meets the + face (which wraps) on every axis and, reversed, the dead - face of z
 ORIENTATIONS = {"z": ("z", False), "y": ("y", False), "x": ("x", False), "zr": ("z", True)}
 SEEDS = (501, 502, 503)
-# entries of a table: von Neumann faces, the Moore total, and the clustered classes main (the Moore total), edges, corners
-TABLES = {"vn": 7, "moore": 27, "main": 27, "edges": 13, "corners": 9}
+# entries of a table: von Neumann faces, the Moore total, and the clustered classes main (the Moore total), edges, corners; then the other
+# four main neighbourhoods: the edge and the corner neighbours as the MAIN list, and the two that count in the cell's own plane only
+TABLES = {"vn": 7, "moore": 27, "main": 27, "edges": 13, "corners": 9, "edges main": 13, "corners main": 9, "moore 2D": 9, "vn 2D": 5}
 CLASSES = ("main", "edges", "corners")
+# kinds whose rule is one Rule over a main neighbourhood, sides silent: kind -> (neighbourhood string, key of counts_of)
+PLAIN = {"vn": ("von neumann", "F"), "moore": ("moore", "T"), "edges main": ("edges", "E"), "corners main": ("corners", "C"),
+         "moore 2D": ("moore 2D", "M2"), "vn 2D": ("von neumann 2D", "F2")}
+# kinds whose rule is a (von Neumann main Rule, side Rule) pair: kind -> (side class, key of counts_of)
+MIXED = {"vn+edges": ("edges", "E"), "vn+corners": ("corners", "C")}
+SIZES = {"T": 27, "F": 7, "E": 13, "C": 9, "F2": 5, "M2": 9}  # values a count of counts_of takes
 
 
 def unpack(G, words):
@@ -58,24 +66,53 @@ def _neighbour(cells, d, axis):
     return out
 
 
-def class_counts(G, words):
+def _sum_classes(planes, dtype):
+    """planes[dz + 1]: the cells at z + dz (boundary already applied) -> [own cell, F, E, C, F2, M2]: the shifted copies added up by the
+    number of axes they moved along; F2 / M2 take the dz = 0 copies only."""
+    out = [np.zeros(planes[1].shape, dtype=dtype) for _ in range(6)]
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            sy = _neighbour(planes[dz + 1], dy, 1)
+            for dx in (-1, 0, 1):
+                v = _neighbour(sy, dx, 2)
+                out[abs(dx) + abs(dy) + abs(dz)] += v
+                if dz == 0 and (dx or dy):
+                    out[5] += v
+                    if abs(dx) + abs(dy) == 1:
+                        out[4] += v
+    return out
+
+
+def class_counts(G, words, dtype=np.int32):
     """(F, E, C) per cell, int32 [z, y, x]: live face (0 .. 6), edge (0 .. 12) and corner (0 .. 8) neighbours, from 26 shifted copies,
     each axis applying its own boundary. The Moore total is T = F + E + C."""
     cells = unpack(G, words)
-    out = [np.zeros((G, G, G), dtype=np.int32) for _ in range(4)]
-    for dz in (-1, 0, 1):
-        sz = _neighbour(cells, dz, 0)
-        for dy in (-1, 0, 1):
-            sy = _neighbour(sz, dy, 1)
-            for dx in (-1, 0, 1):
-                out[abs(dx) + abs(dy) + abs(dz)] += _neighbour(sy, dx, 2)
-    return out[1], out[2], out[3]
+    return tuple(_sum_classes([_neighbour(cells, dz, 0) for dz in (-1, 0, 1)], dtype)[1:4])
 
 
-def counts_of(G, words):
-    """dict(F, E, C, T) of class_counts."""
-    F, E, C = class_counts(G, words)
-    return {"F": F, "E": E, "C": C, "T": F + E + C}
+def plane_counts(G, words, dtype=np.int32):
+    """(F2, M2) per cell: live face (0 .. 4) and Moore (0 .. 8) neighbours in the cell's own z plane — the 2D neighbourhoods (rules.cpp:
+    MAIN_VN2D, MAIN_MOORE2D are the von Neumann and Moore lists with dz = 0), x and y applying the same boundary as above."""
+    cells = unpack(G, words)
+    return tuple(_sum_classes([_neighbour(cells, dz, 0) for dz in (-1, 0, 1)], dtype)[4:6])
+
+
+def _as_dict(s):
+    return {"F": s[1], "E": s[2], "C": s[3], "T": s[1] + s[2] + s[3], "F2": s[4], "M2": s[5]}
+
+
+def counts_of(G, words, dtype=np.int32):
+    """dict(F, E, C, T) of class_counts and (F2, M2) of plane_counts."""
+    cells = unpack(G, words)
+    return _as_dict(_sum_classes([_neighbour(cells, dz, 0) for dz in (-1, 0, 1)], dtype))
+
+
+def counts_of_planes(G, words, lo, hi, dtype=np.int32):
+    """(alive, counts_of) of the z planes lo .. hi - 1 alone, 1 <= lo < hi <= G - 1 (no z boundary inside): arrays [hi - lo, y, x]. What a
+    large grid's check needs without 27 full-size copies."""
+    assert 1 <= lo < hi <= G - 1
+    cells = unpack(G, words)
+    return cells[lo:hi], _as_dict(_sum_classes([cells[lo + dz:hi + dz] for dz in (-1, 0, 1)], dtype))
 
 
 def lookup(alive, count, born, survive):
@@ -130,13 +167,23 @@ def coded_all(j):
     return tuple(f[(j + s) % len(f)] for s, f in enumerate(fams))
 
 
+def vn_with(cls, main, side):
+    """(kind, rule) of a von Neumann main rule with one side table firing: the shape of gpu_common's vn_edges_only / vn_corners_only."""
+    assert cls in ("edges", "corners")
+    return "vn+" + cls, (main, side)
+
+
 def strings_of(kind, rule):
-    """The keyword arguments of oracle_lib.Rules.from_strings / set_rule_strings. kind "vn" / "moore": `rule` is a Rule and the sides keep
-    the silent default; kind "clustered": `rule` is a (main, edges, corners) triple of Rules."""
-    if kind == "vn":
-        return dict(neighbourhood="von neumann", born=rule.born_str, survive=rule.survive_str)
-    if kind == "moore":
-        return dict(neighbourhood="moore", born=rule.born_str, survive=rule.survive_str)
+    """The keyword arguments of oracle_lib.Rules.from_strings / set_rule_strings. A PLAIN kind ("vn", "moore", "edges main", ...): `rule` is
+    a Rule over that main neighbourhood and the sides keep the silent default; a MIXED kind ("vn+edges", "vn+corners"): `rule` is a (main,
+    side) pair of Rules; kind "clustered": `rule` is a (main, edges, corners) triple of Rules."""
+    if kind in PLAIN:
+        return dict(neighbourhood=PLAIN[kind][0], born=rule.born_str, survive=rule.survive_str)
+    if kind in MIXED:
+        m, s = rule
+        side = MIXED[kind][0]
+        return {"neighbourhood": "von neumann", "born": m.born_str, "survive": m.survive_str, "born_" + side: s.born_str,
+                "survive_" + side: s.survive_str}
     assert kind == "clustered"
     m, e, c = rule
     return dict(neighbourhood="moore", born=m.born_str, survive=m.survive_str, born_edges=e.born_str, survive_edges=e.survive_str,
@@ -144,29 +191,33 @@ def strings_of(kind, rule):
 
 
 def name_of(kind, rule):
+    if kind in MIXED:
+        return f"vn table: {rule[0].name}; {MIXED[kind][0]} table: {rule[1].name}"
     if kind != "clustered":
         return f"{kind} table: {rule.name}"
     return "clustered " + "; ".join(f"{c} table: {r.name}" for c, r in zip(CLASSES, rule) if r is not SILENT)
 
 
+def next_cells(alive, n, kind, rule):
+    """The next cells (uint8, the shape of `alive`) from the counts `n` (counts_of / counts_of_planes) and the tables alone."""
+    if kind in PLAIN:
+        return lookup(alive, n[PLAIN[kind][1]], rule.born, rule.survive)
+    if kind in MIXED:
+        return lookup(alive, n["F"], rule[0].born, rule[0].survive) | lookup(alive, n[MIXED[kind][1]], rule[1].born, rule[1].survive)
+    assert kind == "clustered"
+    out = np.zeros_like(alive)
+    for r, key in zip(rule, "TEC"):
+        out |= lookup(alive, n[key], r.born, r.survive)
+    return out
+
+
 def next_state(G, words, kind, rule, counts=None):
-    """The next state from class_counts and the tables alone (no oracle)."""
-    alive = unpack(G, words)
-    n = counts_of(G, words) if counts is None else counts
-    if kind == "vn":
-        out = lookup(alive, n["F"], rule.born, rule.survive)
-    elif kind == "moore":
-        out = lookup(alive, n["T"], rule.born, rule.survive)
-    else:
-        out = np.zeros_like(alive)
-        for r, key in zip(rule, "TEC"):
-            out |= lookup(alive, n[key], r.born, r.survive)
-    return pack(G, out)
+    """The next state from class_counts / plane_counts and the tables alone (no oracle)."""
+    return pack(G, next_cells(unpack(G, words), counts_of(G, words) if counts is None else counts, kind, rule))
 
 
 def coverage(G, words, counts=None):
-    """{"T" | "F" | "E" | "C": int64 [2, N]}: how many (alive, count) pairs of each kind the state holds."""
-    alive = unpack(G, words).astype(np.int64)
+    """{"T" | "F" | "E" | "C" | "F2" | "M2": int64 [2, N]}: how many (alive, count) pairs of each kind the state holds."""
+    alive = unpack(G, words).astype(np.int16)
     n = counts_of(G, words) if counts is None else counts
-    sizes = {"T": 27, "F": 7, "E": 13, "C": 9}
-    return {k: np.bincount((alive * sizes[k] + n[k]).ravel(), minlength=2 * sizes[k]).reshape(2, sizes[k]) for k in sizes}
+    return {k: np.bincount((alive * N + n[k]).ravel(), minlength=2 * N).reshape(2, N) for k, N in SIZES.items()}

@@ -8,9 +8,8 @@ import numpy as np
 import pytest
 
 import graded_lib as gl
-import oracle_lib as ol
 from cellularautomatons3d_amd import host
-from gpu_common import set_rules
+from rule_tables_common import differs, engine_case, first_state, form, label, settle, trajectory
 
 pytestmark = pytest.mark.gpu
 
@@ -19,66 +18,6 @@ CELLS = G ** 3
 EXTINCT, STILL, PERIODIC, MOVING = 1, 2, 4, 8
 NB = {"vn": "von neumann", "moore": "moore"}
 KINDS = ["vn", "moore", "main", "edges", "corners"]  # graded_lib.TABLES: the last three are the classes of a clustered rule, one firing
-
-_FIRST, _TRAJ = {}, {}
-
-
-def first_state(g, name):
-    """A start state by name: a graded orientation, "full" or "empty"."""
-    if (g, name) not in _FIRST:
-        if name in gl.ORIENTATIONS:
-            axis, reverse = gl.ORIENTATIONS[name]
-            w = gl.graded_state(g, axis, reverse)
-        else:
-            w = np.full(host.words_per_buffer(g), 0xFFFFFFFF if name == "full" else 0, dtype=np.uint32)
-        _FIRST[g, name] = w
-    return _FIRST[g, name]
-
-
-def form(kind, rule):
-    """(oracle kind, rule) of a table kind: "vn" / "moore" take the Rule as it is, a clustered class fires alone; "all": `rule` is a
-    (main, edges, corners) triple already."""
-    if kind in NB:
-        return kind, rule
-    return "clustered", (rule if kind == "all" else gl.clustered(kind, rule))
-
-
-def trajectory(g, name, kind, rule, steps):
-    """Oracle states 0 .. steps from a named start state under a rule, computed once per module and extended on demand."""
-    k, r = form(kind, rule)
-    kw = gl.strings_of(k, r)
-    t = _TRAJ.setdefault((g, name, tuple(sorted(kw.items()))), [first_state(g, name)])
-    if len(t) <= steps:
-        rules = ol.Rules.from_strings(**kw)
-        while len(t) <= steps:
-            t.append(ol.packed_step(g, t[-1], rules))
-    return t
-
-
-def label(kind, rule, name):
-    k, r = form(kind, rule)
-    return f"{gl.name_of(k, r)}, start {name}"
-
-
-def differs(g, got, want, before, what):
-    """None when got == want, else a line that says which (alive, faces, edges, corners) cells of `before` were answered wrongly."""
-    if np.array_equal(got, want):
-        return None
-    bad = gl.unpack(g, np.asarray(got, dtype=np.uint32) ^ want).astype(bool)
-    n = gl.counts_of(g, before)
-    alive = gl.unpack(g, before)
-    rows = np.stack([alive[bad], n["F"][bad], n["E"][bad], n["C"][bad], n["T"][bad]], axis=1)
-    uniq, cnt = np.unique(rows, axis=0, return_counts=True)
-    z, y, x = (int(v[0]) for v in np.nonzero(bad))
-    return (f"{what}: {int(bad.sum())} cells differ from the oracle, the first at (x, y, z) = ({x}, {y}, {z}); "
-            f"(alive, F, E, C, T) x cells: {[(tuple(int(v) for v in u), int(c)) for u, c in zip(uniq[:8], cnt[:8])]}")
-
-
-def settle(lines):
-    """Fail with every difference found, not the first alone: which bits fail together is what locates a fault."""
-    lines = [m for m in lines if m]
-    if lines:
-        pytest.fail(f"{len(lines)} cases differ:\n" + "\n".join(lines[:60]), pytrace=False)
 
 
 @pytest.fixture()
@@ -302,24 +241,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def engine_case(eng, g, kind, rule, name, modes):
-    """One step, then a second (the engine's ping-pong buffers) under every mode, against the oracle -> the differences found."""
-    lines = []
-    t = trajectory(g, name, kind, rule, 2)
-    k, r = form(kind, rule)
-    rules = ol.Rules.from_strings(**gl.strings_of(k, r))
-    for jit, variant in modes:
-        eng.set_option("jit", jit)
-        eng.set_option("variant", variant)
-        set_rules(eng, rules)
-        eng.upload_state(t[0])
-        for step in (1, 2):
-            eng.step(1)
-            lines.append(differs(g, eng.read_state(), t[step], t[step - 1],
-                                 f"{label(kind, rule, name)} at {g}^3, step {step}, jit={jit} variant={variant} {eng.info().kernel_name}"))
-    return lines
 
 
 def restore(eng):

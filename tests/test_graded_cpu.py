@@ -1,11 +1,14 @@
 """graded_lib without a GPU: the graded states reach every (alive, count) pair of every table often enough for a wrong leaf or a wrong
-carry to show, and class_counts — the plain numpy restatement of the three neighbour classes — gives the oracle's next state under rules
-that answer any two counts differently. Run with -s for the coverage figures."""
+carry to show, and class_counts / plane_counts — the plain numpy restatement of the three neighbour classes and of the two in-plane
+neighbourhoods — give the oracle's next state under rules that answer any two counts differently. The families of
+test_gpu_rule_tables_forms.py decide something on every start state it uses, and its short family sees a count that lost one of its top
+planes. Run with -s for the coverage figures."""
 import numpy as np
 import pytest
 
 import graded_lib as gl
 import oracle_lib as ol
+import rule_tables_common as rc
 
 FLOOR = 32  # occurrences of every (alive, count) pair, whatever the orientation and the grid
 
@@ -80,7 +83,7 @@ def test_the_classes_occur_in_combination():
 
 
 def test_the_rule_families():
-    for N in (7, 27, 13, 9):
+    for N in (7, 27, 13, 9, 5):
         hot, cod = gl.one_hot(N), gl.coded(N)
         assert len(hot) == 2 * N and len(cod) == 2 * gl.coded_bits(N) and 1 << gl.coded_bits(N) >= N > 1 << (gl.coded_bits(N) - 1)
         assert sorted(r.born for r in hot if r.born) == sorted(r.survive for r in hot if r.survive) == [1 << k for k in range(N)]
@@ -103,7 +106,7 @@ def test_the_rule_families():
 def rules_of(kind):
     """(oracle kind, rule) list: the coded rules of a table; a clustered class fires alone."""
     fam = gl.coded(gl.TABLES[kind])
-    return [(kind, r) for r in fam] if kind in ("vn", "moore") else [("clustered", gl.clustered(kind, r)) for r in fam]
+    return [(kind, r) for r in fam] if kind in gl.PLAIN else [("clustered", gl.clustered(kind, r)) for r in fam]
 
 
 def pin(G, name, kind, rule):
@@ -128,7 +131,7 @@ def test_the_lowest_and_highest_bit_of_every_table(kind):
     N = gl.TABLES[kind]
     hot = gl.one_hot(N)
     for r in (hot[0], hot[N - 1], hot[N], hot[2 * N - 1]):
-        if kind in ("vn", "moore"):
+        if kind in gl.PLAIN:
             pin(64, "z", kind, r)
         else:
             pin(64, "z", "clustered", gl.clustered(kind, r))
@@ -137,3 +140,132 @@ def test_the_lowest_and_highest_bit_of_every_table(kind):
 def test_all_three_classes_at_once():
     for j in (0, 7):
         pin(64, "x", "clustered", gl.coded_all(j))
+
+
+# ------------------------------------------------------------------------------------------------ the kinds and grids of test_gpu_rule_tables_forms.py
+
+NEW_PLAIN = ["edges main", "corners main", "moore 2D", "vn 2D"]
+
+
+def test_the_plane_counts_by_hand():
+    """F2 / M2 on a state small enough to count by eye: a plus and a far corner cell in plane 3 of a 32^3 grid, nothing else."""
+    G = 32
+    cells = np.zeros((G, G, G), dtype=np.uint8)
+    for y, x in ((5, 5), (4, 5), (6, 5), (5, 4), (5, 6), (31, 31)):
+        cells[3, y, x] = 1
+    n = gl.counts_of(G, gl.pack(G, cells))
+    assert (n["F2"][3, 5, 5], n["M2"][3, 5, 5]) == (4, 4) and (n["F2"][3, 4, 4], n["M2"][3, 4, 4]) == (2, 3)
+    assert not n["F2"][2].any() and not n["M2"][4].any() and n["F"][2, 5, 5] == 1  # the planes above and below see it through F only
+    # (31, 31) is the + neighbour of x = 30 / y = 30 and, wrapped, of nobody's - side: coordinate -1 is dead, coordinate G wraps to 0
+    assert n["M2"][3, 30, 30] == 1 and n["F2"][3, 30, 31] == 1 and n["M2"][3, 0, 0] == 0 and n["M2"][3, 31, 31] == 0
+    cells[3, 0, 0] = 1
+    n = gl.counts_of(G, gl.pack(G, cells))
+    assert n["M2"][3, 31, 31] == 1 and n["F2"][3, 31, 0] == 1 and n["M2"][3, 0, 0] == 0
+    F2, M2 = gl.plane_counts(G, gl.pack(G, cells))
+    np.testing.assert_array_equal(F2, n["F2"])
+    np.testing.assert_array_equal(M2, n["M2"])
+
+
+@pytest.mark.parametrize("G,name", [(32, n) for n in gl.ORIENTATIONS] + [(64, "z"), (64, "x")])
+@pytest.mark.parametrize("kind", NEW_PLAIN)
+def test_the_new_main_tables_give_the_oracles_next_state(kind, G, name):
+    """One one-hot rule per table entry (a count off by one, or taken from another neighbourhood, answers for the wrong entry) and the
+    coded family, at 32^3 and 64^3."""
+    N = gl.TABLES[kind]
+    for r in gl.one_hot(N) + gl.coded(N):
+        pin(G, name, kind, r)
+
+
+@pytest.mark.parametrize("G,name", [(32, n) for n in gl.ORIENTATIONS] + [(64, "z"), (64, "x")])
+@pytest.mark.parametrize("cls", ["edges", "corners"])
+def test_a_von_neumann_main_with_one_side_table(cls, G, name):
+    """The mixed kinds: the side table one-hot and coded under the sparse main rule, and coded under a coded main."""
+    N = gl.TABLES[cls]
+    for side in gl.one_hot(N) + gl.coded(N):
+        pin(G, name, *gl.vn_with(cls, rc.VN_MAIN, side))
+    for j, side in enumerate(gl.coded(N)):
+        pin(G, name, *gl.vn_with(cls, gl.coded(7)[j % 6], side))
+
+
+def test_counts_of_a_plane_range():
+    G, st = 64, state(64, "x")
+    alive, n = gl.counts_of_planes(G, st, 5, 40, dtype=np.int8)
+    np.testing.assert_array_equal(alive, gl.unpack(G, st)[5:40])
+    for k, v in counts(G, "x").items():
+        np.testing.assert_array_equal(n[k], v[5:40], err_msg=k)
+
+
+@pytest.mark.parametrize("G,floor", [(32, 8), (96, 32), (256, 32), (384, 32)])
+def test_every_count_occurs_at_the_grids_of_the_kernel_forms(G, floor):
+    """What test_gpu_rule_tables_forms.py rests on: every (alive, count) pair of every table — the two in-plane counts included — at least
+    32 times on every orientation at 96, 256 and 384, and at least 8 times at 32 (one graded axis is enough there too). At 256 and 384
+    the pairs are counted on a part of the planes only — 64 planes of a state graded along y or x, 12 planes around each of the eight
+    density steps of one graded along z: what occurs there occurs in the grid, so the bound holds for the grid all the more."""
+    for name, (axis, reverse) in gl.ORIENTATIONS.items():
+        st = gl.graded_state(G, axis, reverse)
+        if G < 256:
+            cov = gl.coverage(G, st, gl.counts_of(G, st, dtype=np.int8))
+        else:
+            steps = [-(-k * G // 9) for k in range(1, 9)] if axis == "z" else []  # the first plane of each denser block ("zr": mirrored)
+            ranges = [(max(b - 6, 1), min(b + 6, G - 1)) for b in steps] or [(G // 2, G // 2 + 64)]
+            if reverse:
+                ranges = [(G - hi, G - lo) for lo, hi in ranges]
+            cov = {k: np.zeros((2, N), dtype=np.int64) for k, N in gl.SIZES.items()}
+            for lo, hi in ranges:
+                alive, n = gl.counts_of_planes(G, st, lo, hi, dtype=np.int8)
+                for k, N in gl.SIZES.items():
+                    cov[k] += np.bincount((alive.astype(np.int16) * N + n[k]).ravel(), minlength=2 * N).reshape(2, N)
+        print(f"graded {name} at {G}^3: smallest number of occurrences of an (alive, count) pair", {k: int(v.min()) for k, v in cov.items()})
+        for k, v in cov.items():
+            assert v.min() >= floor, f"{k}: (alive, count) pair {np.unravel_index(v.argmin(), v.shape)} occurs {v.min()} times in graded {name} at {G}"
+
+
+def slab_of(G, name):
+    """Up to 16 inner planes of a graded state that hold its dense end: across the step from density 7/8 to 1 where z is the graded axis."""
+    if name not in ("z", "zr"):
+        return G // 2, min(G // 2 + 16, G - 1)
+    edge = -(-8 * G // 9)  # the first full plane of "z"
+    lo, hi = edge - 8, min(edge + 8, G - 1)
+    return (lo, hi) if name == "z" else (G - hi, G - lo)
+
+
+LOST_PLANES = {"T": (4, 3), "E": (3, 2), "C": (3, 2), "M2": (3, 2), "F2": (2, 1)}  # the two top planes of each count
+KEY_OF = {"moore": "T", "edges main": "E", "corners main": "C", "moore 2D": "M2", "vn 2D": "F2"}
+
+
+@pytest.mark.parametrize("G", sorted(rc.FORM_STARTS))
+def test_the_short_family_sees_a_lost_top_plane(G):
+    """Sensitivity without a kernel: on every start state the GPU file uses, a count that lost one of its two top planes (a dropped carry)
+    makes at least one rule of the family that runs there differ from the oracle — and the intact counts do not. On a plane range of
+    the dense end (the counts of a whole 768^3 state are not needed to show it)."""
+    family = rc.FLAT_TOP if G == 768 else rc.SHORT
+    for name in rc.FORM_STARTS[G]:
+        st = state(G, name) if G <= 128 else gl.graded_state(G, *gl.ORIENTATIONS[name])
+        lo, hi = slab_of(G, name)
+        alive, n = gl.counts_of_planes(G, st, lo, hi, dtype=np.int8)
+        want = {}
+
+        def notices(c, broken):
+            """The rule answers the broken counts differently from the oracle (and the intact ones as the oracle does)."""
+            if c.id not in want:
+                want[c.id] = gl.unpack(G, ol.packed_step(G, st, rc.rules_of(c.kind, c.rule)))[lo:hi]
+                np.testing.assert_array_equal(gl.next_cells(alive, n, c.kind, c.rule), want[c.id], err_msg=f"{c.id} on graded {name} at {G}")
+            return bool((gl.next_cells(alive, broken, c.kind, c.rule) != want[c.id]).any())
+
+        for key in sorted({KEY_OF[c.kind] for c in family if c.kind in KEY_OF}):
+            for plane in LOST_PLANES[key]:
+                broken = dict(n)
+                broken[key] = n[key] & ~np.int8(1 << plane)
+                assert (broken[key] != n[key]).any()
+                rules = sorted((c for c in family if KEY_OF.get(c.kind) == key), key=lambda c: f"bit{plane}-" not in c.id)  # that bit's rules first
+                assert any(notices(c, broken) for c in rules), f"no rule notices plane {plane} of {key} missing on graded {name} at {G}"
+
+
+@pytest.mark.parametrize("G", [32, 64, 96])
+def test_the_families_decide_something(G):
+    """Every rule of the GPU file's families changes the graded state and leaves it non-empty (asserted again where the oracle states are
+    made on the larger grids)."""
+    for c in rc.FULL + rc.FLAT:
+        for name in rc.starts(c):
+            nxt = ol.packed_step(G, state(G, name), rc.rules_of(c.kind, c.rule))
+            assert nxt.any() and (nxt != state(G, name)).any(), (c.id, name, G)
