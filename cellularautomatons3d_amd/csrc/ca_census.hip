@@ -5,9 +5,11 @@
 // waits on other workgroups, no atomics) are ca_flood.inc's. R[4][2] holds the cells no listed component has taken yet, F[4][2] the
 // component being filled.
 //
-// The row loads, the seed and the flood loop are WRITTEN OUT below, not called: they are ca_flood.inc's load_universe, seed_cell and
-// flood (its closed form, Torus = false), line for line, and a change to one is a change to the other. Called, they compute the same with the same instructions, but the
-// compiler allocates this kernel's registers differently and the census measured 1.3 to 4.5 % slower on an MI355X.
+// The row loads, the seed and the flood loop are TEXT in this kernel, not calls. Called, ca_flood.inc's load_universe, seed_cell and
+// flood compute the same, but the compiler allocates this kernel's registers differently and the census measured 1.3 to 4.5 % slower on
+// an MI355X. The flood loop, the long one, exists once all the same: it is the fragment ca_flood_loop.inc, flood's
+// body, included below under Torus = false, and the kernel's listing is the measured one line for line. The six lines of load_universe
+// and the seven of seed_cell stay written out: even one of them as a call moves this listing (21 and 24 lines of it).
 //
 // One round of the loop: SEED (the lowest live cell of R in the order z, y, x: thread -> wave -> LDS -> workgroup), FLOOD, RECORD
 // (population and box, then — the box known — the digest of the component translated to the origin; thread 0 stores the 32 bytes),
@@ -87,57 +89,11 @@ __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_census64(CensusArgs a
 				for (u32 h = 0; h < 2u; h++) F[p][h] = own && p == (sz & 3u) && h == (sx >> 5) ? 1u << (sx & 31u) : 0u;
 		}
 
-		// ---- flood (flood): F <- R & dilate(F) until an iteration changes nothing anywhere. Iteration k carries the waves' "changed in
+		// ---- flood (flood's body, the closed form): F <- R & dilate(F) until an iteration changes nothing anywhere. Iteration k carries the waves' "changed in
 		// iteration k - 1" bits in the exchange buffer of its parity, so the barrier of the exchange is the barrier of the test.
-		u32 changed = 1u; // wave-uniform
-		for (u32 it = 0;; it++)
 		{
-			const u32 buf = it & 1u;
-			u32 Y[kPT][2]; // x and y of the dilation
-#pragma unroll
-			for (u32 p = 0; p < kPT; p++)
-#pragma unroll
-				for (u32 h = 0; h < 2u; h++)
-				{
-					const u32 w = F[p][h], other = F[p][h ^ 1u];
-					const u32 l = from_left(w, h ? other : 0u);  // cell x - 1: word 0's comes from nowhere, word 1's from word 0
-					const u32 r = from_right(h ? 0u : other, w); // cell x + 1: word 0's from word 1, word 1's from nowhere (closed: no wrap)
-					const u32 x = w | l | r;
-					// row y - 1 (zero into row 0), row y + 1 (zero into row 63: wave_shl, not the step's wave_rol)
-					Y[p][h] = x | dpp_mov<kDppWaveShr1>(x) | dpp_mov<kDppWaveShl1>(x);
-				}
-			xch[slot(buf, wave, 0u, 0u, row)] = Y[0][0];
-			xch[slot(buf, wave, 0u, 1u, row)] = Y[0][1];
-			xch[slot(buf, wave, 1u, 0u, row)] = Y[kPT - 1][0];
-			xch[slot(buf, wave, 1u, 1u, row)] = Y[kPT - 1][1];
-			if (row == 0u) flg[buf * kWaves + wave] = changed;
-			// (a wave writes this parity's buffer again two iterations on, behind the next iteration's barrier, which no wave passes
-			// before it has read this one's)
-			__syncthreads();
-			const uint4 *f4 = reinterpret_cast<const uint4 *>(flg + buf * kWaves);
-			uint4 m = f4[0];
-#pragma unroll
-			for (u32 i = 1; i < kWaves / 4u; i++) { const uint4 v = f4[i]; m.x |= v.x; m.y |= v.y; m.z |= v.z; m.w |= v.w; }
-			if (__builtin_amdgcn_readfirstlane((int)(m.x | m.y | m.z | m.w)) == 0) break; // from LDS behind the barrier: workgroup-uniform
-			u32 below[2], above[2];
-#pragma unroll
-			for (u32 h = 0; h < 2u; h++)
-			{
-				below[h] = wave ? xch[slot(buf, wave - 1u, 1u, h, row)] : 0u;                        // z == -1: closed
-				above[h] = wave + 1u < kWaves ? xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)] : 0u; // z == 64: closed (the step wraps here)
-			}
-			u32 ch = 0;
-#pragma unroll
-			for (u32 p = 0; p < kPT; p++)
-#pragma unroll
-				for (u32 h = 0; h < 2u; h++)
-				{
-					const u32 z = Y[p][h] | (p ? Y[p ? p - 1u : 0u][h] : below[h]) | (p + 1u < kPT ? Y[p + 1u < kPT ? p + 1u : p][h] : above[h]);
-					const u32 f = R[p][h] & z; // F is part of R and of its own dilation: f holds F
-					ch |= f ^ F[p][h];
-					F[p][h] = f;
-				}
-			changed = __ballot(ch != 0u) ? 1u : 0u;
+			constexpr bool Torus = false;
+#include "ca_flood_loop.inc"
 		}
 
 		// ---- record: population and box first (F holds its seed: nothing below is taken of an empty word pair) ...

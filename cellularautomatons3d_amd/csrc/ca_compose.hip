@@ -18,10 +18,12 @@
 //    of the turned box only, so a small object costs a few reads a row.
 // The image is two planes of words, [word][z][y] with 65 words a plane of rows: lanes that run along the piece's y are 1 word apart,
 // lanes that run along its z 65 — both reach 32 different banks; with the natural [z][y][2] they would be 128 words apart, one bank.
+// Its constants, the permutation tables and uni, pick and shifted are ca_turn_image.inc's, shared with the canon kernels.
 //
-// ca_canon.hip carries the image, the map and the row assembly written out, with at = 0: as an include shared by both
-// kernels the text changed this kernel's register allocation and instruction count, so it stays here as it was
-// measured: change that text with this one. ca_canon_period.hip carries ca_canon.hip's copy once more: that one too.
+// THE MAP AND THE ROW ASSEMBLY BELOW ARE THIS KERNEL'S OWN. The canon kernels' (ca_canon_pass.inc) are the case at = 0, where the
+// intervals are [0, e'[i] - 1] and nothing is clipped; here every axis is clipped by `at` (lo and hi, rows and planes clamped into
+// them), and the result is ORed into A, not digested. That is another text, not a copy: as functions shared by both kernels the common
+// pieces changed this kernel's register allocation and instruction count, so each keeps its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,6 +36,7 @@ namespace
 #include "ca_bitops.inc"
 #include "ca_wave_ops.inc"
 #include "ca_flood.inc"
+#include "ca_turn_image.inc"
 
 struct ComposeArgs
 {
@@ -46,18 +49,6 @@ struct ComposeArgs
 	ca3d_composed *out;              // [n_dst]
 	u32 dst_first, over, rule_words; // rule_words 0: rules stay
 };
-
-constexpr u32 kImgPlane = 65u;                 // words from one plane of rows to the next: odd, so lanes along z spread over the banks
-constexpr u32 kImgHalf = 64u * kImgPlane;      // words of one of the two word planes
-constexpr u32 kImgWords = 2u * kImgHalf;       // 33 280 B
-constexpr u32 kPerm0 = 0u | 0u << 2 | 1u << 4 | 1u << 6 | 2u << 8 | 2u << 10; // PERMS[m][i], two bits an m
-constexpr u32 kPerm1 = 1u | 2u << 2 | 0u << 4 | 2u << 6 | 0u << 8 | 1u << 10;
-constexpr u32 kPerm2 = 2u | 1u << 2 | 2u << 4 | 0u << 6 | 1u << 8 | 0u << 10;
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int pick(u32 j, int a, int b, int c) { return j == 0u ? a : j == 1u ? b : c; }
-// v shifted left by t (right by -t), zero from |t| >= 64 on
-__device__ __forceinline__ u64 shifted(u64 v, int t) { return t >= 64 || t <= -64 ? 0ull : t >= 0 ? v << (u32)t : v >> (u32)-t; }
 
 __global__ __launch_bounds__(kThreads, 4) void ca_ensemble_compose64(ComposeArgs a)
 {

@@ -1,8 +1,9 @@
 // The step policies of the ensemble kernels: one step of a 64^3 universe held in eight registers a thread (lane = row y, wave w = planes
 // 4 w .. 4 w + 3, a row's two words in one thread), with the rule as data. A policy (VnStep, MooreStep, ClusteredStep) owns the rule's
-// registers (`load`), the size of its LDS exchange (`kXchWords`, two step parities) and one step (`step`, ONE barrier, reached by all
-// 1024 threads). Shared by ca_ensemble.hip and ca_ensemble_boundary.hip (through ca_ensemble_run.inc) and ca_canon_period.hip. Device
-// code only; include inside namespace ca3d { namespace { ... } }, after ca_bitops.inc, with u32, kWaves and kPT defined.
+// registers (`load`), the words of a universe's rule (`kRuleWords`, checked against the host's ensemble_rule_words()), the size of its
+// LDS exchange (`kXchWords`, two step parities) and one step (`step`, ONE barrier, reached by all 1024 threads). Shared by ca_ensemble.hip
+// and ca_ensemble_boundary.hip (through ca_ensemble_run.inc), ca_canon_period.hip and ca_envelope.hip. Device code only; include inside
+// namespace ca3d { namespace { ... } }, after ca3d_internal.h and ca_bitops.inc, with u32, kWaves and kPT defined.
 //
 // A policy is a template over the universe's BOUNDARY (include/ca3d.h, ca3d_ensemble_set_boundary), which sits in three places of a step:
 // the operand that enters a row's end word (x), the DPP control that brings the neighbouring row (y), the exchange slot that brings the
@@ -51,6 +52,8 @@ template <int B>
 struct VnStepT
 {
 	static constexpr u32 kXchWords = 2u * kWaves * 2u * 2u * 64u; // [step parity][wave][first / last plane][word][row]: 32 KiB
+	static constexpr u32 kRuleWords = 1u; // a universe's rule in the ensemble's rule array, as `load` indexes it
+	static_assert(kRuleWords == ensemble_rule_words(CA3D_ENSEMBLE_VON_NEUMANN), "the host's rule array and the policy agree");
 	// leaf[c] = all-ones where a DEAD cell with c live neighbours is born, leaf[7 + c] where a LIVE one survives
 	u32 leaf[14];
 
@@ -125,6 +128,8 @@ template <int B>
 struct MooreStepT
 {
 	static constexpr u32 kXchWords = 2u * kWaves * 2u * 2u * 64u * 4u; // [step parity][wave][first / last plane][word][row][sum plane]: 128 KiB
+	static constexpr u32 kRuleWords = 2u;
+	static_assert(kRuleWords == ensemble_rule_words(CA3D_ENSEMBLE_MOORE), "the host's rule array and the policy agree");
 	// The update is a multiplexer tree over (alive, T4 .. T0) with 28 + 28 workgroup-uniform leaves. A select reads ONE scalar operand, so
 	// the born leaves live in vector registers and the (shifted) survive leaves in scalar ones: the leaf level is 28 selects on the
 	// alive word with one operand of each kind.
@@ -250,6 +255,8 @@ template <int B>
 struct ClusteredStepT
 {
 	static constexpr u32 kXchWords = VnStep::kXchWords;
+	static constexpr u32 kRuleWords = 6u;
+	static_assert(kRuleWords == ensemble_rule_words(CA3D_ENSEMBLE_MOORE, true), "the host's rule array and the policy agree");
 	// all-zeros / all-ones per table bit: the born leaves in vector registers, the survive leaves in scalar ones (a select reads ONE scalar)
 	u32 bornM[27], survM[27], bornE[13], survE[13], bornC[9], survC[9];
 

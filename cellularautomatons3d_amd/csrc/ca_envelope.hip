@@ -75,7 +75,7 @@ __device__ __forceinline__ uint2 box_of(const Extent &e)
 	                  (63u - (u32)__builtin_clzll(xm)) | (63u - (u32)__builtin_clzll(e.ym)) << 8 | (63u - (u32)__builtin_clzll(e.zm)) << 16);
 }
 
-template <typename Step, u32 RuleWords, bool InRegisters>
+template <typename Step, bool InRegisters>
 __device__ __forceinline__ void envelope_run(const EnvelopeArgs &a)
 {
 	constexpr u32 kAccBytes = InRegisters ? 0u : kAccWords * kThreads * 4u;
@@ -221,10 +221,10 @@ __device__ __forceinline__ void envelope_run(const EnvelopeArgs &a)
 		}
 		if (tid == 0u)
 		{
-			const u32 *rs = a.rules + (size_t)u * RuleWords;
-			u32 *rd = a.dst_rules + (size_t)slot * RuleWords;
+			const u32 *rs = a.rules + (size_t)u * Step::kRuleWords;
+			u32 *rd = a.dst_rules + (size_t)slot * Step::kRuleWords;
 #pragma nounroll
-			for (u32 i = 0; i < a.rule_words; i++) rd[i] = rs[i]; // rule_words is 0 or RuleWords
+			for (u32 i = 0; i < a.rule_words; i++) rd[i] = rs[i]; // rule_words is 0 or Step::kRuleWords
 		}
 		slot++;
 	};
@@ -234,13 +234,13 @@ __device__ __forceinline__ void envelope_run(const EnvelopeArgs &a)
 }
 
 // a kind's kernels under the three boundaries; four waves per SIMD as in ca_ensemble.hip
-#define CA3D_ENVELOPE_KERNELS(kind, StepT, words, regs)                                                                                                              \
-	__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_envelope_##kind##64(EnvelopeArgs a) { envelope_run<StepT<kBoundaryReference>, words, regs>(a); }      \
-	__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_envelope_##kind##64_torus(EnvelopeArgs a) { envelope_run<StepT<kBoundaryTorus>, words, regs>(a); }    \
-	__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_envelope_##kind##64_closed(EnvelopeArgs a) { envelope_run<StepT<kBoundaryClosed>, words, regs>(a); }
-CA3D_ENVELOPE_KERNELS(vn, VnStepT, 1u, true)
-CA3D_ENVELOPE_KERNELS(moore, MooreStepT, 2u, false)
-CA3D_ENVELOPE_KERNELS(clustered, ClusteredStepT, 6u, false)
+#define CA3D_ENVELOPE_KERNELS(kind, StepT, regs)                                                                                                              \
+	__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_envelope_##kind##64(EnvelopeArgs a) { envelope_run<StepT<kBoundaryReference>, regs>(a); }      \
+	__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_envelope_##kind##64_torus(EnvelopeArgs a) { envelope_run<StepT<kBoundaryTorus>, regs>(a); }    \
+	__global__ __launch_bounds__(kThreads, 4) void ca_ensemble_envelope_##kind##64_closed(EnvelopeArgs a) { envelope_run<StepT<kBoundaryClosed>, regs>(a); }
+CA3D_ENVELOPE_KERNELS(vn, VnStepT, true)
+CA3D_ENVELOPE_KERNELS(moore, MooreStepT, false)
+CA3D_ENVELOPE_KERNELS(clustered, ClusteredStepT, false)
 #undef CA3D_ENVELOPE_KERNELS
 
 } // namespace

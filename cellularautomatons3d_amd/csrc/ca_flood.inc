@@ -19,8 +19,9 @@
 //  - an iteration that does not end a flood adds a cell: a flood takes population + 1 iterations at most, population + 2 (that is, 2)
 //    from an empty seed, whose iteration 0 changes nothing and whose iteration 1 reads that;
 //  - no waits on other workgroups, no spins, no atomics, nothing but vector stores.
-// ca_isolate.hip calls everything here. ca_census.hip calls extent and carries the text of load_universe, seed_cell and flood written
-// out, because the called form measured slower there (its header, DESIGN.md 12.7): change that text with this one.
+// ca_isolate.hip calls everything here. ca_census.hip calls extent, and takes the flood as text, not as a call, because the called form
+// measured slower there (its header, DESIGN.md 12.7): the loop is ca_flood_loop.inc, a fragment that is flood's whole body here and is
+// included once more in the census kernel.
 // The LDS arrays are declared by the kernels (kXchWords, kFlgWords, kPartWords) and passed in: a kernel's LDS stays visible in one place.
 #pragma once
 
@@ -61,59 +62,11 @@ __device__ __forceinline__ void seed_cell(u32 (&F)[kPT][2], u32 cell, u32 wave, 
 // barrier of the test: ONE barrier an iteration. xch and flg are dead on return: the iteration that ends the flood reads none of xch,
 // and every wave has passed that iteration's barrier only after all had finished the reads of the one before.
 // Torus: every face joins the opposite one (see the head of this file); the closed form is flood(...), the default.
+// The body is the fragment ca_flood_loop.inc (its head has the contract): the parameters here are the names it reads.
 template <bool Torus = false>
 __device__ __forceinline__ void flood(const u32 (&R)[kPT][2], u32 (&F)[kPT][2], u32 *xch, u32 *flg, u32 wave, u32 row)
 {
-	u32 changed = 1u; // wave-uniform
-	for (u32 it = 0;; it++)
-	{
-		const u32 buf = it & 1u;
-		u32 Y[kPT][2]; // x and y of the dilation
-#pragma unroll
-		for (u32 p = 0; p < kPT; p++)
-#pragma unroll
-			for (u32 h = 0; h < 2u; h++)
-			{
-				const u32 w = F[p][h], other = F[p][h ^ 1u];
-				const u32 l = from_left(w, Torus || h ? other : 0u);  // cell x - 1: word 0's comes from nowhere, word 1's from word 0
-				const u32 r = from_right(Torus || !h ? other : 0u, w); // cell x + 1: word 0's from word 1, word 1's from nowhere (closed: no wrap)
-				const u32 x = w | l | r;
-				// row y - 1 (zero into row 0), row y + 1 (zero into row 63: wave_shl, not the step's wave_rol); the torus rotates
-				Y[p][h] = x | dpp_mov<Torus ? kDppWaveRor1 : kDppWaveShr1>(x) | dpp_mov<Torus ? kDppWaveRol1 : kDppWaveShl1>(x);
-			}
-		xch[slot(buf, wave, 0u, 0u, row)] = Y[0][0];
-		xch[slot(buf, wave, 0u, 1u, row)] = Y[0][1];
-		xch[slot(buf, wave, 1u, 0u, row)] = Y[kPT - 1][0];
-		xch[slot(buf, wave, 1u, 1u, row)] = Y[kPT - 1][1];
-		if (row == 0u) flg[buf * kWaves + wave] = changed;
-		// (a wave writes this parity's buffer again two iterations on, behind the next iteration's barrier, which no wave passes
-		// before it has read this one's)
-		__syncthreads();
-		const uint4 *f4 = reinterpret_cast<const uint4 *>(flg + buf * kWaves);
-		uint4 m = f4[0];
-#pragma unroll
-		for (u32 i = 1; i < kWaves / 4u; i++) { const uint4 v = f4[i]; m.x |= v.x; m.y |= v.y; m.z |= v.z; m.w |= v.w; }
-		if (__builtin_amdgcn_readfirstlane((int)(m.x | m.y | m.z | m.w)) == 0) break; // from LDS behind the barrier: workgroup-uniform
-		u32 below[2], above[2];
-#pragma unroll
-		for (u32 h = 0; h < 2u; h++)
-		{
-			below[h] = Torus || wave ? xch[slot(buf, Torus ? (wave - 1u) & (kWaves - 1u) : wave - 1u, 1u, h, row)] : 0u; // z == -1: closed
-			above[h] = Torus || wave + 1u < kWaves ? xch[slot(buf, (wave + 1u) & (kWaves - 1u), 0u, h, row)] : 0u; // z == 64: closed (the step wraps here)
-		}
-		u32 ch = 0;
-#pragma unroll
-		for (u32 p = 0; p < kPT; p++)
-#pragma unroll
-			for (u32 h = 0; h < 2u; h++)
-			{
-				const u32 z = Y[p][h] | (p ? Y[p ? p - 1u : 0u][h] : below[h]) | (p + 1u < kPT ? Y[p + 1u < kPT ? p + 1u : p][h] : above[h]);
-				const u32 f = R[p][h] & z; // F is part of R and of its own dilation: f holds F
-				ch |= f ^ F[p][h];
-				F[p][h] = f;
-			}
-		changed = __ballot(ch != 0u) ? 1u : 0u;
-	}
+#include "ca_flood_loop.inc"
 }
 
 // Population and extent of F, workgroup-uniform: x0 / x1 the OR of every row's word 0 / 1, bit y of ym and bit z of zm set where that
