@@ -113,6 +113,18 @@ class EnvelopeStruct(C.Structure):
 
 #: the one flag bit of `ca3d_ensemble_envelope` beside its image bits (`host.ENVELOPE_IMAGES`)
 ENVELOPE_COPY_RULES = 0x100
+
+
+class DamageStruct(C.Structure):
+    """ca3d_damage (include/ca3d.h): what `ca3d_ensemble_damage` says of one universe, 48 bytes (`host.DAMAGE_DTYPE`)."""
+    _fields_ = [("steps", C.c_uint32), ("flags", C.c_uint32), ("healed_at", C.c_uint32), ("final_distance", C.c_uint32),
+                ("initial_distance", C.c_uint32), ("max_distance", C.c_uint32), ("max_at", C.c_uint32), ("distance_sum", C.c_uint32),
+                ("damage_min", C.c_uint8 * 4), ("damage_max", C.c_uint8 * 4), ("touched_min", C.c_uint8 * 4), ("touched_max", C.c_uint8 * 4)]
+
+
+#: the flag bits of `ca3d_ensemble_damage`
+DAMAGE_IMAGE_DAMAGE = 0x1
+DAMAGE_COPY_RULES = 0x100
 #: the flag bits of `ca3d_ensemble_compose`, and the most parts a call takes
 COMPOSE_OVER = 0x1
 COMPOSE_COPY_RULES = 0x100
@@ -234,6 +246,8 @@ SYMBOLS = [
                                              C.POINTER(C.c_float)]),
     ("ca3d_ensemble_envelope", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _H, C.c_uint32, C.c_uint32, C.POINTER(EnvelopeStruct),
                                          C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_damage", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _H, C.c_uint32, C.c_uint32, C.POINTER(DamageStruct),
+                                       _u32p, C.c_uint32, C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

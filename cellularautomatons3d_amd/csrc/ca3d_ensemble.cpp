@@ -13,9 +13,10 @@
 // ca3d_ensemble_canon names universes up to the 48 symmetries of the cube and translation (ca_canon.hip).
 // ca3d_ensemble_canon_period does so over a period of each universe's own steps, inside the kernel (ca_canon_period.hip).
 // ca3d_ensemble_envelope takes envelope, stator, rotor and heat over such a period, and may write them as universes (ca_envelope.hip).
+// ca3d_ensemble_damage follows a universe and a perturbed twin and takes their Hamming distance at every step (ca_damage.hip).
 // What these calls share is written once, in the unnamed namespace: a staging array on the handle (Scratch) and the event pair around a
 // launch (Timer), both had from `reserve`; reset_records and mark_state / mark_rules for universes that were just written; and, for
-// isolate, compose and envelope, the checks on two handles, the wait on the source's stream and the end of the call (finish_destinations).
+// isolate, compose, envelope and damage, the checks on two handles, the wait on the source's stream and the end of the call (finish_destinations).
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -104,6 +105,11 @@ struct ca3d_ensemble
 	Scratch envelope;
 	Timer envelope_time;
 	hipEvent_t envelope_src = nullptr;
+	// ca3d_ensemble_damage, on the handle the launch runs on, as the envelope's: the records of the call under way, [count] of 48 bytes,
+	// then the uploaded steps, twins and flips, [count] x 6 words, then the curve, [count][curve_stride] words, when one is asked for
+	Scratch damage;
+	Timer damage_time;
+	hipEvent_t damage_src = nullptr;
 };
 
 namespace
@@ -128,7 +134,7 @@ void free_arrays(ca3d_ensemble *e)
 	e->sheet_counters = nullptr;
 	e->sheet_px = 0;
 	e->sheet_drawn = false;
-	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon, &e->envelope})
+	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon, &e->envelope, &e->damage})
 	{
 		if (s->array) hipFree(s->array);
 		*s = Scratch{};
@@ -593,10 +599,10 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	hipSetDevice(e->device);
 	if (e->stream) hipStreamSynchronize(e->stream);
 	free_arrays(e);
-	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time, e->envelope_time})
+	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time, e->envelope_time, e->damage_time})
 		for (hipEvent_t ev : {t.start, t.stop})
 			if (ev) hipEventDestroy(ev);
-	for (hipEvent_t ev : {e->ev_seed, e->isolate_src, e->compose_src, e->envelope_src})
+	for (hipEvent_t ev : {e->ev_seed, e->isolate_src, e->compose_src, e->envelope_src, e->damage_src})
 		if (ev) hipEventDestroy(ev);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
@@ -1269,6 +1275,111 @@ int ca3d_ensemble_envelope(ca3d_ensemble_t *src, uint32_t first, uint32_t count,
 	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, src->stream));
 	HIP_TRY(hipStreamSynchronize(src->stream));
 	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, src->envelope_time.start, src->envelope_time.stop));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_damage(ca3d_ensemble_t *src, uint32_t first, uint32_t count, const uint32_t *steps, const uint32_t *twins, const uint32_t *flips, ca3d_ensemble_t *dst,
+                         uint32_t dst_first, uint32_t flags, ca3d_damage *out, uint32_t *curve, uint32_t curve_stride, float *gpu_ms) CA3D_API_TRY
+{
+	if (!src) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!steps) return fail(CA3D_ERR_INVALID_ARGUMENT, "steps is NULL");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	int rc = check_range(src, first, count);
+	if (rc) return rc;
+	uint32_t longest = 0;
+	for (uint32_t k = 0; k < count; k++)
+	{
+		if (steps[k] == 0 || steps[k] > CA3D_CANON_MAX_PERIOD)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "steps[%u] is %u (universe %u): a step count is 1 .. %u", k, steps[k], first + k, (unsigned)CA3D_CANON_MAX_PERIOD);
+		if (steps[k] > longest) longest = steps[k];
+	}
+	for (uint32_t k = 0; twins && k < count; k++)
+		if (twins[k] != CA3D_DAMAGE_SELF && twins[k] >= src->n)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "twins[%u] is %u (universe %u): a twin is CA3D_DAMAGE_SELF or one of the ensemble's %u universes", k, twins[k], first + k, src->n);
+	for (uint32_t k = 0; flips && k < count; k++)
+		for (uint32_t i = 0; i < CA3D_DAMAGE_FLIPS; i++)
+		{
+			const uint32_t f = flips[k * CA3D_DAMAGE_FLIPS + i];
+			if (f != CA3D_DAMAGE_NO_FLIP && ((f & 0xFFu) >= 64u || ((f >> 8) & 0xFFu) >= 64u || ((f >> 16) & 0xFFu) >= 64u || f >> 24))
+				return fail(CA3D_ERR_INVALID_ARGUMENT, "flips[%u][%u] is %#x (universe %u): a flip is x | y << 8 | z << 16 with x, y, z below 64, or CA3D_DAMAGE_NO_FLIP", k, i, f,
+				            first + k);
+		}
+	if (curve && curve_stride < longest + 1u)
+		return fail(CA3D_ERR_INVALID_ARGUMENT, "curve_stride is %u: a curve of %u steps holds %u samples", curve_stride, longest, longest + 1u);
+	const uint32_t image = flags & CA3D_DAMAGE_IMAGE_DAMAGE;
+	const bool copy_rules = (flags & CA3D_DAMAGE_COPY_RULES) != 0u;
+	if (flags & ~(CA3D_DAMAGE_IMAGE_DAMAGE | CA3D_DAMAGE_COPY_RULES)) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown bits in flags %#x", flags);
+	if (image && !dst) return fail(CA3D_ERR_INVALID_ARGUMENT, "flags %#x ask for the image, and dst is NULL", flags);
+	if (!image && dst) return fail(CA3D_ERR_INVALID_ARGUMENT, "dst is given, and flags %#x ask for no image (CA3D_DAMAGE_IMAGE_DAMAGE = 1)", flags);
+	if (!image && copy_rules) return fail(CA3D_ERR_INVALID_ARGUMENT, "CA3D_DAMAGE_COPY_RULES in flags %#x that ask for no image: there is no destination to copy a rule to", flags);
+	if (dst)
+	{
+		if ((rc = check_destinations(dst, src, dst_first, count, "images into"))) return rc;
+		// the source range and the destinations are two intervals of the same ensemble: the first universe they share
+		const uint32_t shared = first > dst_first ? first : dst_first;
+		if (src == dst && shared - first < count && shared - dst_first < count)
+			return check_source(dst, src, dst_first, count, "source", shared - first, shared, false);
+		for (uint32_t k = 0; src == dst && twins && k < count; k++)
+			if (twins[k] != CA3D_DAMAGE_SELF && twins[k] >= dst_first && twins[k] - dst_first < count) return check_source(dst, src, dst_first, count, "twin", k, twins[k], false);
+		if ((rc = check_same_device_and_kind(dst, src, false, "CA3D_DAMAGE_COPY_RULES"))) return rc; // the device
+	}
+	if ((rc = require_state(src, first, count))) return rc;
+	for (uint32_t k = 0; twins && k < count; k++)
+		if (twins[k] != CA3D_DAMAGE_SELF && !src->has_state[twins[k]])
+			return fail(CA3D_ERR_NOT_CONFIGURED, "twins[%u]: ca3d_ensemble_upload_state has not been called for universe %u", k, twins[k]);
+	for (uint32_t u = first; u < first + count; u++)
+		if (!src->has_rules[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_set_rules has not been called for universe %u", u);
+	if (dst && (rc = check_same_device_and_kind(dst, src, copy_rules, "CA3D_DAMAGE_COPY_RULES"))) return rc; // the kind
+	ca3d_ensemble *run = dst ? dst : src; // the handle whose stream takes the launch
+	HIP_TRY(hipSetDevice(run->device));
+	constexpr uint32_t kItemWords = 2u + CA3D_DAMAGE_FLIPS; // a universe's step count, twin and flips
+	const size_t rec_bytes = (size_t)count * sizeof(ca3d_damage), item_bytes = (size_t)count * kItemWords * sizeof(uint32_t);
+	const size_t curve_bytes = curve ? (size_t)count * curve_stride * sizeof(uint32_t) : 0, bytes = rec_bytes + item_bytes + curve_bytes;
+	if ((rc = reserve(run, run->damage, bytes, &run->damage_time, &run->damage_src, "%zu bytes of damage records", bytes))) return rc;
+	// steps, twins and flips as the kernel reads them, every default written out
+	std::vector<uint32_t> items((size_t)count * kItemWords, 0xFFFFFFFFu); // CA3D_DAMAGE_SELF, CA3D_DAMAGE_NO_FLIP
+	memcpy(items.data(), steps, (size_t)count * sizeof(uint32_t));
+	if (twins) memcpy(items.data() + count, twins, (size_t)count * sizeof(uint32_t));
+	if (flips) memcpy(items.data() + 2u * (size_t)count, flips, (size_t)count * CA3D_DAMAGE_FLIPS * sizeof(uint32_t));
+	DamageLaunch l{};
+	l.state = src->state;
+	l.rules = src->rules;
+	l.neighbourhood = src->neighbourhood;
+	l.clustered = src->clustered;
+	l.boundary = src->boundary;
+	l.first = first; l.count = count;
+	l.out = run->damage.at<ca3d_damage>();
+	uint32_t *items_dev = run->damage.at<uint32_t>(rec_bytes);
+	l.steps = items_dev;
+	l.twins = items_dev + count;
+	l.flips = items_dev + 2u * (size_t)count;
+	l.curve = curve ? run->damage.at<uint32_t>(rec_bytes + item_bytes) : nullptr;
+	l.curve_stride = curve_stride;
+	l.image = image;
+	if (dst)
+	{
+		l.dst_state = dst->state; l.dst_prev = dst->prev;
+		l.dst_rules = dst->rules;
+		l.dst_first = dst_first;
+		l.rule_words = copy_rules ? rule_words(dst) : 0u;
+	}
+	if ((rc = wait_for_source(run, src, run->damage_src))) return rc;
+	// (from pageable memory: the copy has left `items` when the call returns)
+	HIP_TRY(hipMemcpyAsync(items_dev, items.data(), item_bytes, hipMemcpyHostToDevice, run->stream));
+	HIP_TRY(hipEventRecord(run->damage_time.start, run->stream));
+	HIP_TRY(launch_damage(l, run->stream));
+	HIP_TRY(hipEventRecord(run->damage_time.stop, run->stream));
+	if (curve) HIP_TRY(hipMemcpyAsync(curve, l.curve, curve_bytes, hipMemcpyDeviceToHost, run->stream));
+	if (dst)
+	{
+		if ((rc = finish_destinations(dst, dst_first, count, dst->damage, dst->damage_time, out, rec_bytes, gpu_ms))) return rc;
+		if (copy_rules) mark_rules(dst, dst_first, count);
+		return CA3D_OK;
+	}
+	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, src->stream));
+	HIP_TRY(hipStreamSynchronize(src->stream));
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, src->damage_time.start, src->damage_time.stop));
 	return CA3D_OK;
 }
 CA3D_API_CATCH

@@ -331,6 +331,33 @@ struct EnvelopeLaunch
 	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
 };
 hipError_t launch_envelope(const EnvelopeLaunch &l, hipStream_t stream);
+// ca_damage.hip: the Hamming distance between universe first + k and a perturbed twin over steps[k] steps, for universes [first, first +
+// count) of a source ensemble's state and rule arrays (ca3d_ensemble_damage), one workgroup each of ca_ensemble_damage_{vn,moore,
+// clustered}64[_torus|_closed] by the source's kind and boundary; out, steps, twins, flips and curve are indexed by universe - first.
+// With the image, source k writes D_P into both buffers of destination universe dst_first + k. The caller has checked every range, step
+// count, twin and flip, that curve_stride > max(steps) when there is a curve, and that no source or twin universe is a destination. The
+// source's states and rules are only read.
+struct DamageLaunch
+{
+	const uint32_t *state;          // [Bs][8192], the source ensemble's current states
+	const uint32_t *rules;          // [Bs][ensemble_rule_words()]
+	int neighbourhood;              // CA3D_ENSEMBLE_*, of the source
+	bool clustered;
+	int boundary;                   // CA3D_ENSEMBLE_BOUNDARY_*, of the source
+	uint32_t first, count;
+	const uint32_t *steps;          // device, [count]
+	const uint32_t *twins;          // device, [count]: a universe of the source, or CA3D_DAMAGE_SELF
+	const uint32_t *flips;          // device, [count][CA3D_DAMAGE_FLIPS]: x | y << 8 | z << 16, or CA3D_DAMAGE_NO_FLIP
+	ca3d_damage *out;               // device, [count]: every entry is written
+	uint32_t *curve;                // device, [count][curve_stride]: every word is written; or NULL
+	uint32_t curve_stride;
+	uint32_t image;                 // 0 or CA3D_DAMAGE_IMAGE_DAMAGE; 0: nothing below is used
+	uint32_t *dst_state, *dst_prev; // [Bd][8192], the destination ensemble's two buffers
+	uint32_t *dst_rules;            // [Bd][rule_words]
+	uint32_t dst_first;
+	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
+};
+hipError_t launch_damage(const DamageLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

@@ -406,6 +406,60 @@ class Ensemble:
         """hipEvent time of the last `envelope` launch of this object, in milliseconds (None before the first)."""
         return getattr(self, "_envelope_ms", None)
 
+    def damage(self, steps, first: int = 0, twins=None, flips=None, dst: Optional["Ensemble"] = None, dst_first: int = 0,
+               image: bool = False, copy_rules: bool = False, curve: bool = False):
+        """`ca3d_ensemble_damage`: how a perturbation of universe first + k spreads over steps[k] steps — the universe and a perturbed
+        twin stepped side by side INSIDE one launch behind the queued steps, under the universe's rule and this ensemble's boundary,
+        and their Hamming distance d_t taken at every t = 0 .. steps[k]; this ensemble is left exactly as it is -> records of
+        `host.DAMAGE_DTYPE`, or (records, curve) with `curve=True`: curve[k, t] = d_t, zero behind steps[k], max(steps) + 1 columns.
+        `steps` is one number for every universe from `first` on, or one per universe, each 1 .. `host.CANON_MAX_PERIOD`.
+        The twin starts as the universe itself, or as universe twins[k] of this ensemble (`host.DAMAGE_SELF`: itself), with the cells
+        of flips[k] flipped: up to `host.DAMAGE_FLIPS` cells (x, y, z) a universe, a cell listed twice cancels; `flips` may also be
+        one (x, y, z) for every universe, or an array [count, 4] of flip words (`host.damage_flip_word`, `host.DAMAGE_NO_FLIP`).
+        `image`: universe dst_first + k of `dst` (this ensemble or another one on the same device; required with the image, None
+        without) becomes the last difference S ^ T, at step 0. `copy_rules`: each destination takes its source universe's rule (both
+        ensembles of one kind). `host.damage` is the same on the CPU for one universe; `damage_gpu_ms()` tells what the launch took."""
+        p = _as_u32(steps).ravel()
+        if np.ndim(steps) == 0:
+            p = np.full(max(self.n - first, 0), p[0], dtype=np.uint32)
+        p = np.ascontiguousarray(p)
+        tw = None
+        if twins is not None:
+            tw = np.ascontiguousarray(_as_u32(twins).ravel())
+            if tw.size != p.size:
+                raise ValueError(f"{tw.size} twins for {p.size} universes")
+        fl = None
+        if flips is not None:
+            if isinstance(flips, np.ndarray) and flips.dtype == np.uint32 and flips.shape == (p.size, host.DAMAGE_FLIPS):
+                fl = np.ascontiguousarray(flips)
+            else:
+                per = list(flips)
+                if len(per) == 3 and all(np.ndim(v) == 0 for v in per):
+                    per = [[per]] * p.size  # one cell for every universe
+                if len(per) != p.size:
+                    raise ValueError(f"flips for {len(per)} universes, steps for {p.size}")
+                fl = np.full((p.size, host.DAMAGE_FLIPS), host.DAMAGE_NO_FLIP, dtype=np.uint32)
+                for k, cells in enumerate(per):
+                    cells = list(cells)
+                    if len(cells) > host.DAMAGE_FLIPS:
+                        raise ValueError(f"universe {first + k}: {len(cells)} flips, at most {host.DAMAGE_FLIPS}")
+                    fl[k, :len(cells)] = [host.damage_flip_word(c) for c in cells]
+        flags = (_capi.DAMAGE_IMAGE_DAMAGE if image else 0) | (_capi.DAMAGE_COPY_RULES if copy_rules else 0)
+        rec = np.zeros(p.size, dtype=host.DAMAGE_DTYPE)
+        stride = int(p.max()) + 1 if curve and p.size else 0
+        samples = np.zeros((p.size, stride), dtype=np.uint32) if curve else None
+        ms = C.c_float(0.0)
+        _capi.check(self._lib.ca3d_ensemble_damage(self._h, first, p.size, p.ctypes.data_as(_u32p), None if tw is None else tw.ctypes.data_as(_u32p),
+                                                   None if fl is None else fl.ctypes.data_as(_u32p), None if dst is None else dst._h, dst_first, flags,
+                                                   rec.ctypes.data_as(C.POINTER(_capi.DamageStruct)),
+                                                   None if samples is None else samples.ctypes.data_as(_u32p), stride, C.byref(ms)))
+        self._damage_ms = float(ms.value)
+        return (rec, samples) if curve else rec
+
+    def damage_gpu_ms(self) -> float:
+        """hipEvent time of the last `damage` launch of this object, in milliseconds (None before the first)."""
+        return getattr(self, "_damage_ms", None)
+
     def canon_phases(self, periods, first: int = 0, count: Optional[int] = None,
                      max_period: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """`canon` over a whole period, for universes already classified as oscillators or ships (`step_until_cycle`,

@@ -1014,6 +1014,109 @@ def envelope_derived(records) -> dict:
             "heat_per_step": r["heat"] / np.maximum(r["period"], 1), "returns": (r["flags"] & ENVELOPE_RETURNS) != 0}
 
 
+# ------------------------------------------------------------------------------------------ damage spreading
+# The definition of ca3d_ensemble_damage (include/ca3d.h) in executable form, for one universe.
+
+#: ca3d_damage (include/ca3d.h), 48 bytes; a box corner is x, y, z and a zero byte
+DAMAGE_DTYPE = np.dtype([("steps", "<u4"), ("flags", "<u4"), ("healed_at", "<u4"), ("final_distance", "<u4"), ("initial_distance", "<u4"),
+                         ("max_distance", "<u4"), ("max_at", "<u4"), ("distance_sum", "<u4"), ("damage_min", "u1", 4), ("damage_max", "u1", 4),
+                         ("touched_min", "u1", 4), ("touched_max", "u1", 4)])
+#: bit 0 of `flags`; `healed_at` without it; flip words a universe; "the universe itself" among the twins; "no cell" among the flips
+DAMAGE_HEALED = 1
+DAMAGE_NEVER = 0xFFFFFFFF
+DAMAGE_FLIPS = 4
+DAMAGE_SELF = 0xFFFFFFFF
+DAMAGE_NO_FLIP = 0xFFFFFFFF
+
+
+def damage_flip_word(cell) -> int:
+    """The flip word of cell (x, y, z): x | y << 8 | z << 16."""
+    x, y, z = (int(v) for v in cell)
+    if not (0 <= x < 64 and 0 <= y < 64 and 0 <= z < 64):
+        raise ValueError(f"a flipped cell lies inside the 64^3 universe, not at {(x, y, z)}")
+    return x | y << 8 | z << 16
+
+
+def _damage_over(pairs, p: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(curve, record, D_P) of the pairs (S_t, T_t), t = 0 .. p, that `pairs` yields. It may stop early: after a pair with d_t == 0 it is
+    not asked again, and when it ends by itself every later D_t is the last one it gave."""
+    curve = np.zeros(p + 1, dtype=np.uint32)
+    touched = np.zeros(words_per_buffer(64), dtype=np.uint32)
+    for i, (s, t) in enumerate(pairs):
+        d = s ^ t
+        curve[i] = _packed_popcount(d)
+        touched |= d
+        if curve[i] == 0 or i == p:
+            break
+    curve[i:] = curve[i]
+    rec = np.zeros((), dtype=DAMAGE_DTYPE)
+    zeros = np.flatnonzero(curve == 0)
+    rec["steps"] = p
+    rec["flags"] = DAMAGE_HEALED if zeros.size else 0
+    rec["healed_at"] = zeros[0] if zeros.size else DAMAGE_NEVER
+    rec["final_distance"], rec["initial_distance"] = curve[p], curve[0]
+    rec["max_distance"], rec["max_at"] = curve.max(), int(np.argmax(curve))
+    rec["distance_sum"] = int(curve.astype(np.uint64).sum())
+    for name, image in (("damage", d), ("touched", touched)):
+        lo, hi = _packed_box(image)
+        rec[name + "_min"][:3], rec[name + "_max"][:3] = lo, hi
+    return curve, rec, d.astype(np.uint32)
+
+
+def damage_of_phases(states, twins) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`ca3d_ensemble_damage` of ONE universe whose two trajectories the caller has stepped: `states` is [P + 1, 8192], S_0 .. S_P, and
+    `twins` T_0 .. T_P likewise -> (curve, record of DAMAGE_DTYPE, D_P), as `damage` gives them."""
+    s, t = np.ascontiguousarray(states, dtype="<u4"), np.ascontiguousarray(twins, dtype="<u4")
+    if s.ndim != 2 or s.shape[0] < 2 or s.shape[1] != words_per_buffer(64) or t.shape != s.shape:
+        raise ValueError("states and twins are [P + 1, 8192] with P >= 1: S_0 .. S_P and T_0 .. T_P")
+    if s.shape[0] - 1 > CANON_MAX_PERIOD:
+        raise ValueError(f"a step count is at most {CANON_MAX_PERIOD}")
+    return _damage_over(zip(s, t), s.shape[0] - 1)
+
+
+def damage_twin(state, twin=None, flips=()) -> np.ndarray:
+    """T_0 = W ^ F of `damage`: `twin` (None: `state` itself) with the cells (x, y, z) of `flips` XORed in one after another."""
+    flips = list(flips)
+    if len(flips) > DAMAGE_FLIPS:
+        raise ValueError(f"at most {DAMAGE_FLIPS} flips a universe")
+    t = np.ascontiguousarray(state if twin is None else twin, dtype="<u4").ravel().astype(np.uint32)
+    if t.size != words_per_buffer(64):
+        raise ValueError("a universe is 8192 words")
+    for cell in flips:
+        damage_flip_word(cell)  # inside the universe
+        t ^= cells_to_words(64, [tuple(int(v) for v in cell)])
+    return t
+
+
+def damage(state, kind: str, tables, steps: int, boundary: str = "reference", twin=None, flips=()) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`ca3d_ensemble_damage` for ONE packed 64^3 universe, in plain numpy over `ensemble_step`: `state` (S_0) and a perturbed twin are
+    followed over `steps` steps (P, 1 .. CANON_MAX_PERIOD) of the rule `kind`, `tables` under `boundary`, as `ensemble_step` takes them
+    -> (curve [P + 1] of d_0 .. d_P, record of DAMAGE_DTYPE, D_P as a packed state). The twin starts as T_0 = W ^ F (`damage_twin`): W
+    is `twin`, another packed state, or S_0 itself (None); F has exactly the cells (x, y, z) of `flips` set, at most DAMAGE_FLIPS of
+    them, XORed in one after another, so a cell listed twice cancels. D_t = S_t ^ T_t, d_t = popcount(D_t). DAMAGE_HEALED (bit 0 of
+    flags) is set exactly when some d_t == 0, and `healed_at` is the first such t (DAMAGE_NEVER if none); `max_at` is the first t that
+    reaches `max_distance`; `distance_sum` sums d_0 .. d_P; `damage_min` / `damage_max` is the inclusive box of D_P and `touched_min` /
+    `touched_max` that of D_0 | .. | D_P, zero for an empty set. Once d_t == 0 both trajectories are one and the rest is zero; once a
+    step changes neither state every later sample repeats this one: the stepping stops there, and the result is that of the full P
+    steps."""
+    p = int(steps)
+    if not 1 <= p <= CANON_MAX_PERIOD:
+        raise ValueError(f"a step count is 1 .. {CANON_MAX_PERIOD}")
+    s0 = np.ascontiguousarray(state, dtype="<u4").ravel().astype(np.uint32)
+    if s0.size != words_per_buffer(64):
+        raise ValueError("a universe is 8192 words")
+
+    def pairs(s, t):
+        while True:
+            yield s, t
+            s1, t1 = ensemble_step(s, kind, tables, boundary), ensemble_step(t, kind, tables, boundary)
+            if np.array_equal(s1, s) and np.array_equal(t1, t):  # two still lifes
+                return
+            s, t = s1, t1
+
+    return _damage_over(pairs(s0, damage_twin(s0, twin, flips)), p)
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

@@ -1541,6 +1541,54 @@ static napi_value js_ensemble_envelope(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* ensembleDamage(srcHandle, first, Uint32Array(count) steps, Uint32Array(count) twins or null, Uint32Array(count * 4) flips or null,
+ *                dstHandle or null, dstFirst, flags, Uint32Array(count * 12) records, Uint32Array(count * curveStride) curve or null,
+ *                curveStride) -> gpuMs: the Hamming distance between universes [first, first + count) and their perturbed twins over
+ * steps[k] steps of their own, taken inside the kernel, the last difference written into dst's universes from dstFirst when flags asks
+ * for it (ca3d_ensemble_damage); a record is ca3d_damage's twelve words: steps, flags, healedAt, finalDistance, initialDistance,
+ * maxDistance, maxAt, distanceSum, damageMin, damageMax, touchedMin, touchedMax (x | y << 8 | z << 16 each) (js/ca3d.js opens them) */
+static napi_value js_ensemble_damage(napi_env env, napi_callback_info info)
+{
+	napi_value argv[11];
+	if (!get_args(env, info, 11, argv)) return NULL;
+	ca3d_ensemble_t *src = get_ensemble(env, argv[0]);
+	if (!src) return NULL;
+	ca3d_ensemble_t *dst = NULL;
+	napi_valuetype t;
+	napi_typeof(env, argv[5], &t);
+	if (t != napi_null && t != napi_undefined && !(dst = get_ensemble(env, argv[5]))) return NULL;
+	uint32_t first, dst_first, flags, stride;
+	void *steps, *twins, *flips, *recs, *curve;
+	size_t count, ntwins, nflips, nrecs, ncurve;
+	if (!get_u32(env, argv[1], &first) || !get_typed(env, argv[2], napi_uint32_array, 0, &steps, &count) ||
+	    !get_typed(env, argv[3], napi_uint32_array, 1, &twins, &ntwins) || !get_typed(env, argv[4], napi_uint32_array, 1, &flips, &nflips) ||
+	    !get_u32(env, argv[6], &dst_first) || !get_u32(env, argv[7], &flags) || !get_typed(env, argv[8], napi_uint32_array, 0, &recs, &nrecs) ||
+	    !get_typed(env, argv[9], napi_uint32_array, 1, &curve, &ncurve) || !get_u32(env, argv[10], &stride))
+		return NULL;
+	if (count > 0xFFFFFFFFu || nrecs != count * 12u || (twins && ntwins != count) || (flips && nflips != count * CA3D_DAMAGE_FLIPS) ||
+	    (curve && ncurve != count * (size_t)stride))
+	{
+		napi_throw_range_error(env, NULL, "records must hold twelve words a universe, twins one, flips four and the curve curveStride");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_damage) == 48, "a record crosses as twelve words");
+	float ms = 0.f;
+	/* (count 0: the library refuses the call and names the reason; it reads and writes no array, and an empty typed array may have no
+	 * address at all) */
+	uint32_t none[12];
+	if (!count)
+	{
+		steps = recs = none;
+		twins = flips = curve = NULL;
+	}
+	int rc = ca3d_ensemble_damage(src, first, (uint32_t)count, (const uint32_t *)steps, (const uint32_t *)twins, (const uint32_t *)flips, dst, dst_first, flags,
+	                              (ca3d_damage *)recs, (uint32_t *)curve, stride, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1767,7 +1815,8 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleCensus", js_ensemble_census}, {"ensembleIsolate", js_ensemble_isolate}, {"ensembleCompose", js_ensemble_compose},
 	    {"ensembleCanon", js_ensemble_canon},
 	    {"ensembleCanonPeriod", js_ensemble_canon_period},
-	    {"ensembleEnvelope", js_ensemble_envelope}};
+	    {"ensembleEnvelope", js_ensemble_envelope},
+	    {"ensembleDamage", js_ensemble_damage}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{
 		napi_value f;

@@ -235,6 +235,8 @@ const COMPOSE_OVER = 0x1, COMPOSE_COPY_RULES = 0x100; // CA3D_COMPOSE_OVER / CA3
 const CANON_CLOSED = 0x1, CANON_MAX_PERIOD = 4096; // CA3D_CANON_CLOSED / CA3D_CANON_MAX_PERIOD (Ensemble.canonPeriod)
 // CA3D_ENVELOPE_RETURNS, the image bits in the order the images are written, CA3D_ENVELOPE_COPY_RULES (Ensemble.envelope)
 const ENVELOPE_RETURNS = 0x1, ENVELOPE_IMAGES = { envelope: 1, stator: 2, rotor: 4 }, ENVELOPE_COPY_RULES = 0x100;
+// CA3D_DAMAGE_HEALED, CA3D_DAMAGE_FLIPS, CA3D_DAMAGE_SELF = CA3D_DAMAGE_NO_FLIP, CA3D_DAMAGE_IMAGE_DAMAGE, CA3D_DAMAGE_COPY_RULES (Ensemble.damage)
+const DAMAGE_HEALED = 0x1, DAMAGE_FLIPS = 4, DAMAGE_NONE = 0xFFFFFFFF, DAMAGE_IMAGE_DAMAGE = 0x1, DAMAGE_COPY_RULES = 0x100;
 
 class Engine
 {
@@ -742,6 +744,58 @@ class Ensemble
 				statorPopulation: r[5], rotorPopulation: r[4] - r[5], envelopeMin: box(r[6]), envelopeMax: box(r[7]), rotorMin: box(r[8]), rotorMax: box(r[9]) });
 		}
 		return { records, gpuMs };
+	}
+	/** Damage spreading (ca3d_ensemble_damage): how a perturbation of universe opts.first + k spreads over steps[k] steps — the universe
+	 *  and a perturbed twin stepped side by side INSIDE one launch behind the queued steps, under the universe's rule and this ensemble's
+	 *  boundary, their Hamming distance d_t taken at every t = 0 .. steps[k]; this ensemble is left exactly as it is.
+	 *  steps: one number for every universe from opts.first on, or an array with one step count per universe, each 1 .. 4096
+	 *  -> {records, gpuMs} and, with opts.curve, curve: records[k] = {steps, healed, healedAt (the first t with d_t = 0, null if none),
+	 *  finalDistance, initialDistance, maxDistance, maxAt, distanceSum, damageMin, damageMax (the box of the last difference),
+	 *  touchedMin, touchedMax (the box of every difference; [x, y, z], inclusive; zeros for an empty set)}; curve[k] = Uint32Array of
+	 *  d_0 .. d_steps[k].
+	 *  opts.twins: per universe the universe of this ensemble the twin starts from, null for the universe itself (the default for all);
+	 *  opts.flips: per universe up to four cells [x, y, z] flipped in the twin, a cell listed twice cancels. opts.image: universe
+	 *  opts.dstFirst + k of opts.dst (this ensemble or another one on the same device; required with the image) becomes the last
+	 *  difference, at step 0. opts.copyRules (default false): each destination takes its source universe's rule (both ensembles of
+	 *  one kind). */
+	damage(steps, opts)
+	{
+		const o = Object.assign({ first: 0, twins: null, flips: null, dst: null, dstFirst: 0, image: false, copyRules: false, curve: false }, opts || {});
+		const count = Math.max(this.n - o.first, 0);
+		const p = typeof steps === "number" ? new Uint32Array(count).fill(steps) : Uint32Array.from(steps);
+		const twins = o.twins ? Uint32Array.from(o.twins, (u) => (u === null || u === undefined ? DAMAGE_NONE : u)) : null;
+		let flips = null;
+		if (o.flips)
+		{
+			if (o.flips.length !== p.length) throw new Error(`flips for ${o.flips.length} universes, steps for ${p.length}`);
+			flips = new Uint32Array(p.length * DAMAGE_FLIPS).fill(DAMAGE_NONE);
+			o.flips.forEach((cells, k) =>
+			{
+				if (cells.length > DAMAGE_FLIPS) throw new Error(`universe ${o.first + k}: ${cells.length} flips, at most ${DAMAGE_FLIPS}`);
+				cells.forEach(([x, y, z], i) =>
+				{
+					if (![x, y, z].every((v) => Number.isInteger(v) && v >= 0 && v < 64)) throw new Error(`a flipped cell lies inside the 64^3 universe, not at ${[x, y, z]}`);
+					flips[k * DAMAGE_FLIPS + i] = (x | y << 8 | z << 16) >>> 0;
+				});
+			});
+		}
+		const flags = (o.image ? DAMAGE_IMAGE_DAMAGE : 0) | (o.copyRules ? DAMAGE_COPY_RULES : 0);
+		const stride = o.curve && p.length ? p.reduce((a, b) => Math.max(a, b), 0) + 1 : 0;
+		const samples = o.curve ? new Uint32Array(p.length * stride) : null;
+		const words = new Uint32Array(p.length * 12);
+		const gpuMs = this._a.ensembleDamage(this._e, o.first, p, twins, flips, o.dst ? o.dst._e : null, o.dstFirst, flags, words, samples, stride);
+		const box = (w) => [w & 0xFF, (w >>> 8) & 0xFF, (w >>> 16) & 0xFF];
+		const records = [];
+		for (let k = 0; k < p.length; k++)
+		{
+			const r = words.subarray(12 * k, 12 * k + 12);
+			records.push({ steps: r[0], healed: (r[1] & DAMAGE_HEALED) !== 0, healedAt: r[1] & DAMAGE_HEALED ? r[2] : null, finalDistance: r[3], initialDistance: r[4],
+				maxDistance: r[5], maxAt: r[6], distanceSum: r[7], damageMin: box(r[8]), damageMax: box(r[9]), touchedMin: box(r[10]), touchedMax: box(r[11]) });
+		}
+		if (!o.curve) return { records, gpuMs };
+		const curve = [];
+		for (let k = 0; k < p.length; k++) curve.push(samples.slice(k * stride, k * stride + p[k] + 1));
+		return { records, curve, gpuMs };
 	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at

@@ -855,6 +855,75 @@ typedef struct ca3d_envelope
 int ca3d_ensemble_envelope(ca3d_ensemble_t *src, uint32_t first, uint32_t count, const uint32_t *periods /* [count] */,
                            ca3d_ensemble_t *dst /* NULL without images */, uint32_t dst_first, uint32_t flags,
                            ca3d_envelope *out /* [count] */, float *gpu_ms /* may be NULL */);
+/*
+ * Damage spreading (no reference counterpart): flip a cell — does the difference die out, stay put, or take over the universe? The
+ * Hamming distance between a state and a perturbed twin over time, the standard classifier of ordered, critical and chaotic rules.
+ * One launch of ca_ensemble_damage_{vn,moore,clustered}64[_torus|_closed] (csrc/ca_damage.hip, by the source ensemble's kind and its
+ * CURRENT boundary mode, one workgroup a universe) for universes first .. first + count - 1 of `src`. Both trajectories of universe
+ * first + k are followed over steps[k] steps INSIDE the kernel; nothing is written back to `src`. host.damage restates it in plain
+ * numpy over host.ensemble_step.
+ *
+ * The definition. For source universe u = first + k let P = steps[k], 1 <= P <= CA3D_CANON_MAX_PERIOD, and S_0 its current state.
+ *   The twin starts as T_0 = W ^ F. W is S_0 when twins is NULL or twins[k] == CA3D_DAMAGE_SELF, else the current state of universe
+ *   twins[k] of the same ensemble. F has exactly the cells of flips[k][0 .. CA3D_DAMAGE_FLIPS - 1] set, XORed in one after another,
+ *   so a cell listed twice cancels; a flip is x | y << 8 | z << 16 with x, y, z < 64, or CA3D_DAMAGE_NO_FLIP; flips == NULL: none.
+ *   S_(t+1) = step(S_t) and T_(t+1) = step(T_t) by the ensemble's own step: u's rule (a twin's rule is never read) and the ensemble's
+ *   current boundary mode (reference, torus or closed), exactly as ca3d_ensemble_step does.
+ *   D_t = S_t ^ T_t and d_t = popcount(D_t) for t = 0 .. P.
+ *   steps echoes P. flags bit 0, CA3D_DAMAGE_HEALED, is set exactly when some d_t == 0 with t <= P, and healed_at is the first such
+ *   t, 0xFFFFFFFF if none: from there on the trajectories are equal for good, every later sample is 0 and D_P is empty. (A kernel may
+ *   stop stepping there; the definition does not depend on whether it does.)
+ *   final_distance = d_P, initial_distance = d_0, max_distance the largest d_t and max_at the first t that reaches it,
+ *   distance_sum = the sum of d_t over t = 0 .. P: at most 262 144 * 4 097 = 1 074 003 968, which fits a word.
+ *   damage_min / damage_max are the inclusive bounding box of D_P, touched_min / touched_max that of D_0 | ... | D_P, the cone the
+ *   damage swept: x, y, z and a zero byte; an empty set has min = max = 0.
+ *
+ * The curve. With curve != NULL, curve[k * curve_stride + t] = d_t for t <= P and 0 for P < t < curve_stride;
+ *   curve_stride >= max(steps) + 1. curve_stride is not looked at when curve is NULL.
+ *
+ * The image. CA3D_DAMAGE_IMAGE_DAMAGE writes D_P as universe dst_first + k of `dst`, which is `src` itself or a second ensemble on the
+ *   same device: both ping-pong buffers are written and the records rebuilt at step 0, as ca3d_ensemble_envelope's images are.
+ *   CA3D_DAMAGE_COPY_RULES copies u's rule words to its destination as CA3D_ENVELOPE_COPY_RULES does: `src` and `dst` must then be of
+ *   one kind. The boundary of `dst` is not looked at. Without the image bit `dst` must be NULL.
+ *
+ * Ordering. The launch runs behind what is queued on both ensembles' streams, on the destination's when there is one. `src` is only
+ * read: states, records, step counters, anchors, steps_done and stats are unchanged. It needs a state on every source and twin
+ * universe and a rule on every source universe. The call waits for its own result. gpu_ms (nullable) receives the hipEvent time around
+ * the launch. Records, curve, steps, twins and flips are staged in a device array of the call's own on the handle the launch runs on.
+ *
+ * Errors: NULL `src`, steps or out — CA3D_ERR_INVALID_ARGUMENT without touching a device; `src` (or `dst`) not configured —
+ * CA3D_ERR_NOT_CONFIGURED; count == 0, first + count > n, a step count of 0 or above CA3D_CANON_MAX_PERIOD, a twin that is neither
+ * CA3D_DAMAGE_SELF nor a universe of `src`, a flip that is neither CA3D_DAMAGE_NO_FLIP nor three coordinates below 64 with a zero top
+ * byte, curve with curve_stride < max(steps) + 1, unknown bits in flags, the image bit without `dst`, `dst` without the image bit,
+ * CA3D_DAMAGE_COPY_RULES without the image bit, destinations past dst's n, a source or twin universe among the destinations of the
+ * same ensemble, different devices — CA3D_ERR_INVALID_ARGUMENT; a source or twin universe without a state, a source universe without
+ * a rule — CA3D_ERR_NOT_CONFIGURED; CA3D_DAMAGE_COPY_RULES across kinds — CA3D_ERR_UNSUPPORTED. Each message names its argument and
+ * the first offending universe. A refused call touches none of the caller's arrays and nothing on the device.
+ */
+#define CA3D_DAMAGE_HEALED 1u /* ca3d_damage.flags bit 0 */
+#define CA3D_DAMAGE_FLIPS 4u  /* flip words a universe */
+#define CA3D_DAMAGE_SELF 0xFFFFFFFFu
+#define CA3D_DAMAGE_NO_FLIP 0xFFFFFFFFu
+#define CA3D_DAMAGE_IMAGE_DAMAGE 1u
+#define CA3D_DAMAGE_COPY_RULES 0x100u
+typedef struct ca3d_damage
+{
+	uint32_t steps;            /* echoed */
+	uint32_t flags;            /* bit 0 CA3D_DAMAGE_HEALED */
+	uint32_t healed_at;        /* the first t with d_t == 0; 0xFFFFFFFF if none */
+	uint32_t final_distance;   /* d_P */
+	uint32_t initial_distance; /* d_0 */
+	uint32_t max_distance;     /* the largest d_t */
+	uint32_t max_at;           /* the first t that reaches it */
+	uint32_t distance_sum;     /* of d_0 .. d_P */
+	uint8_t damage_min[4], damage_max[4];   /* of D_P: x, y, z, 0: inclusive; both zero for an empty set */
+	uint8_t touched_min[4], touched_max[4]; /* of D_0 | ... | D_P */
+} ca3d_damage;                 /* 48 bytes */
+int ca3d_ensemble_damage(ca3d_ensemble_t *src, uint32_t first, uint32_t count, const uint32_t *steps /* [count] */,
+                         const uint32_t *twins /* [count] or NULL */, const uint32_t *flips /* [count][CA3D_DAMAGE_FLIPS] or NULL */,
+                         ca3d_ensemble_t *dst /* NULL without the image */, uint32_t dst_first, uint32_t flags,
+                         ca3d_damage *out /* [count] */, uint32_t *curve /* [count][curve_stride], may be NULL */,
+                         uint32_t curve_stride, float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

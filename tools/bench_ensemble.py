@@ -118,6 +118,16 @@ loop's host clock and the summed hipEvent time of its step launches. Before timi
 universes, and every loop's heat, envelope and stator populations must equal the call's everywhere. Reported: medians of --repeats
 measurements. No ratio is required. Written to profiles/ensemble_envelope_64.json unless --out says otherwise.
 
+--damage measures damage spreading (ca3d_ensemble_damage, kernels ca_ensemble_damage_{vn,moore,clustered}64: a universe and its twin
+with one random cell flipped, stepped side by side INSIDE one launch, their Hamming distance at every step) for all three kinds at
+B = 256 and 1024 over --steps steps, with the curve: the launch's hipEvent time and the host clock around the call. First against the
+loop it replaces — two ensembles kept in lock step, per sample step(1) on each, read_state of both, numpy XOR and byte-table popcounts on
+the host — run on --loop-samples samples and scaled to --steps (the loop's cost a sample does not depend on the sample). Second against
+the floor: two plain step(--steps) launches of the same kind on the same two ensembles, one after the other, their hipEvent times summed, since damage does
+twice the stepping. Before timing, the records and curves must equal host.damage in sampled universes over 3 steps, and the loop's
+distances must equal the call's curve in every universe. Reported: medians of --repeats measurements. No ratio is required. Written to
+profiles/ensemble_damage_64.json unless --out says otherwise.
+
 With --boundary: the plain step kernel of each new boundary mode (Ensemble.set_boundary: "torus", "closed") against the reference
 boundary's kernel on the same universes, for all three kinds (von Neumann, Moore, clustered) at B = 256 and 1024: Ensemble.step(--steps)
 from the same uploaded fills, the modes alternating inside one process, hipEvent times. Before timing, the state of sampled universes
@@ -1060,6 +1070,100 @@ def envelope_rows(args):
     return rows
 
 
+def damage_rows(args):
+    """damage against the two-ensemble step(1) + read_state + numpy loop it replaces and against two plain step launches, the floor:
+    one row per (kind, B). -> rows"""
+    def masks(s, bits):
+        return sum(1 << v for v in host.rules_components_to_values(s)) & ((1 << bits) - 1)
+
+    bits = np.array([bin(v).count("1") for v in range(256)], dtype=np.uint8)
+
+    def popcounts(a):
+        """popcount of every row of a [n, words] array, through a table of the 256 bytes"""
+        return bits[np.ascontiguousarray(a).view(np.uint8)].sum(axis=1, dtype=np.uint64)
+
+    a, b = Ensemble(0), Ensemble(0)
+    rows = []
+    med = statistics.median
+    for kind in ("von neumann", "moore", "clustered"):
+        clustered = kind == "clustered"
+        nb = "moore" if clustered else kind
+        if clustered:
+            keys = ("born", "survive", "born_edges", "survive_edges", "born_corners", "survive_corners")
+            tables = ([masks(CLUSTERED[keys[2 * i]], n) for i, n in enumerate((27, 13, 9))], [masks(CLUSTERED[keys[2 * i + 1]], n) for i, n in enumerate((27, 13, 9))])
+        else:
+            tables = (masks(RULES[nb][0], 27 if nb == "moore" else 7), masks(RULES[nb][1], 27 if nb == "moore" else 7))
+        for B in args.universes:
+            words = fills(B)
+            rng = np.random.default_rng(B)
+            cells = rng.integers(0, 64, (B, 3))
+            flips = [[tuple(int(v) for v in c)] for c in cells]
+            twins = words.copy()
+            for u, (x, y, z) in enumerate(cells):
+                twins[u] ^= host.cells_to_words(G, [(int(x), int(y), int(z))])
+            for e in (a, b):
+                e.configure(B, neighbourhood=nb, clustered=clustered)
+                if clustered:
+                    e.set_clustered_tables(0, tables[0], tables[1])
+                else:
+                    e.set_rule_tables(0, tables[0], tables[1])
+            a.upload_state(0, words)
+            b.upload_state(0, twins)
+            sample = sorted({0, B // 2, B - 1})
+            short, short_curve = a.damage(3, flips=flips, curve=True)
+            for u in sample:
+                curve, rec, _ = host.damage(words[u], kind, tables, 3, flips=flips[u])
+                if short[u].tobytes() != rec.tobytes() or short_curve[u].tolist() != curve.tolist():
+                    raise SystemExit(f"{kind} B={B}: universe {u} is not host.damage's")
+            rec, curve = a.damage(args.steps, flips=flips, curve=True)  # warm-up of the timed shape, and what the loop is held to
+            n_loop = min(args.loop_samples, args.steps)
+            gpu, wall, loop_wall, loop_gpu, floor = [], [], [], [], []
+            for _ in range(args.repeats):
+                a.synchronize()
+                t0 = time.perf_counter()
+                now, now_curve = a.damage(args.steps, flips=flips, curve=True)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                gpu.append(a.damage_gpu_ms())
+                if now.tobytes() != rec.tobytes() or not np.array_equal(now_curve, curve):
+                    raise SystemExit(f"{kind} B={B}: two calls differ")
+                # the loop: samples 0 .. n_loop of the curve from two ensembles in lock step
+                a.synchronize(); b.synchronize()
+                t0 = time.perf_counter()
+                s_ms = 0.0
+                d = [popcounts(a.read_state() ^ b.read_state())]
+                for _t in range(n_loop):
+                    a.step(1)
+                    b.step(1)
+                    d.append(popcounts(a.read_state() ^ b.read_state()))
+                    s_ms += a.stats().gpu_ms + b.stats().gpu_ms  # (the two launches may overlap: an upper bound of their own time)
+                loop_wall.append((time.perf_counter() - t0) * 1e3 * args.steps / n_loop)
+                loop_gpu.append(s_ms * args.steps / n_loop)
+                if not np.array_equal(np.stack(d, axis=1), curve[:, :n_loop + 1]):
+                    raise SystemExit(f"{kind} B={B}: the loop found other distances than the call")
+                # the floor: two plain launches of --steps steps
+                a.upload_state(0, words)
+                b.upload_state(0, twins)
+                a.synchronize(); b.synchronize()
+                a.step(args.steps)
+                a.synchronize()  # one after the other: on two streams at once each launch's events would span the other's work too
+                b.step(args.steps)
+                b.synchronize()
+                floor.append(a.stats().gpu_ms + b.stats().gpu_ms)
+                a.upload_state(0, words)
+                b.upload_state(0, twins)
+            row = {"kernel": kind, "universes": B, "steps": args.steps, "verified_against_host_damage_in": len(sample),
+                   "healed": int((rec["flags"] & 1).sum()), "final_distance_median": float(np.median(rec["final_distance"])),
+                   "damage_gpu_ms": med(gpu), "damage_gpu_ms_all": gpu, "damage_wall_ms": med(wall), "damage_wall_ms_all": wall,
+                   "loop_samples_run": n_loop, "loop_wall_ms_scaled": med(loop_wall), "loop_wall_ms_scaled_all": loop_wall, "loop_step_gpu_ms_scaled": med(loop_gpu),
+                   "two_step_launches_gpu_ms": med(floor), "two_step_launches_gpu_ms_all": floor,
+                   "wall_ratio_loop_over_damage": med(loop_wall) / med(wall), "gpu_ratio_damage_over_two_step_launches": med(gpu) / med(floor)}
+            rows.append(row)
+            print(json.dumps(row))
+    a.close()
+    b.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -1080,12 +1184,14 @@ def main():
     ap.add_argument("--canon", action="store_true", help="measure canon against the read_state + host.canon loop instead (B = 256)")
     ap.add_argument("--canon-period", action="store_true", help="measure canon_period against canon_phases instead (B = 256)")
     ap.add_argument("--envelope", action="store_true", help="measure envelope against the read_state + step(1) loop with numpy OR / AND / popcount instead (B = 256)")
+    ap.add_argument("--damage", action="store_true", help="measure damage against the two-ensemble step(1) + read_state + numpy XOR / popcount loop and against two plain step launches instead (all three kinds; B = 256 1024)")
+    ap.add_argument("--loop-samples", type=int, default=8, help="--damage: samples the replaced loop is run on; its time is scaled to --steps")
     ap.add_argument("--boundary", action="store_true", help="measure step under the torus and closed boundaries against the reference boundary instead (all three kinds; B = 256 1024)")
     ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose, --canon: destinations / universes the CPU loop is run on")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period or args.envelope else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.census_torus or args.boundary else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period or args.envelope else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.census_torus or args.boundary or args.damage else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -1101,6 +1207,29 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.damage:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_damage_64.json")
+        rows = damage_rows(args)
+        result = {
+            "what": "B universes of 64^3 (random fills, seeds 1 .. B) and their twins with one random cell flipped, followed over --steps steps by ONE "
+                    "Ensemble.damage call with the curve — one launch of ca_ensemble_damage_<kind>64, records and curve copied to the host — for von Neumann, "
+                    "Moore and clustered ensembles under this tool's rules; vs. the loop it replaces (two ensembles in lock step: per sample step(1) on each, "
+                    "read_state of both, numpy XOR and byte-table popcounts on the host) and vs. two plain Ensemble.step(--steps) launches, the floor",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "timing": f"damage_gpu_ms: hipEvent time around the launch; damage_wall_ms: host clock around the call; loop_wall_ms_scaled and "
+                      f"loop_step_gpu_ms_scaled: the loop run on loop_samples_run samples, its host clock and the summed hipEvent times of its step launches scaled "
+                      f"by steps / loop_samples_run; two_step_launches_gpu_ms: the summed hipEvent times of the two step launches, run one after the other; medians of {args.repeats} "
+                      "alternating measurements, after records and curves equalled host.damage over 3 steps in the sampled universes; the loop's distances "
+                      "equalled the call's curve in every universe",
+            "not_measured": "the torus and closed kernels, twins in other universes, the image, other step counts, other B, other rules",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.boundary:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_boundary_64.json")
         rows = boundary_rows(args)
