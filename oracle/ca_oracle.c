@@ -329,6 +329,13 @@ int ca3d_oracle_unpacked_step_planes(uint32_t G, const uint32_t *in, uint32_t *o
 {
 	if (G == 0 || (G & (G - 1u)) || lo > hi || hi > nplanes) return -1;
 	const size_t plane = (size_t)G * G;
+	/* every z-neighbour of the range lies inside the array (checked here, so that the rows below can be shared among threads) */
+	if (lo < hi)
+		for (uint32_t i = 0; i + 2 < n_offs; i += 3)
+			if ((int64_t)lo + offs[i + 2] < 0 || (int64_t)(hi - 1u) + offs[i + 2] >= (int64_t)nplanes) return -4;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) collapse(2)
+#endif
 	for (uint32_t j = lo; j < hi; j++)
 		for (uint32_t y = 0; y < G; y++)
 			for (uint32_t x = 0; x < G; x++)
@@ -339,7 +346,6 @@ int ca3d_oracle_unpacked_step_planes(uint32_t G, const uint32_t *in, uint32_t *o
 					const uint32_t nx = (uint32_t)((int32_t)x + offs[i]) % G;
 					const uint32_t ny = (uint32_t)((int32_t)y + offs[i + 1]) % G;
 					const int64_t nj = (int64_t)j + offs[i + 2];
-					if (nj < 0 || nj >= (int64_t)nplanes) return -4;
 					count += in[(size_t)nj * plane + (size_t)ny * G + nx];
 				}
 				const size_t idx = (size_t)j * plane + (size_t)y * G + x;

@@ -40,41 +40,57 @@ def pack(G, cells):
     return np.packbits(c.ravel(), bitorder="little").view("<u4").astype(np.uint32)
 
 
-def graded_state(G, axis, reverse=False, seeds=SEEDS):
+def graded_cells(G, axis, reverse=False, seeds=SEEDS, planes=None):
     """Three independent host.random_fill bit planes number every cell n = 0 .. 7; a cell is alive iff n < min(9 c // G, 8), c its
-    coordinate on `axis` (G - 1 - c reversed): the density rises from 0 to 1 in steps of 1/8 and the last block is full."""
-    n_words = (G // 32) * G * G
-    n = sum(unpack(G, host.random_fill(n_words, seed=s)) << k for k, s in enumerate(seeds))
+    coordinate on `axis` (G - 1 - c reversed): the density rises from 0 to 1 in steps of 1/8 and the last block is full. uint8 [z, y, x];
+    `planes`: that many z planes of G x G cells only (graded along y or x), for plane arrays of grids too large to hold whole."""
+    nz = G if planes is None else planes
+    assert planes is None or axis != "z"
+    n_words = (G // 32) * G * nz
+    n = sum(np.unpackbits(host.random_fill(n_words, seed=s).astype("<u4").view(np.uint8), bitorder="little").reshape(nz, G, G) << k
+            for k, s in enumerate(seeds))
     c = np.arange(G)
     if reverse:
         c = G - 1 - c
     thr = np.minimum(9 * c // G, 8)
     shape = [1, 1, 1]
     shape[AXES[axis]] = G
-    return pack(G, n < thr.reshape(shape))
+    return (n < thr.reshape(shape)).astype(np.uint8)
 
 
-def _neighbour(cells, d, axis):
-    """cells at coordinate + d on `axis` with the project's boundary: coordinate -1 is dead, coordinate G wraps to 0."""
+def graded_state(G, axis, reverse=False, seeds=SEEDS):
+    """graded_cells as packed words."""
+    return pack(G, graded_cells(G, axis, reverse, seeds))
+
+
+def unpacked_state(G, name):
+    """The graded state of an orientation in the one-u32-per-cell layout: cell (x, y, z) at index x + G y + G^2 z."""
+    axis, reverse = ORIENTATIONS[name]
+    return graded_cells(G, axis, reverse).astype(np.uint32).ravel()
+
+
+def _neighbour(cells, d, axis, torus=False):
+    """cells at coordinate + d on `axis` with the project's boundary: coordinate -1 is dead, coordinate G wraps to 0. `torus`: both
+    wrap (np.roll alone) — the one-u32-per-cell layout on a power-of-two grid (compute.wgsl:27: `% G` of a wrapped u32)."""
     if d == 0:
         return cells
     out = np.roll(cells, -d, axis=axis)
-    if d < 0:
+    if d < 0 and not torus:
         idx = [slice(None)] * 3
         idx[axis] = 0
         out[tuple(idx)] = 0
     return out
 
 
-def _sum_classes(planes, dtype):
+def _sum_classes(planes, dtype, torus=False):
     """planes[dz + 1]: the cells at z + dz (boundary already applied) -> [own cell, F, E, C, F2, M2]: the shifted copies added up by the
-    number of axes they moved along; F2 / M2 take the dz = 0 copies only."""
+    number of axes they moved along; F2 / M2 take the dz = 0 copies only. `torus`: y and x wrap on both sides."""
     out = [np.zeros(planes[1].shape, dtype=dtype) for _ in range(6)]
     for dz in (-1, 0, 1):
         for dy in (-1, 0, 1):
-            sy = _neighbour(planes[dz + 1], dy, 1)
+            sy = _neighbour(planes[dz + 1], dy, 1, torus)
             for dx in (-1, 0, 1):
-                v = _neighbour(sy, dx, 2)
+                v = _neighbour(sy, dx, 2, torus)
                 out[abs(dx) + abs(dy) + abs(dz)] += v
                 if dz == 0 and (dx or dy):
                     out[5] += v
@@ -101,18 +117,27 @@ def _as_dict(s):
     return {"F": s[1], "E": s[2], "C": s[3], "T": s[1] + s[2] + s[3], "F2": s[4], "M2": s[5]}
 
 
-def counts_of(G, words, dtype=np.int32):
-    """dict(F, E, C, T) of class_counts and (F2, M2) of plane_counts."""
-    cells = unpack(G, words)
-    return _as_dict(_sum_classes([_neighbour(cells, dz, 0) for dz in (-1, 0, 1)], dtype))
+def counts_of_cells(cells, dtype=np.int32, torus=False):
+    """counts_of for 0 / 1 cells [z, y, x] as they are (any uint type)."""
+    return _as_dict(_sum_classes([_neighbour(cells, dz, 0, torus) for dz in (-1, 0, 1)], dtype, torus))
 
 
-def counts_of_planes(G, words, lo, hi, dtype=np.int32):
+def counts_of(G, words, dtype=np.int32, torus=False):
+    """dict(F, E, C, T) of class_counts and (F2, M2) of plane_counts; `torus`: no dead face, every axis wraps on both sides."""
+    return counts_of_cells(unpack(G, words), dtype, torus)
+
+
+def cells_counts_of_planes(cells, lo, hi, dtype=np.int32, torus=False):
+    """(alive, counts) of the z planes lo .. hi - 1 of cells [z, y, x], 1 <= lo < hi <= len(cells) - 1 (no z boundary inside)."""
+    assert 1 <= lo < hi <= len(cells) - 1
+    return cells[lo:hi], _as_dict(_sum_classes([cells[lo + dz:hi + dz] for dz in (-1, 0, 1)], dtype, torus))
+
+
+def counts_of_planes(G, words, lo, hi, dtype=np.int32, torus=False):
     """(alive, counts_of) of the z planes lo .. hi - 1 alone, 1 <= lo < hi <= G - 1 (no z boundary inside): arrays [hi - lo, y, x]. What a
     large grid's check needs without 27 full-size copies."""
     assert 1 <= lo < hi <= G - 1
-    cells = unpack(G, words)
-    return cells[lo:hi], _as_dict(_sum_classes([cells[lo + dz:hi + dz] for dz in (-1, 0, 1)], dtype))
+    return cells_counts_of_planes(unpack(G, words), lo, hi, dtype, torus)
 
 
 def lookup(alive, count, born, survive):
@@ -216,8 +241,12 @@ def next_state(G, words, kind, rule, counts=None):
     return pack(G, next_cells(unpack(G, words), counts_of(G, words) if counts is None else counts, kind, rule))
 
 
-def coverage(G, words, counts=None):
-    """{"T" | "F" | "E" | "C" | "F2" | "M2": int64 [2, N]}: how many (alive, count) pairs of each kind the state holds."""
-    alive = unpack(G, words).astype(np.int16)
-    n = counts_of(G, words) if counts is None else counts
+def coverage_of_cells(alive, n):
+    """coverage from 0 / 1 cells and their counts (counts_of_cells / cells_counts_of_planes)."""
+    alive = alive.astype(np.int16)
     return {k: np.bincount((alive * N + n[k]).ravel(), minlength=2 * N).reshape(2, N) for k, N in SIZES.items()}
+
+
+def coverage(G, words, counts=None, torus=False):
+    """{"T" | "F" | "E" | "C" | "F2" | "M2": int64 [2, N]}: how many (alive, count) pairs of each kind the state holds."""
+    return coverage_of_cells(unpack(G, words), counts_of(G, words, torus=torus) if counts is None else counts)

@@ -346,3 +346,64 @@ def launches(nz, K, batches, dead_bottom, phased):
                 if lens:
                     out.append(lens)
     return out
+
+
+def wide_states(G, wide, r, steps):
+    """States 0 .. steps of a plane array of the one-u32-per-cell layout that is nobody's slab: sub-step s is `ol.unpacked_step_planes`
+    over planes [s, W - s), so state s is right on those planes (and zero outside them). Read-only, like a Trajectory's."""
+    W = wide.size // (G * G)
+    out = [np.ascontiguousarray(wide, dtype=np.uint32)]
+    for s in range(1, steps + 1):
+        assert W - 2 * s > 0
+        out.append(ol.unpacked_step_planes(G, out[-1], s, W - s, r.main, r.survive, r.born))
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def run_lone_slab_planes(eng, G, states, r, z0, nz, K, batches, phased, options=(), after_batch=None):
+    """run_lone_slab for a grid too large for a full-grid oracle state (unpacked layout): `states` are `wide_states` of an array of
+    W = nz + 4 K planes, of which the slab's plane array is planes K .. W - K - 1 and its owned planes 2 K .. 2 K + nz - 1; state n <= K is
+    right on every plane of the slab's array, ghosts included. Every batch starts again from state 0 (there is no state to refresh the
+    ghosts from for a second batch in a row) and is compared on the owned planes; the phased form also on what the edge phase sends."""
+    pw = G * G
+    W = states[0].size // pw
+    assert W == nz + 4 * K and len(states) > max(batches)
+    what = f"G {G} plane array, slab z0 {z0} nz {nz} K {K} {'phased' if phased else 'whole'}"
+
+    def planes(st, first, count):
+        return st[first * pw:(first + count) * pw]
+
+    def ghosts(st):
+        eng.synchronize()
+        low, high = planes(st, K, K), planes(st, 2 * K + nz, K)
+        _write_region(eng, SLAB_RECV_LOW, low)
+        _write_region(eng, SLAB_RECV_HIGH, high)
+        return low, high
+
+    eng.configure_slab(G, z0, nz, K, LAYOUT_UNPACKED)
+    for name, value in options:
+        eng.set_option(name, value)
+    eng.set_rules(r.main, r.edges, r.corners, r.survive, r.born)
+    for n in batches:
+        assert 1 <= n <= K
+        at = f"{what}, batch of {n}"
+        now = states[n]
+        eng.upload_state(planes(states[0], 2 * K, nz))
+        ghosts(states[0])
+        if not phased:
+            eng.slab_step(n)
+            eng.synchronize()
+        else:
+            eng.slab_step_phase(n, SLAB_PHASE_EDGES)
+            eng.synchronize()
+            _equal(_read_region(eng, SLAB_SEND_LOW), planes(now, 2 * K, K), at + ": send_low after the edge phase", G, LAYOUT_UNPACKED, z0)
+            _equal(_read_region(eng, SLAB_SEND_HIGH), planes(now, K + nz, K), at + ": send_high after the edge phase", G, LAYOUT_UNPACKED, z0 + nz - K)
+            low, high = ghosts(now)
+            eng.slab_step_phase(n, SLAB_PHASE_INTERIOR)
+            eng.synchronize()
+            _equal(_read_region(eng, SLAB_RECV_LOW), low, at + ": recv_low after the interior phase", G, LAYOUT_UNPACKED, z0 - K)
+            _equal(_read_region(eng, SLAB_RECV_HIGH), high, at + ": recv_high after the interior phase", G, LAYOUT_UNPACKED, z0 + nz)
+        _equal(eng.read_state(), planes(now, 2 * K, nz), at + ": owned planes", G, LAYOUT_UNPACKED, z0)
+        if after_batch is not None:
+            after_batch(n)

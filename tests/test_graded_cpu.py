@@ -269,3 +269,89 @@ def test_the_families_decide_something(G):
         for name in rc.starts(c):
             nxt = ol.packed_step(G, state(G, name), rc.rules_of(c.kind, c.rule))
             assert nxt.any() and (nxt != state(G, name)).any(), (c.id, name, G)
+
+
+# ------------------------------------------------------------------------------------------------ the torus of the one-u32-per-cell layout
+
+def test_the_unpacked_state_is_the_graded_state_one_word_a_cell():
+    G = 32
+    for name in gl.ORIENTATIONS:
+        u = gl.unpacked_state(G, name)
+        assert u.dtype == np.uint32 and u.shape == (G ** 3,) and int(u.max()) == 1
+        cells = gl.unpack(G, state(G, name))
+        np.testing.assert_array_equal(u.reshape(G, G, G), cells)
+        for x, y, z in ((0, 0, 0), (31, 0, 0), (5, 9, 2), (30, 31, 17), (31, 31, 31)):
+            assert u[x + G * y + G * G * z] == cells[z, y, x]
+
+
+def test_the_torus_counts_by_hand():
+    """Coordinate -1 is coordinate G - 1 on every axis: the live cell in the last corner is a neighbour of cell (0, 0, 0) and of the
+    other cells that look at it across a - face; with the packed layout's boundary those see nothing there."""
+    G = 32
+    cells = np.zeros((G, G, G), dtype=np.uint8)
+    cells[31, 31, 31] = 1
+    n = gl.counts_of_cells(cells, torus=True)
+    assert n["C"][0, 0, 0] == n["C"][30, 30, 30] == n["C"][0, 30, 0] == 1 and n["C"].sum() == 8
+    assert n["F"][0, 31, 31] == n["F"][31, 0, 31] == n["F"][31, 31, 0] == n["F"][30, 31, 31] == 1 and n["F"].sum() == 6
+    assert n["E"].sum() == 12 and n["T"].sum() == 26 and n["F2"].sum() == 4 and n["M2"].sum() == 8 and n["M2"][31, 0, 0] == 1
+    dead = gl.counts_of_cells(cells)  # the packed layout's boundary: only the + side wraps
+    assert dead["T"].sum() == 7 and dead["C"][30, 30, 30] == 1 and dead["C"][0, 0, 0] == 0 and dead["M2"][31, 0, 0] == 0
+    np.testing.assert_array_equal(gl.counts_of(G, gl.pack(G, cells), torus=True)["T"], n["T"])
+
+
+@pytest.mark.parametrize("G", [32, 64])
+@pytest.mark.parametrize("name", list(gl.ORIENTATIONS))
+@pytest.mark.parametrize("kind", list(gl.PLAIN))
+def test_torus_counts_give_the_unpacked_oracles_next_state(kind, name, G):
+    """gl.next_cells from the torus counts against ol.unpacked_step (compute.wgsl restated: a torus at a power-of-two grid), every coded
+    rule of every main neighbourhood."""
+    u = gl.unpacked_state(G, name)
+    cells = u.reshape(G, G, G).astype(np.uint8)
+    n = gl.counts_of_cells(cells, torus=True)
+    for rule in gl.coded(gl.TABLES[kind]):
+        r = ol.Rules.from_strings(**gl.strings_of(kind, rule))
+        want = ol.unpacked_step(G, u, r.main, r.survive, r.born)
+        assert want.any() and (want != u).any()
+        np.testing.assert_array_equal(gl.next_cells(cells, n, kind, rule).ravel(), want, err_msg=f"{gl.name_of(kind, rule)} on graded {name}")
+    packed = gl.next_cells(cells, gl.counts_of_cells(cells), kind, gl.coded(gl.TABLES[kind])[0])
+    assert (packed != gl.next_cells(cells, n, kind, gl.coded(gl.TABLES[kind])[0])).any()  # the dead faces would show
+
+
+TORUS_FLOOR = 16  # the rarest pair: (alive, T) at 32^3, graded z
+
+
+@pytest.mark.parametrize("G", [32, 64, 128])
+@pytest.mark.parametrize("name", ["z", "x"])
+def test_every_count_occurs_on_the_torus(G, name):
+    """What test_gpu_unpacked_rule_tables.py rests on: every (alive, count) pair of T (27), F (7), E (13), C (9), F2 (5) and M2 (9) under
+    torus counts, in the two states every id there starts from."""
+    cells = gl.unpacked_state(G, name).reshape(G, G, G).astype(np.uint8)
+    cov = gl.coverage_of_cells(cells, gl.counts_of_cells(cells, dtype=np.int8, torus=True))
+    print(f"graded {name} at {G}^3, torus: smallest number of occurrences of an (alive, count) pair", {k: int(v.min()) for k, v in cov.items()})
+    assert {k: v.shape for k, v in cov.items()} == {k: (2, N) for k, N in gl.SIZES.items()}
+    for k, v in cov.items():
+        assert v.min() >= TORUS_FLOOR, f"{k}: (alive, count) pair {np.unravel_index(v.argmin(), v.shape)} occurs {v.min()} times in graded {name} at {G}"
+
+
+def _range_coverage(cells, ranges):
+    cov = {k: np.zeros((2, N), dtype=np.int64) for k, N in gl.SIZES.items()}
+    for lo, hi in ranges:
+        alive, n = gl.cells_counts_of_planes(cells, lo, hi, dtype=np.int8, torus=True)
+        for k, v in gl.coverage_of_cells(alive, n).items():
+            cov[k] += v
+    return cov
+
+
+@pytest.mark.parametrize("G,name", [(256, "z"), (256, "x"), (512, "z"), (512, "x"), (1024, "x")])
+def test_every_count_occurs_on_the_torus_at_the_larger_grids(G, name):
+    """The same on a part of the planes (what occurs there occurs in the grid): four planes of a state graded along x, four around each
+    of the eight density steps of one graded along z — and, at 1024, four planes of the plane array the thin slab there is cut from."""
+    if G == 1024:
+        cells, ranges = gl.graded_cells(G, "x", planes=21 + 4 * 3), [(14, 18)]  # (test_gpu_unpacked_rule_tables.THIN_1024: nz 21, K 3)
+    else:
+        cells = gl.graded_cells(G, *gl.ORIENTATIONS[name])
+        ranges = [(b - 2, b + 2) for b in (-(-k * G // 9) for k in range(1, 9))] if name == "z" else [(G // 2, G // 2 + 4)]
+    cov = _range_coverage(cells, ranges)
+    print(f"graded {name} at {G}, torus, planes {ranges}: smallest number of occurrences", {k: int(v.min()) for k, v in cov.items()})
+    for k, v in cov.items():
+        assert v.min() >= 32, f"{k}: (alive, count) pair {np.unravel_index(v.argmin(), v.shape)} occurs {v.min()} times in graded {name} at {G}"
