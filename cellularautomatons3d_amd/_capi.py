@@ -122,6 +122,12 @@ class DamageStruct(C.Structure):
                 ("damage_min", C.c_uint8 * 4), ("damage_max", C.c_uint8 * 4), ("touched_min", C.c_uint8 * 4), ("touched_max", C.c_uint8 * 4)]
 
 
+class UsageStruct(C.Structure):
+    """ca3d_usage (include/ca3d.h): what `ca3d_ensemble_usage` says of one universe, 432 bytes (`host.USAGE_DTYPE`)."""
+    _fields_ = [("steps", C.c_uint32), ("flags", C.c_uint32), ("used_born", C.c_uint32 * 3), ("used_survive", C.c_uint32 * 3),
+                ("dead", C.c_uint32 * 49), ("alive", C.c_uint32 * 49), ("reserved", C.c_uint32 * 2)]
+
+
 #: the flag bits of `ca3d_ensemble_damage`
 DAMAGE_IMAGE_DAMAGE = 0x1
 DAMAGE_COPY_RULES = 0x100
@@ -248,6 +254,7 @@ SYMBOLS = [
                                          C.POINTER(C.c_float)]),
     ("ca3d_ensemble_damage", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _H, C.c_uint32, C.c_uint32, C.POINTER(DamageStruct),
                                        _u32p, C.c_uint32, C.POINTER(C.c_float)]),
+    ("ca3d_ensemble_usage", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.POINTER(UsageStruct), C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -110,6 +110,9 @@ struct ca3d_ensemble
 	Scratch damage;
 	Timer damage_time;
 	hipEvent_t damage_src = nullptr;
+	// ca3d_ensemble_usage: the records of the call under way, [count] of 432 bytes, then the uploaded step counts, [count] words
+	Scratch usage;
+	Timer usage_time;
 };
 
 namespace
@@ -134,7 +137,7 @@ void free_arrays(ca3d_ensemble *e)
 	e->sheet_counters = nullptr;
 	e->sheet_px = 0;
 	e->sheet_drawn = false;
-	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon, &e->envelope, &e->damage})
+	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon, &e->envelope, &e->damage, &e->usage})
 	{
 		if (s->array) hipFree(s->array);
 		*s = Scratch{};
@@ -599,7 +602,7 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	hipSetDevice(e->device);
 	if (e->stream) hipStreamSynchronize(e->stream);
 	free_arrays(e);
-	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time, e->envelope_time, e->damage_time})
+	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time, e->envelope_time, e->damage_time, e->usage_time})
 		for (hipEvent_t ev : {t.start, t.stop})
 			if (ev) hipEventDestroy(ev);
 	for (hipEvent_t ev : {e->ev_seed, e->isolate_src, e->compose_src, e->envelope_src, e->damage_src})
@@ -1380,6 +1383,44 @@ int ca3d_ensemble_damage(ca3d_ensemble_t *src, uint32_t first, uint32_t count, c
 	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, src->stream));
 	HIP_TRY(hipStreamSynchronize(src->stream));
 	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, src->damage_time.start, src->damage_time.stop));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_ensemble_usage(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *steps, ca3d_usage *out, float *gpu_ms) CA3D_API_TRY
+{
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!steps) return fail(CA3D_ERR_INVALID_ARGUMENT, "steps is NULL");
+	if (!out) return fail(CA3D_ERR_INVALID_ARGUMENT, "out is NULL");
+	int rc = check_range(e, first, count);
+	if (rc) return rc;
+	for (uint32_t k = 0; k < count; k++)
+		if (steps[k] == 0 || steps[k] > CA3D_CANON_MAX_PERIOD)
+			return fail(CA3D_ERR_INVALID_ARGUMENT, "steps[%u] is %u (universe %u): a step count is 1 .. %u", k, steps[k], first + k, (unsigned)CA3D_CANON_MAX_PERIOD);
+	if ((rc = require_state(e, first, count))) return rc;
+	for (uint32_t u = first; u < first + count; u++)
+		if (!e->has_rules[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_set_rules has not been called for universe %u", u);
+	HIP_TRY(hipSetDevice(e->device));
+	const size_t rec_bytes = (size_t)count * sizeof(ca3d_usage), step_bytes = (size_t)count * sizeof(uint32_t), bytes = rec_bytes + step_bytes;
+	if ((rc = reserve(e, e->usage, bytes, &e->usage_time, nullptr, "%zu bytes of usage records", bytes))) return rc;
+	UsageLaunch l{};
+	l.state = e->state;
+	l.rules = e->rules;
+	l.neighbourhood = e->neighbourhood;
+	l.clustered = e->clustered;
+	l.boundary = e->boundary;
+	l.first = first; l.count = count;
+	l.out = e->usage.at<ca3d_usage>();
+	uint32_t *steps_dev = e->usage.at<uint32_t>(rec_bytes);
+	l.steps = steps_dev;
+	// (from pageable memory: the copy has left the caller's array when the call returns)
+	HIP_TRY(hipMemcpyAsync(steps_dev, steps, step_bytes, hipMemcpyHostToDevice, e->stream));
+	HIP_TRY(hipEventRecord(e->usage_time.start, e->stream));
+	HIP_TRY(launch_usage(l, e->stream));
+	HIP_TRY(hipEventRecord(e->usage_time.stop, e->stream));
+	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, e->stream));
+	HIP_TRY(hipStreamSynchronize(e->stream));
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->usage_time.start, e->usage_time.stop));
 	return CA3D_OK;
 }
 CA3D_API_CATCH

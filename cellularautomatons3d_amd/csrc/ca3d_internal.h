@@ -358,6 +358,22 @@ struct DamageLaunch
 	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
 };
 hipError_t launch_damage(const DamageLaunch &l, hipStream_t stream);
+// ca_usage.hip: the histograms of the neighbour counts that steps[k] steps of universe first + k look up in its rule tables, split by
+// dead and alive, for universes [first, first + count) of an ensemble's state and rule arrays (ca3d_ensemble_usage), one workgroup each
+// of ca_ensemble_usage_{vn,moore,clustered}64[_torus|_closed] by the ensemble's kind and boundary; out and steps are indexed by
+// universe - first. The caller has checked the range and every step count. States and rules are only read.
+struct UsageLaunch
+{
+	const uint32_t *state; // [B][8192], the ensemble's current states
+	const uint32_t *rules; // [B][ensemble_rule_words()]
+	int neighbourhood;
+	bool clustered;
+	int boundary;          // CA3D_ENSEMBLE_BOUNDARY_*
+	uint32_t first, count;
+	const uint32_t *steps; // device, [count]
+	ca3d_usage *out;       // device, [count]: every word is written
+};
+hipError_t launch_usage(const UsageLaunch &l, hipStream_t stream);
 // render_sheet.hip: universes [first, first + count) of an ensemble's state array drawn as tiles of one sheet, columns x
 // ceil(count / columns) tiles of tile_w x tile_h pixels (multiples of 16), row-major, in one launch of ca_render_sheet64; the tile
 // slots past `count` are zeroed in front of it. The caller has checked every size.

@@ -460,6 +460,32 @@ class Ensemble:
         """hipEvent time of the last `damage` launch of this object, in milliseconds (None before the first)."""
         return getattr(self, "_damage_ms", None)
 
+    def usage(self, steps, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """`ca3d_ensemble_usage`: WHICH entries of its rule tables universe first + k reads over steps[k] steps of its own, taken INSIDE
+        one launch behind the queued steps under this ensemble's rule and boundary; this ensemble is left exactly as it is -> records
+        of `host.USAGE_DTYPE`: `dead[base + c]` / `alive[base + c]`, the cells dead / alive with count c summed over the steps, per
+        class (`host.USAGE_CLASSES`: main, edges, corners; von Neumann and Moore fill main only), and `used_born` / `used_survive`,
+        the masks of the table bits that were read. `steps` is one number for every universe of the range (`count` universes from
+        `first` on, default: to the end), or one per universe, each 1 .. `host.CANON_MAX_PERIOD`. `host.usage` is the same on the CPU
+        for one universe, `host.usage_dont_care` and `host.usage_births_deaths` read a record; `usage_gpu_ms()` tells what the launch
+        took."""
+        p = _as_u32(steps).ravel()
+        if np.ndim(steps) == 0:
+            p = np.full(max(self.n - first, 0) if count is None else count, p[0], dtype=np.uint32)
+        elif count is not None and count != p.size:
+            raise ValueError(f"{p.size} step counts for {count} universes")
+        p = np.ascontiguousarray(p)
+        rec = np.zeros(p.size, dtype=host.USAGE_DTYPE)
+        ms = C.c_float(0.0)
+        _capi.check(self._lib.ca3d_ensemble_usage(self._h, first, p.size, p.ctypes.data_as(_u32p), rec.ctypes.data_as(C.POINTER(_capi.UsageStruct)),
+                                                  C.byref(ms)))
+        self._usage_ms = float(ms.value)
+        return rec
+
+    def usage_gpu_ms(self) -> float:
+        """hipEvent time of the last `usage` launch of this object, in milliseconds (None before the first)."""
+        return getattr(self, "_usage_ms", None)
+
     def canon_phases(self, periods, first: int = 0, count: Optional[int] = None,
                      max_period: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """`canon` over a whole period, for universes already classified as oscillators or ships (`step_until_cycle`,

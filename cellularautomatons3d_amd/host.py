@@ -586,15 +586,11 @@ def _table(mask: int, n: int) -> np.ndarray:
     return ((int(mask) >> np.arange(n)) & 1).astype(np.uint8)
 
 
-def ensemble_step(words, kind: str, tables, boundary: str = "reference") -> np.ndarray:
-    """One step of ONE packed 64^3 universe (8192 words) -> its packed successor, in plain numpy on the unpacked [z, y, x] array.
-
-    `kind`: "von neumann" (counts 0 .. 6 over the six face neighbours), "moore" (0 .. 26) or "clustered". `tables`: the masks
-    `Ensemble.set_rule_tables` / `set_clustered_tables` take — (born, survive), bit c = at count c; clustered: (born[3], survive[3]) for
-    the main (Moore, 0 .. 26), edges (0 .. 12) and corners (0 .. 8) rule-sets, whose three lookups are ORed; a live cell looks up
-    survive at its count, a dead one born. `boundary`: "reference", "torus" or "closed".
-    Every axis applies its boundary to what the axis before it produced — x, then y, then z — so an edge or corner neighbour exists
-    exactly when each of its three coordinates does; the counts are formed separably for that reason."""
+def _ensemble_counts(words, kind: str, boundary: str):
+    """(cells [z, y, x] of one packed 64^3 universe, the counts its step looks up): one array for "von neumann" (F, 0 .. 6) and "moore"
+    (0 .. 26), the three (T, E, C) of the main, edges and corners tables for "clustered". Every axis applies its boundary to what the
+    axis before it produced — x, then y, then z — so an edge or corner neighbour exists exactly when each of its three coordinates
+    does; the counts are formed separably for that reason."""
     if kind not in ENSEMBLE_KINDS:
         raise ValueError(f"unknown ensemble kind {kind!r}: one of {ENSEMBLE_KINDS}")
     if boundary not in ENSEMBLE_BOUNDARIES:
@@ -609,26 +605,41 @@ def ensemble_step(words, kind: str, tables, boundary: str = "reference") -> np.n
     def both(v, axis):  # the two neighbours along one axis, summed
         return _neighbour(v, axis, -1, boundary) + _neighbour(v, axis, +1, boundary)
 
-    alive = a.astype(bool)
-    born, survive = tables
     if kind == "von neumann":
-        count = both(a, X) + both(a, Y) + both(a, Z)
-        nxt = np.where(alive, _table(survive, 7)[count], _table(born, 7)[count])
-    elif kind == "moore":
+        return a, (both(a, X) + both(a, Y) + both(a, Z),)
+    if kind == "moore":
         s = a
         for axis in (X, Y, Z):
             s = s + both(s, axis)
-        count = s - a  # the 3 x 3 x 3 sum without the cell itself
-        nxt = np.where(alive, _table(survive, 27)[count], _table(born, 27)[count])
+        return a, (s - a,)  # the 3 x 3 x 3 sum without the cell itself
+    left, right = _neighbour(a, X, -1, boundary), _neighbour(a, X, +1, boundary)
+    faces_in_plane = left + right + both(a, Y)            # the 4 face neighbours in the cell's own plane
+    diagonals_in_plane = both(left, Y) + both(right, Y)   # the 4 in-plane diagonals
+    faces = faces_in_plane + both(a, Z)                   # 0 .. 6
+    edges = diagonals_in_plane + both(faces_in_plane, Z)  # 0 .. 12
+    corners = both(diagonals_in_plane, Z)                 # 0 .. 8
+    return a, (faces + edges + corners, edges, corners)
+
+
+def ensemble_step(words, kind: str, tables, boundary: str = "reference") -> np.ndarray:
+    """One step of ONE packed 64^3 universe (8192 words) -> its packed successor, in plain numpy on the unpacked [z, y, x] array.
+
+    `kind`: "von neumann" (counts 0 .. 6 over the six face neighbours), "moore" (0 .. 26) or "clustered". `tables`: the masks
+    `Ensemble.set_rule_tables` / `set_clustered_tables` take — (born, survive), bit c = at count c; clustered: (born[3], survive[3]) for
+    the main (Moore, 0 .. 26), edges (0 .. 12) and corners (0 .. 8) rule-sets, whose three lookups are ORed; a live cell looks up
+    survive at its count, a dead one born. `boundary`: "reference", "torus" or "closed".
+    Every axis applies its boundary to what the axis before it produced — x, then y, then z — so an edge or corner neighbour exists
+    exactly when each of its three coordinates does; the counts are formed separably for that reason (`_ensemble_counts`)."""
+    a, counts = _ensemble_counts(words, kind, boundary)
+    alive = a.astype(bool)
+    born, survive = tables
+    if kind == "von neumann":
+        nxt = np.where(alive, _table(survive, 7)[counts[0]], _table(born, 7)[counts[0]])
+    elif kind == "moore":
+        nxt = np.where(alive, _table(survive, 27)[counts[0]], _table(born, 27)[counts[0]])
     else:
-        left, right = _neighbour(a, X, -1, boundary), _neighbour(a, X, +1, boundary)
-        faces_in_plane = left + right + both(a, Y)            # the 4 face neighbours in the cell's own plane
-        diagonals_in_plane = both(left, Y) + both(right, Y)   # the 4 in-plane diagonals
-        faces = faces_in_plane + both(a, Z)                   # 0 .. 6
-        edges = diagonals_in_plane + both(faces_in_plane, Z)  # 0 .. 12
-        corners = both(diagonals_in_plane, Z)                 # 0 .. 8
         nxt = np.zeros_like(a)
-        for count, n, b, s in ((faces + edges + corners, 27, born[0], survive[0]), (edges, 13, born[1], survive[1]), (corners, 9, born[2], survive[2])):
+        for count, n, b, s in zip(counts, (27, 13, 9), born, survive):
             nxt |= np.where(alive, _table(s, n)[count], _table(b, n)[count])
     return np.packbits(nxt.astype(np.uint8).ravel(), bitorder="little").view("<u4").copy()
 
@@ -1115,6 +1126,86 @@ def damage(state, kind: str, tables, steps: int, boundary: str = "reference", tw
             s, t = s1, t1
 
     return _damage_over(pairs(s0, damage_twin(s0, twin, flips)), p)
+
+
+# --------------------------------------------------------------------------------------------------- usage
+# The definition of ca3d_ensemble_usage (include/ca3d.h) in executable form, for one universe.
+
+USAGE_MAIN, USAGE_EDGES, USAGE_CORNERS, USAGE_BINS = 0, 27, 40, 49
+USAGE_CLASSES = {"main": (USAGE_MAIN, 27), "edges": (USAGE_EDGES, 13), "corners": (USAGE_CORNERS, 9)}  # class -> (first bin, bins)
+USAGE_DTYPE = np.dtype([("steps", "<u4"), ("flags", "<u4"), ("used_born", "<u4", (3,)), ("used_survive", "<u4", (3,)),
+                        ("dead", "<u4", (USAGE_BINS,)), ("alive", "<u4", (USAGE_BINS,)), ("reserved", "<u4", (2,))])
+assert USAGE_DTYPE.itemsize == 432
+
+
+def _usage_classes(kind: str):
+    """(first bin, bins) of the tables a kind looks up, in the order of `_ensemble_counts`."""
+    if kind not in ENSEMBLE_KINDS:
+        raise ValueError(f"unknown ensemble kind {kind!r}: one of {ENSEMBLE_KINDS}")
+    if kind == "von neumann":
+        return ((USAGE_MAIN, 7),)
+    if kind == "moore":
+        return ((USAGE_MAIN, 27),)
+    return tuple(USAGE_CLASSES.values())
+
+
+def usage_of_phases(states, kind: str, boundary: str = "reference") -> np.ndarray:
+    """The usage record (USAGE_DTYPE, shape ()) of the phases S_0 .. S_(P-1), packed 64^3 states: dead[base + c] / alive[base + c] is
+    the number of (t, cell) pairs whose cell is dead / alive in S_t with count c in the class that starts at bin `base`
+    (`USAGE_CLASSES`; von Neumann and Moore fill the main class only), the counts as `ensemble_step` forms them under `boundary`;
+    used_born[i] / used_survive[i] has bit c set where dead / alive[base_i + c] is not zero."""
+    states = list(states)
+    if not 1 <= len(states) <= CANON_MAX_PERIOD:
+        raise ValueError(f"a step count is 1 .. {CANON_MAX_PERIOD}")
+    classes = _usage_classes(kind)
+    hist = np.zeros((2, USAGE_BINS), dtype=np.int64)
+    for s in states:
+        a, counts = _ensemble_counts(s, kind, boundary)
+        for (base, n), count in zip(classes, counts):
+            hist[:, base:base + n] += np.bincount((a.astype(np.int64) * n + count).ravel(), minlength=2 * n).reshape(2, n)
+    rec = np.zeros((), dtype=USAGE_DTYPE)
+    rec["steps"] = len(states)
+    rec["dead"], rec["alive"] = hist[0], hist[1]
+    for i, (base, n) in enumerate(USAGE_CLASSES.values()):
+        rec["used_born"][i] = sum(1 << c for c in range(n) if hist[0, base + c])
+        rec["used_survive"][i] = sum(1 << c for c in range(n) if hist[1, base + c])
+    return rec
+
+
+def usage(state, kind: str, tables, steps: int, boundary: str = "reference") -> np.ndarray:
+    """`ca3d_ensemble_usage` for ONE packed 64^3 universe, in plain numpy over `ensemble_step`: `usage_of_phases` of S_0 = `state` and
+    its `steps` - 1 successors under the rule `kind`, `tables` and `boundary`, as `ensemble_step` takes them."""
+    p = int(steps)
+    if not 1 <= p <= CANON_MAX_PERIOD:
+        raise ValueError(f"a step count is 1 .. {CANON_MAX_PERIOD}")
+    phases = [np.ascontiguousarray(state, dtype="<u4").ravel().astype(np.uint32)]
+    for _ in range(p - 1):
+        phases.append(ensemble_step(phases[-1], kind, tables, boundary))
+    return usage_of_phases(phases, kind, boundary)
+
+
+def usage_dont_care(record, kind: str) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """(born[3], survive[3]): per class (main, edges, corners) the mask of table bits the run behind `record` never read. Flipping
+    any of them leaves every state of that run as it is. A class the kind does not look up has no bits at all (0)."""
+    born, survive = [0, 0, 0], [0, 0, 0]
+    for i, (_, n) in enumerate(_usage_classes(kind)):  # (the classes a kind looks up come first)
+        full = (1 << n) - 1
+        born[i] = full & ~int(record["used_born"][i])
+        survive[i] = full & ~int(record["used_survive"][i])
+    return tuple(born), tuple(survive)
+
+
+def usage_births_deaths(record, kind: str, tables) -> Tuple[int, int]:
+    """(births, deaths) summed over the steps of the run behind `record`: the sum over c of dead[c] born_c and of
+    alive[c] (1 - survive_c). Exact for "von neumann" and "moore"; a clustered cell's three lookups are ORed, which the three
+    histograms do not determine: ValueError."""
+    if kind == "clustered":
+        raise ValueError("a clustered universe's three lookups are ORed: births and deaths do not follow from the histograms")
+    ((base, n),) = _usage_classes(kind)
+    born, survive = tables
+    births = sum(int(record["dead"][base + c]) for c in range(n) if int(born) >> c & 1)
+    deaths = sum(int(record["alive"][base + c]) for c in range(n) if not int(survive) >> c & 1)
+    return births, deaths
 
 
 # ------------------------------------------------------------------------------------------------ renderer

@@ -1589,6 +1589,39 @@ static napi_value js_ensemble_damage(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* ensembleUsage(handle, first, Uint32Array(count) steps, Uint32Array(count * 108) records) -> gpuMs: which entries of their rule tables
+ * universes [first, first + count) read over steps[k] steps of their own, taken inside the kernel (ca3d_ensemble_usage); a record is
+ * ca3d_usage's 108 words: steps, flags, usedBorn[3], usedSurvive[3], dead[49], alive[49], 0, 0 (js/ca3d.js opens them) */
+static napi_value js_ensemble_usage(napi_env env, napi_callback_info info)
+{
+	napi_value argv[4];
+	if (!get_args(env, info, 4, argv)) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[0]);
+	if (!e) return NULL;
+	uint32_t first;
+	void *steps, *recs;
+	size_t count, nrecs;
+	if (!get_u32(env, argv[1], &first) || !get_typed(env, argv[2], napi_uint32_array, 0, &steps, &count) ||
+	    !get_typed(env, argv[3], napi_uint32_array, 0, &recs, &nrecs))
+		return NULL;
+	_Static_assert(sizeof(ca3d_usage) == 432, "a record crosses as 108 words");
+	if (count > 0xFFFFFFFFu || nrecs != count * (sizeof(ca3d_usage) / 4u))
+	{
+		napi_throw_range_error(env, NULL, "records must hold 108 words a universe");
+		return NULL;
+	}
+	float ms = 0.f;
+	/* (count 0: the library refuses the call and names the reason; it reads and writes no array, and an empty typed array may have no
+	 * address at all) */
+	uint32_t none[1];
+	if (!count) steps = recs = none;
+	int rc = ca3d_ensemble_usage(e, first, (uint32_t)count, (const uint32_t *)steps, (ca3d_usage *)recs, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+
 static napi_value js_ensemble_synchronize(napi_env env, napi_callback_info info)
 {
 	napi_value argv[1];
@@ -1816,6 +1849,7 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleCanon", js_ensemble_canon},
 	    {"ensembleCanonPeriod", js_ensemble_canon_period},
 	    {"ensembleEnvelope", js_ensemble_envelope},
+	    {"ensembleUsage", js_ensemble_usage},
 	    {"ensembleDamage", js_ensemble_damage}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{

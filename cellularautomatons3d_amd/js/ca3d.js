@@ -797,6 +797,27 @@ class Ensemble
 		for (let k = 0; k < p.length; k++) curve.push(samples.slice(k * stride, k * stride + p[k] + 1));
 		return { records, curve, gpuMs };
 	}
+	/** Rule usage (ca3d_ensemble_usage): WHICH entries of its rule tables universe opts.first + k reads over steps[k] steps of its own,
+	 *  taken INSIDE one launch behind the queued steps under this ensemble's rule and boundary; this ensemble is left exactly as it is.
+	 *  steps: one number for every universe from opts.first on, or an array with one step count per universe, each 1 .. 4096
+	 *  -> {records, gpuMs}, records[k] = {steps, usedBorn, usedSurvive ([main, edges, corners]: bit c set where a dead / live cell with
+	 *  count c occurred, that is, where born_c / survive_c was read), dead, alive (Uint32Array(49): the cells dead / alive with count c,
+	 *  summed over the steps, at bin base + c; main from bin 0, edges from 27, corners from 40; von Neumann and Moore fill main only)}. */
+	usage(steps, opts)
+	{
+		const o = Object.assign({ first: 0 }, opts || {});
+		const count = Math.max(this.n - o.first, 0);
+		const p = typeof steps === "number" ? new Uint32Array(count).fill(steps) : Uint32Array.from(steps);
+		const words = new Uint32Array(p.length * 108);
+		const gpuMs = this._a.ensembleUsage(this._e, o.first, p, words);
+		const records = [];
+		for (let k = 0; k < p.length; k++)
+		{
+			const r = words.subarray(108 * k, 108 * k + 108);
+			records.push({ steps: r[0], usedBorn: Array.from(r.subarray(2, 5)), usedSurvive: Array.from(r.subarray(5, 8)), dead: r.slice(8, 57), alive: r.slice(57, 106) });
+		}
+		return { records, gpuMs };
+	}
 	/** The contact sheet (ca3d_ensemble_render_sheet): universes first .. first + count - 1 (default: all from `first`) as tiles of one
 	 *  image, one launch; tile k — column k % columns, row floor(k / columns) — is the frame Engine.render draws of universe first + k at
 	 *  64^3 with "render_skip" 0, bit for bit. `uniforms`: Float32Array(128) filled for a tileW x tileH window, one block for every tile;

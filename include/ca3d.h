@@ -924,6 +924,56 @@ int ca3d_ensemble_damage(ca3d_ensemble_t *src, uint32_t first, uint32_t count, c
                          ca3d_ensemble_t *dst /* NULL without the image */, uint32_t dst_first, uint32_t flags,
                          ca3d_damage *out /* [count] */, uint32_t *curve /* [count][curve_stride], may be NULL */,
                          uint32_t curve_stride, float *gpu_ms /* may be NULL */);
+/*
+ * Rule usage (no reference counterpart): which entries of its born / survive tables does a universe's run actually read? Two rules
+ * that differ only in entries a seed never reads have the same trajectory; the histogram of neighbour counts, split by alive and
+ * dead, is the input of every mean-field estimate; births and deaths follow from it and the table alone. One launch of
+ * ca_ensemble_usage_{vn,moore,clustered}64[_torus|_closed] (csrc/ca_usage.hip, by the ensemble's kind and its CURRENT boundary mode,
+ * one workgroup a universe) for universes first .. first + count - 1. Universe first + k is followed over steps[k] steps INSIDE the
+ * kernel; nothing is written back to the ensemble. host.usage restates it in plain numpy over host.ensemble_step.
+ *
+ * The definition. For universe u = first + k let P = steps[k], 1 <= P <= CA3D_CANON_MAX_PERIOD, and S_0 its current state.
+ *   S_(t+1) = step(S_t) by the ensemble's own step: u's rule and the ensemble's current boundary mode (reference, torus or closed),
+ *   exactly as ca3d_ensemble_step does.
+ *   The counts of a cell of S_t are the counts that step forms (host.ensemble_step): every axis applies its boundary to what the axis
+ *   before it produced. von Neumann: F, the six face neighbours, 0 .. 6, in the main class. Moore: the 26-neighbour count, 0 .. 26, in
+ *   the main class. Clustered: the main table is indexed by T = F + E + C (0 .. 26), the edges table by E (0 .. 12), the corners table
+ *   by C (0 .. 8), and a cell adds one to each of the three histograms every step.
+ *   A class's bins start at CA3D_USAGE_MAIN, _EDGES, _CORNERS. dead[base + c] (alive[base + c]) is the number of pairs (t, cell) with
+ *   t < P, the cell dead (alive) in S_t and that class's count equal to c: at most 2^18 * 2^12 = 2^30. Bins of a class the kind does
+ *   not look up, and main bins 7 .. 26 of a von Neumann ensemble, are zero.
+ *   used_born[i] has bit c set exactly when dead[base_i + c] != 0 — born_c was read — and used_survive[i] the same for alive[]
+ *   (i = 0 main, 1 edges, 2 corners). Flipping a table bit that is NOT set there leaves S_1 .. S_P as they are.
+ *   steps echoes P; flags and reserved are zero.
+ *   Per class that the kind looks up, sum(dead) + sum(alive) = 262 144 * P, and the sum of the class's alive[] is the population summed
+ *   over S_0 .. S_(P-1), ca3d_envelope.population_sum.
+ *
+ * Ordering. As ca3d_ensemble_envelope without images: the launch runs behind what is queued on the ensemble's stream, and the ensemble
+ * is only read: states, records, step counters, anchors, steps_done and stats are byte for byte as they were. It needs a state and a
+ * rule on every universe of the range. The call waits for its own result. gpu_ms (nullable) receives the hipEvent time around the
+ * launch. Records and steps are staged in a device array of the call's own.
+ *
+ * Errors: NULL `e`, steps or out — CA3D_ERR_INVALID_ARGUMENT without touching a device; `e` not configured —
+ * CA3D_ERR_NOT_CONFIGURED; count == 0, first + count > n, a step count of 0 or above CA3D_CANON_MAX_PERIOD —
+ * CA3D_ERR_INVALID_ARGUMENT; a universe without a state or without a rule — CA3D_ERR_NOT_CONFIGURED. Each message names its argument
+ * and the first offending universe. A refused call touches none of the caller's arrays and nothing on the device.
+ */
+#define CA3D_USAGE_MAIN 0u      /* bins 0..26 (von Neumann: 0..6, the rest zero) */
+#define CA3D_USAGE_EDGES 27u    /* bins 27..39, clustered only */
+#define CA3D_USAGE_CORNERS 40u  /* bins 40..48, clustered only */
+#define CA3D_USAGE_BINS 49u
+typedef struct ca3d_usage
+{
+	uint32_t steps;            /* echoed P */
+	uint32_t flags;            /* zero for now */
+	uint32_t used_born[3];     /* main, edges, corners: bit c set iff dead[class base + c] != 0 */
+	uint32_t used_survive[3];  /* the same for alive[] */
+	uint32_t dead[49];         /* cells DEAD in S_t with count c, summed over t = 0..P-1 */
+	uint32_t alive[49];
+	uint32_t reserved[2];      /* zero */
+} ca3d_usage;                  /* 432 bytes, a multiple of 16 */
+int ca3d_ensemble_usage(ca3d_ensemble_t *e, uint32_t first, uint32_t count, const uint32_t *steps /* [count] */,
+                        ca3d_usage *out /* [count] */, float *gpu_ms /* may be NULL */);
 int ca3d_ensemble_synchronize(ca3d_ensemble_t *e);
 int ca3d_ensemble_get_stats(ca3d_ensemble_t *e, struct ca3d_stats *out);
 

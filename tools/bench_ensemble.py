@@ -118,6 +118,12 @@ loop's host clock and the summed hipEvent time of its step launches. Before timi
 universes, and every loop's heat, envelope and stator populations must equal the call's everywhere. Reported: medians of --repeats
 measurements. No ratio is required. Written to profiles/ensemble_envelope_64.json unless --out says otherwise.
 
+--usage measures rule usage (ca3d_ensemble_usage, kernels ca_ensemble_usage_{vn,moore,clustered}64: which table entries a run reads,
+one launch) against the loop it replaces — per step read_state, the neighbour counts and a bincount per universe in numpy, step(1), run
+on --loop-samples steps and scaled — and against the floor, one plain step(--steps) launch of the same ensemble. Before timing, the
+records must equal host.usage in sampled universes over 3 steps, and the loop's histograms the call's. Writes
+profiles/ensemble_usage_64.json unless --out says otherwise.
+
 --damage measures damage spreading (ca3d_ensemble_damage, kernels ca_ensemble_damage_{vn,moore,clustered}64: a universe and its twin
 with one random cell flipped, stepped side by side INSIDE one launch, their Hamming distance at every step) for all three kinds at
 B = 256 and 1024 over --steps steps, with the curve: the launch's hipEvent time and the host clock around the call. First against the
@@ -1164,6 +1170,84 @@ def damage_rows(args):
     return rows
 
 
+def usage_rows(args):
+    """usage against the step(1) + read_state + numpy counts + bincount loop it replaces and against one plain step launch, the floor:
+    one row per (kind, B). -> rows"""
+    def masks(s, bits):
+        return sum(1 << v for v in host.rules_components_to_values(s)) & ((1 << bits) - 1)
+
+    a = Ensemble(0)
+    rows = []
+    med = statistics.median
+    for kind in ("von neumann", "moore", "clustered"):
+        clustered = kind == "clustered"
+        nb = "moore" if clustered else kind
+        if clustered:
+            keys = ("born", "survive", "born_edges", "survive_edges", "born_corners", "survive_corners")
+            tables = ([masks(CLUSTERED[keys[2 * i]], n) for i, n in enumerate((27, 13, 9))], [masks(CLUSTERED[keys[2 * i + 1]], n) for i, n in enumerate((27, 13, 9))])
+        else:
+            tables = (masks(RULES[nb][0], 27 if nb == "moore" else 7), masks(RULES[nb][1], 27 if nb == "moore" else 7))
+        for B in args.universes:
+            words = fills(B)
+            a.configure(B, neighbourhood=nb, clustered=clustered)
+            if clustered:
+                a.set_clustered_tables(0, tables[0], tables[1])
+            else:
+                a.set_rule_tables(0, tables[0], tables[1])
+            a.upload_state(0, words)
+            sample = sorted({0, B // 2, B - 1})
+            short = a.usage(3)
+            for u in sample:
+                if short[u].tobytes() != host.usage(words[u], kind, tables, 3).tobytes():
+                    raise SystemExit(f"{kind} B={B}: universe {u} is not host.usage's")
+            rec = a.usage(args.steps)  # warm-up of the timed shape
+            n_loop = min(args.loop_samples, args.steps)
+            head = a.usage(n_loop)  # what the loop is held to
+            gpu, wall, loop_wall, loop_gpu, floor = [], [], [], [], []
+            for _ in range(args.repeats):
+                a.synchronize()
+                t0 = time.perf_counter()
+                now = a.usage(args.steps)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                gpu.append(a.usage_gpu_ms())
+                if now.tobytes() != rec.tobytes():
+                    raise SystemExit(f"{kind} B={B}: two calls differ")
+                # the loop: steps 0 .. n_loop - 1 of every universe, counted on the host
+                a.synchronize()
+                t0 = time.perf_counter()
+                s_ms = 0.0
+                seen = [[] for _ in range(B)]
+                for _t in range(n_loop):
+                    for u, w in enumerate(a.read_state()):
+                        seen[u].append(host.usage_of_phases([w], kind))
+                    a.step(1)
+                    s_ms += a.stats().gpu_ms
+                a.synchronize()
+                loop_wall.append((time.perf_counter() - t0) * 1e3 * args.steps / n_loop)
+                loop_gpu.append(s_ms * args.steps / n_loop)
+                for u in range(B):
+                    for f in ("dead", "alive"):
+                        if not np.array_equal(sum(r[f].astype(np.uint64) for r in seen[u]), head[u][f]):
+                            raise SystemExit(f"{kind} B={B}: the loop counted otherwise than the call in universe {u}")
+                # the floor: one plain launch of --steps steps
+                a.upload_state(0, words)
+                a.synchronize()
+                a.step(args.steps)
+                a.synchronize()
+                floor.append(a.stats().gpu_ms)
+                a.upload_state(0, words)
+            row = {"kernel": kind, "universes": B, "steps": args.steps, "verified_against_host_usage_in": len(sample),
+                   "table_bits_read_median": float(np.median([sum(bin(int(v)).count("1") for v in list(r["used_born"]) + list(r["used_survive"])) for r in rec])),
+                   "usage_gpu_ms": med(gpu), "usage_gpu_ms_all": gpu, "usage_wall_ms": med(wall), "usage_wall_ms_all": wall,
+                   "loop_samples_run": n_loop, "loop_wall_ms_scaled": med(loop_wall), "loop_wall_ms_scaled_all": loop_wall, "loop_step_gpu_ms_scaled": med(loop_gpu),
+                   "step_launch_gpu_ms": med(floor), "step_launch_gpu_ms_all": floor,
+                   "wall_ratio_loop_over_usage": med(loop_wall) / med(wall), "gpu_ratio_usage_over_step_launch": med(gpu) / med(floor)}
+            rows.append(row)
+            print(json.dumps(row))
+    a.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--universes", type=int, nargs="+", default=None, help="default: 1 256 1024 4096 (--cycle: 256 1024)")
@@ -1185,13 +1269,14 @@ def main():
     ap.add_argument("--canon-period", action="store_true", help="measure canon_period against canon_phases instead (B = 256)")
     ap.add_argument("--envelope", action="store_true", help="measure envelope against the read_state + step(1) loop with numpy OR / AND / popcount instead (B = 256)")
     ap.add_argument("--damage", action="store_true", help="measure damage against the two-ensemble step(1) + read_state + numpy XOR / popcount loop and against two plain step launches instead (all three kinds; B = 256 1024)")
-    ap.add_argument("--loop-samples", type=int, default=8, help="--damage: samples the replaced loop is run on; its time is scaled to --steps")
+    ap.add_argument("--usage", action="store_true", help="measure usage against the step(1) + read_state + numpy counts + bincount loop and against one plain step launch instead (all three kinds; B = 256 1024)")
+    ap.add_argument("--loop-samples", type=int, default=8, help="--damage, --usage: samples the replaced loop is run on; its time is scaled to --steps")
     ap.add_argument("--boundary", action="store_true", help="measure step under the torus and closed boundaries against the reference boundary instead (all three kinds; B = 256 1024)")
     ap.add_argument("--loop-destinations", type=int, default=1024, help="--compose, --canon: destinations / universes the CPU loop is run on")
     ap.add_argument("--commit", default=None, help="commit the figures belong to (default: git rev-parse HEAD)")
     args = ap.parse_args()
     if args.universes is None:
-        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period or args.envelope else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.census_torus or args.boundary or args.damage else [1, 256, 1024, 4096]
+        args.universes = [256] if args.isolate or args.compose or args.canon or args.canon_period or args.envelope else [256, 1024] if args.cycle or args.trace or args.moving or args.sheet or args.census or args.census_torus or args.boundary or args.damage or args.usage else [1, 256, 1024, 4096]
     nb = args.neighbourhood
     clustered = nb == "clustered"
     if clustered:
@@ -1207,6 +1292,29 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
         except Exception:
             commit = "unknown"
+    if args.usage:
+        out = args.out or os.path.join(ROOT, "profiles", "ensemble_usage_64.json")
+        rows = usage_rows(args)
+        result = {
+            "what": "B universes of 64^3 (random fills, seeds 1 .. B) followed over --steps steps by ONE Ensemble.usage call — one launch of "
+                    "ca_ensemble_usage_<kind>64, records copied to the host — for von Neumann, Moore and clustered ensembles under this tool's rules; vs. the "
+                    "loop it replaces (per step read_state, the counts and a bincount per universe in numpy on the host, step(1)) and vs. one plain "
+                    "Ensemble.step(--steps) launch of the same ensemble, the floor",
+            "date": datetime.date.today().isoformat(), "commit": commit, "device": "MI355X (gfx950)",
+            "timing": f"usage_gpu_ms: hipEvent time around the launch; usage_wall_ms: host clock around the call; loop_wall_ms_scaled and "
+                      f"loop_step_gpu_ms_scaled: the loop run on loop_samples_run steps, its host clock and the summed hipEvent times of its step launches scaled "
+                      f"by steps / loop_samples_run; step_launch_gpu_ms: the hipEvent time of the step launch; medians of {args.repeats} "
+                      "alternating measurements, after the records equalled host.usage over 3 steps in the sampled universes; the loop's histograms "
+                      "equalled the call's over loop_samples_run steps in every universe",
+            "not_measured": "the torus and closed kernels, other step counts, other B, other rules",
+            "rows": rows,
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps({k: v for k, v in result.items() if k != "rows"}))
+        return
     if args.damage:
         out = args.out or os.path.join(ROOT, "profiles", "ensemble_damage_64.json")
         rows = damage_rows(args)
