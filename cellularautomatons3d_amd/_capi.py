@@ -137,6 +137,16 @@ COMPOSE_COPY_RULES = 0x100
 COMPOSE_MAX_PARTS = 1 << 20
 
 
+class WindowStruct(C.Structure):
+    """ca3d_window (include/ca3d.h): a universe of an ensemble and the grid cell (x, y, z) its cell (0, 0, 0) maps to, 16 bytes
+    (`host.WINDOW_DTYPE`)."""
+    _fields_ = [("universe", C.c_uint32), ("origin", C.c_uint32 * 3)]
+
+
+#: enum CA3D_STAMP_*: the mode of `ca3d_stamp_windows`
+STAMP_MODES = {"or": 0, "replace": 1, "erase": 2}
+
+
 class SeedStruct(C.Structure):
     """ca3d_seed (include/ca3d.h)."""
     _fields_ = [("seed", C.c_uint32), ("and_rounds", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
@@ -255,6 +265,8 @@ SYMBOLS = [
     ("ca3d_ensemble_damage", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _H, C.c_uint32, C.c_uint32, C.POINTER(DamageStruct),
                                        _u32p, C.c_uint32, C.POINTER(C.c_float)]),
     ("ca3d_ensemble_usage", C.c_int, [_H, C.c_uint32, C.c_uint32, _u32p, C.POINTER(UsageStruct), C.POINTER(C.c_float)]),
+    ("ca3d_cut_windows", C.c_int, [_H, _H, C.c_uint32, C.POINTER(WindowStruct), C.POINTER(C.c_float)]),
+    ("ca3d_stamp_windows", C.c_int, [_H, _H, C.c_uint32, C.POINTER(WindowStruct), C.c_uint32, C.POINTER(C.c_float)]),
     ("ca3d_ensemble_synchronize", C.c_int, [_H]),
     ("ca3d_ensemble_get_stats", C.c_int, [_H, C.POINTER(Stats)]),
     ("ca3d_ensemble_render_sheet", C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -154,6 +154,16 @@ int check_ready(ca3d_engine *h)
 	return CA3D_OK;
 }
 
+// "State edited": what holds of an engine whose CURRENT buffer has just been written by something other than a step, on the engine's
+// stream (ca3d_stamp_windows edits it in place; the caller has bound the device, joined the frames in flight, submitted the queued steps
+// and settled a resident launch). The step counter and the buffers stay; the other buffer no longer holds the state one step earlier, and
+// what the renderer derived from the state is stale.
+void engine_state_edited(ca3d_engine *h)
+{
+	h->prev_ok = false;
+	h->state_serial++;
+}
+
 // The "state replaced" tail of ca3d_upload_state and ca3d_seed_state: what holds of an engine whose two ping-pong buffers have just been
 // given the same new words (on the engine's stream; the caller has bound the device, joined the frames in flight and dropped the queued
 // steps). A resident launch whose completion has not been looked at must have left the stream before this is called.
@@ -161,8 +171,7 @@ static int state_replaced(ca3d_engine *h)
 {
 	h->step = 0;
 	h->cur = 0;
-	h->prev_ok = false;
-	h->state_serial++;
+	engine_state_edited(h);
 	h->buffers_exposed = false;
 	h->pending_edges = 0; // a restart between the two phases of a batch abandons the batch
 	h->ghosts_valid = false;

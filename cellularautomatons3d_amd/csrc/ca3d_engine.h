@@ -206,6 +206,7 @@ int fail(int code, const char *fmt, ...); // formats the message into the slot, 
 int bind_device(ca3d_engine *h, bool join = true);
 int check_ready(ca3d_engine *h);
 void drop_graph(ca3d_engine *h);
+void engine_state_edited(ca3d_engine *h); // the current buffer was edited in place on the engine's stream: no previous state, derived render data stale
 int engine_mark_state(ca3d_engine *h); // both buffers zeroed on the engine's stream, "has a state" — for engines whose state arrives by device copies
 // ca3d_device_buffer for a writer inside the library (the group's peer copies): the state counts as rewritten by THIS call only — the
 // public call must assume writes at any later time and makes every frame rebuild its derived buffers while the pointer is valid

@@ -14,9 +14,12 @@
 // ca3d_ensemble_canon_period does so over a period of each universe's own steps, inside the kernel (ca_canon_period.hip).
 // ca3d_ensemble_envelope takes envelope, stator, rotor and heat over such a period, and may write them as universes (ca_envelope.hip).
 // ca3d_ensemble_damage follows a universe and a perturbed twin and takes their Hamming distance at every step (ca_damage.hip).
+// ca3d_cut_windows / ca3d_stamp_windows move 64^3 regions between an engine's grid and universes (ca_window.hip); they live here because
+// the ensemble record is private to this file, and reach the engine through ca3d_engine.h.
 // What these calls share is written once, in the unnamed namespace: a staging array on the handle (Scratch) and the event pair around a
 // launch (Timer), both had from `reserve`; reset_records and mark_state / mark_rules for universes that were just written; and, for
 // isolate, compose, envelope and damage, the checks on two handles, the wait on the source's stream and the end of the call (finish_destinations).
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -113,6 +116,11 @@ struct ca3d_ensemble
 	// ca3d_ensemble_usage: the records of the call under way, [count] of 432 bytes, then the uploaded step counts, [count] words
 	Scratch usage;
 	Timer usage_time;
+	// ca3d_cut_windows / ca3d_stamp_windows, whichever way the words go: the windows of the call under way, [n] of 16 bytes; the event
+	// that orders the launches behind the source's stream
+	Scratch windows;
+	Timer windows_time;
+	hipEvent_t windows_src = nullptr;
 };
 
 namespace
@@ -137,7 +145,7 @@ void free_arrays(ca3d_ensemble *e)
 	e->sheet_counters = nullptr;
 	e->sheet_px = 0;
 	e->sheet_drawn = false;
-	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon, &e->envelope, &e->damage, &e->usage})
+	for (Scratch *s : {&e->trace, &e->census, &e->isolate, &e->compose, &e->canon, &e->envelope, &e->damage, &e->usage, &e->windows})
 	{
 		if (s->array) hipFree(s->array);
 		*s = Scratch{};
@@ -552,6 +560,57 @@ int finish_destinations(ca3d_ensemble *dst, uint32_t dst_first, uint32_t n, cons
 	return CA3D_OK;
 }
 
+// ca3d_cut_windows (`cut`: the ensemble is written, its universes must be distinct) and ca3d_stamp_windows (the ensemble is read, its
+// universes must hold a state): everything the two calls refuse, looked at before either handle is touched
+int check_windows(const ca3d_engine *h, const ca3d_ensemble *e, uint32_t n, const ca3d_window *w, bool cut)
+{
+	if (!h) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL engine handle");
+	if (!e) return fail(CA3D_ERR_INVALID_ARGUMENT, "NULL ensemble handle");
+	if (!w) return fail(CA3D_ERR_INVALID_ARGUMENT, "windows is NULL");
+	if (n == 0 || n > kWindowsMax) return fail(CA3D_ERR_INVALID_ARGUMENT, "a call takes 1 to %u windows (got %u)", kWindowsMax, n);
+	if (!h->configured) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_configure has not been called for the engine");
+	if (!e->n) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_ensemble_configure has not been called for the ensemble");
+	if (h->layout != CA3D_LAYOUT_PACKED32) return fail(CA3D_ERR_UNSUPPORTED, "windows are cut from and stamped into the packed layout only");
+	if (h->slab) return fail(CA3D_ERR_UNSUPPORTED, "windows are cut from and stamped into a full-grid engine, not a slab (ca3d_configure_slab, the ranks of a group)");
+	if (h->G < 64u) return fail(CA3D_ERR_UNSUPPORTED, "a window is 64^3 cells: the grid must be 64 or more a side (got %u)", h->G);
+	if (h->device != e->device) return fail(CA3D_ERR_INVALID_ARGUMENT, "the engine is on device %d, the ensemble on device %d", h->device, e->device);
+	if (cut && !h->has_state) return fail(CA3D_ERR_NOT_CONFIGURED, "ca3d_upload_state has not been called for the engine: no state to cut from");
+	std::vector<uint8_t> taken(cut && n > 1u ? e->n : 0u, 0);
+	for (uint32_t k = 0; k < n; k++)
+	{
+		const uint32_t u = w[k].universe;
+		if (u >= e->n) return fail(CA3D_ERR_INVALID_ARGUMENT, "window %u: universe %u of %u", k, u, e->n);
+		for (int i = 0; i < 3; i++)
+			if (w[k].origin[i] >= h->G) return fail(CA3D_ERR_INVALID_ARGUMENT, "window %u: origin[%d] = %u — an origin lies below the grid size %u", k, i, w[k].origin[i], h->G);
+		if (!cut && !e->has_state[u]) return fail(CA3D_ERR_NOT_CONFIGURED, "window %u: ca3d_ensemble_upload_state has not been called for universe %u", k, u);
+		if (!taken.empty())
+		{
+			if (taken[u]) return fail(CA3D_ERR_INVALID_ARGUMENT, "window %u: universe %u is the destination of an earlier window of the call", k, u);
+			taken[u] = 1;
+		}
+	}
+	return CA3D_OK;
+}
+
+// the engine's state as it is after every step requested so far, on its stream: what ca3d_read_state does before it looks
+int settle_engine(ca3d_engine *h)
+{
+	FLUSH_QUEUED(h);
+	const int rc = bind_device(h); // (joins the frames in flight)
+	if (rc) return rc;
+	return settle_resident(h);
+}
+
+// the call's windows into the ensemble's staging array, on `stream`, behind what `behind` holds now
+int stage_windows(ca3d_ensemble *e, uint32_t n, const ca3d_window *w, hipStream_t stream, hipStream_t behind)
+{
+	HIP_TRY(hipEventRecord(e->windows_src, behind));
+	HIP_TRY(hipStreamWaitEvent(stream, e->windows_src, 0));
+	// (from pageable memory: the copy has left the caller's array when the call returns)
+	HIP_TRY(hipMemcpyAsync(e->windows.array, w, (size_t)n * sizeof(ca3d_window), hipMemcpyHostToDevice, stream));
+	return CA3D_OK;
+}
+
 // the three getters of what a configure or ca3d_ensemble_set_boundary chose
 template <class T> int get_setting(const ca3d_ensemble *e, int *out, T ca3d_ensemble::*setting)
 {
@@ -602,10 +661,10 @@ int ca3d_ensemble_destroy(ca3d_ensemble_t *e) CA3D_API_TRY
 	hipSetDevice(e->device);
 	if (e->stream) hipStreamSynchronize(e->stream);
 	free_arrays(e);
-	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time, e->envelope_time, e->damage_time, e->usage_time})
+	for (const Timer &t : {e->run_time, e->sheet_time, e->census_time, e->isolate_time, e->compose_time, e->canon_time, e->canon_period_time, e->envelope_time, e->damage_time, e->usage_time, e->windows_time})
 		for (hipEvent_t ev : {t.start, t.stop})
 			if (ev) hipEventDestroy(ev);
-	for (hipEvent_t ev : {e->ev_seed, e->isolate_src, e->compose_src, e->envelope_src, e->damage_src})
+	for (hipEvent_t ev : {e->ev_seed, e->isolate_src, e->compose_src, e->envelope_src, e->damage_src, e->windows_src})
 		if (ev) hipEventDestroy(ev);
 	if (e->stream) hipStreamDestroy(e->stream);
 	delete e;
@@ -1421,6 +1480,70 @@ int ca3d_ensemble_usage(ca3d_ensemble_t *e, uint32_t first, uint32_t count, cons
 	HIP_TRY(hipMemcpyAsync(out, l.out, rec_bytes, hipMemcpyDeviceToHost, e->stream));
 	HIP_TRY(hipStreamSynchronize(e->stream));
 	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, e->usage_time.start, e->usage_time.stop));
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_cut_windows(ca3d_t *src, ca3d_ensemble_t *dst, uint32_t n, const ca3d_window *w, float *gpu_ms) CA3D_API_TRY
+{
+	int rc = check_windows(src, dst, n, w, true);
+	if (rc) return rc;
+	if ((rc = settle_engine(src))) return rc;
+	if ((rc = reserve(dst, dst->windows, (size_t)n * sizeof(ca3d_window), &dst->windows_time, &dst->windows_src, "%u windows", n))) return rc;
+	if ((rc = stage_windows(dst, n, w, dst->stream, src->stream))) return rc;
+	WindowLaunch l{};
+	l.grid = src->buf[src->cur];
+	l.G = src->G;
+	l.state = dst->state; l.prev = dst->prev;
+	l.windows = dst->windows.at<const ca3d_window>();
+	l.n = n;
+	l.op = kWindowCut;
+	HIP_TRY(hipEventRecord(dst->windows_time.start, dst->stream));
+	HIP_TRY(launch_windows(l, dst->stream));
+	HIP_TRY(hipEventRecord(dst->windows_time.stop, dst->stream));
+	// the records of the universes written, one launch for every run of consecutive ones (a tiling names one run)
+	std::vector<uint32_t> written(n);
+	for (uint32_t k = 0; k < n; k++) written[k] = w[k].universe;
+	std::sort(written.begin(), written.end());
+	for (uint32_t k = 0, run = 0; k < n; k = run)
+	{
+		for (run = k + 1u; run < n && written[run] == written[run - 1u] + 1u; run++) {}
+		if ((rc = reset_records(dst, written[k], run - k))) return rc;
+	}
+	HIP_TRY(hipStreamSynchronize(dst->stream)); // the caller's windows are consumed, and the engine may go on
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, dst->windows_time.start, dst->windows_time.stop));
+	for (uint32_t u : written) mark_state(dst, u, 1u);
+	return CA3D_OK;
+}
+CA3D_API_CATCH
+
+int ca3d_stamp_windows(ca3d_t *dst, ca3d_ensemble_t *src, uint32_t n, const ca3d_window *w, uint32_t mode, float *gpu_ms) CA3D_API_TRY
+{
+	if (mode > CA3D_STAMP_ERASE) return fail(CA3D_ERR_INVALID_ARGUMENT, "unknown mode %u (CA3D_STAMP_OR = 0, CA3D_STAMP_REPLACE = 1, CA3D_STAMP_ERASE = 2)", mode);
+	int rc = check_windows(dst, src, n, w, false);
+	if (rc) return rc;
+	if ((rc = settle_engine(dst))) return rc;
+	if ((rc = reserve(src, src->windows, (size_t)n * sizeof(ca3d_window), &src->windows_time, &src->windows_src, "%u windows", n))) return rc;
+	if (!dst->has_state && (rc = engine_mark_state(dst))) return rc; // a world built from objects alone: all dead, step 0
+	if ((rc = stage_windows(src, n, w, dst->stream, src->stream))) return rc;
+	WindowLaunch l{};
+	l.grid = dst->buf[dst->cur];
+	l.G = dst->G;
+	l.state = src->state;
+	l.windows = src->windows.at<const ca3d_window>();
+	l.n = n;
+	HIP_TRY(hipEventRecord(src->windows_time.start, dst->stream));
+	if (mode == CA3D_STAMP_REPLACE)
+	{
+		l.op = kWindowClear; // every box first: a window's cells must not outlive another window's clear
+		HIP_TRY(launch_windows(l, dst->stream));
+	}
+	l.op = mode == CA3D_STAMP_ERASE ? kWindowErase : kWindowOr;
+	HIP_TRY(launch_windows(l, dst->stream));
+	HIP_TRY(hipEventRecord(src->windows_time.stop, dst->stream));
+	engine_state_edited(dst);
+	HIP_TRY(hipStreamSynchronize(dst->stream)); // the caller's windows are consumed, and the ensemble may go on
+	if (gpu_ms) HIP_TRY(hipEventElapsedTime(gpu_ms, src->windows_time.start, src->windows_time.stop));
 	return CA3D_OK;
 }
 CA3D_API_CATCH

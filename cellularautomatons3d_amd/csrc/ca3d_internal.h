@@ -281,6 +281,22 @@ struct ComposeLaunch
 	uint32_t rule_words;            // 0: rules stay; else ensemble_rule_words() of both ensembles
 };
 hipError_t launch_compose(const ComposeLaunch &l, hipStream_t stream);
+// ca_window.hip: 64^3 windows of a packed full grid of G cells a side (a torus, G a multiple of 32 from 64 up), one per entry of
+// `windows`, against the universes those entries name (ca3d_cut_windows / ca3d_stamp_windows). kWindowCut writes both ensemble buffers
+// from the grid and never the grid; the other three read `state` and edit the grid with atomics, so windows may overlap. The caller has
+// checked every universe and origin, n (1 .. kWindowsMax) and, for a cut, that the universes are distinct.
+constexpr uint32_t kWindowsMax = 1u << 20;
+enum WindowOp { kWindowCut, kWindowOr, kWindowErase, kWindowClear };
+struct WindowLaunch
+{
+	uint32_t *grid;             // [G][G][G / 32], the engine's current buffer
+	uint32_t G;
+	uint32_t *state, *prev;     // [B][8192], the ensemble's two buffers (`prev`: a cut only)
+	const ca3d_window *windows; // device, [n]
+	uint32_t n;
+	WindowOp op;                // kWindowClear: every cell of every window's box is cleared (the first phase of CA3D_STAMP_REPLACE)
+};
+hipError_t launch_windows(const WindowLaunch &l, hipStream_t stream);
 // ca_canon.hip: the key, orientation and symmetry group of universes [first, first + count) of an ensemble's state array
 // (ca3d_ensemble_canon), one workgroup of ca_ensemble_canon64 each; out and digests are indexed by universe - first. The caller has
 // checked the range. The states are only read.

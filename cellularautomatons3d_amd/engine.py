@@ -140,6 +140,36 @@ class Engine:
         _capi.check(self._lib.ca3d_read_state(self._h, out.ctypes.data_as(_u32p), out.size))
         return out
 
+    def cut_windows(self, ens, windows) -> None:
+        """`ca3d_cut_windows`: universe u of the `Ensemble` `ens` becomes the 64^3 window of this engine's current state whose cell
+        (0, 0, 0) is grid cell (x, y, z), for every (u, (x, y, z)) of `windows` — the grid is a torus, a window may wrap. On the device,
+        one launch behind every step asked for so far; the universes are at step 0 afterwards, rules untouched, and must be distinct.
+        `host.cut_window` is the same on the CPU for one window; `host.window_tiling(grid_size)` gives the origins that cover the grid;
+        `windows_gpu_ms()` tells what the launch took. Packed full-grid engines of 64 and more a side."""
+        self._windows(self._lib.ca3d_cut_windows, ens, windows)
+
+    def stamp_windows(self, ens, windows, mode: str = "or") -> None:
+        """`ca3d_stamp_windows`: universe u of the `Ensemble` `ens` is stamped into this engine's current state with its cell (0, 0, 0)
+        at grid cell (x, y, z), for every (u, (x, y, z)) of `windows`. `mode`: "or" sets the universe's live cells, "erase" clears
+        them, "replace" first clears every window's 64^3 box and then sets; windows may overlap and their order does not matter. On
+        the device, behind every step asked for so far; the step counter stays, the next summary has no previous state, the next frame
+        rebuilds what it derives from the state. An engine that was only configured counts as empty. `host.stamp_windows` is the same
+        on the CPU."""
+        if mode not in _capi.STAMP_MODES:
+            raise ValueError(f"unknown mode {mode!r}: one of {tuple(_capi.STAMP_MODES)}")
+        self._windows(self._lib.ca3d_stamp_windows, ens, windows, _capi.STAMP_MODES[mode])
+
+    def _windows(self, call, ens, windows, *mode) -> None:
+        w = windows if isinstance(windows, np.ndarray) and windows.dtype == host.WINDOW_DTYPE else host.window_records(windows)
+        w = np.ascontiguousarray(w)
+        ms = C.c_float(0.0)
+        _capi.check(call(self._h, ens._h, len(w), w.ctypes.data_as(C.POINTER(_capi.WindowStruct)), *mode, C.byref(ms)))
+        self._windows_ms = float(ms.value)
+
+    def windows_gpu_ms(self) -> float:
+        """hipEvent time around the launches of the last `cut_windows` / `stamp_windows`, in milliseconds (None before the first)."""
+        return getattr(self, "_windows_ms", None)
+
     def save_checkpoint(self, path) -> None:
         i = self.info()
         host.save_checkpoint(path, self.read_state(), i.grid_size, i.step, i.layout)

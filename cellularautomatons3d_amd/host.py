@@ -1208,6 +1208,84 @@ def usage_births_deaths(record, kind: str, tables) -> Tuple[int, int]:
     return births, deaths
 
 
+# ------------------------------------------------------------------------------------------------- windows
+# The definition of ca3d_cut_windows / ca3d_stamp_windows (include/ca3d.h) in executable form: 64^3 windows of a packed G^3 grid,
+# addressed as a torus, against packed 64^3 universes.
+
+#: ca3d_window (include/ca3d.h), 16 bytes
+WINDOW_DTYPE = np.dtype([("universe", "<u4"), ("origin", "<u4", (3,))])
+STAMP_MODES = ("or", "replace", "erase")  # index = enum CA3D_STAMP_*
+
+
+def window_records(windows) -> np.ndarray:
+    """[(universe, (x, y, z)), ...] as records of `WINDOW_DTYPE`. Values are handed over as given (modulo 2^32): the library refuses
+    what does not fit."""
+    out = np.zeros(len(windows), dtype=WINDOW_DTYPE)
+    for k, (universe, origin) in enumerate(windows):
+        if len(origin) != 3:
+            raise ValueError("a window is (universe, (x, y, z))")
+        out[k]["universe"] = int(universe) & 0xFFFFFFFF
+        out[k]["origin"] = [int(v) & 0xFFFFFFFF for v in origin]
+    return out
+
+
+def window_tiling(grid_size: int) -> np.ndarray:
+    """The origins (x, y, z) of ceil(G / 64)^3 windows that tile a grid of G, x fastest: every cell lies in exactly one window when 64
+    divides G; otherwise the last window of an axis wraps round and covers cells of the first again -> i64[n, 3]."""
+    G = int(grid_size)
+    if G < 64:
+        raise ValueError("a window is 64^3 cells: the grid must be 64 or more a side")
+    at = 64 * np.arange(-(-G // 64))
+    z, y, x = np.meshgrid(at, at, at, indexing="ij")
+    return np.stack([x.ravel(), y.ravel(), z.ravel()], axis=1)
+
+
+def _window_axes(G: int, origin):
+    ox, oy, oz = (int(v) for v in origin)
+    if G < 64 or G % 32 or not all(0 <= v < G for v in (ox, oy, oz)):
+        raise ValueError("a window's origin lies inside a grid of 64 or more a side")
+    i = np.arange(64)
+    return (ox + i) % G, (oy + i) % G, (oz + i) % G
+
+
+def _window_rows(grid: np.ndarray, yi, zi) -> np.ndarray:
+    """Cells [64 k, 64 j, G x] of the grid rows a window touches; `grid`: [G, G, G / 32] words."""
+    rows = np.ascontiguousarray(grid[np.ix_(zi, yi)])
+    return np.unpackbits(rows.view(np.uint8), axis=-1, bitorder="little")
+
+
+def cut_window(grid_size: int, words, origin) -> np.ndarray:
+    """`ca3d_cut_windows` for ONE window of a packed G^3 state: window cell (i, j, k), each 0 .. 63, is grid cell
+    ((ox + i) mod G, (oy + j) mod G, (oz + k) mod G) -> words u32[8192] of a 64^3 universe."""
+    G = int(grid_size)
+    xi, yi, zi = _window_axes(G, origin)
+    grid = np.ascontiguousarray(words, dtype="<u4").reshape(G, G, G // 32)
+    cells = _window_rows(grid, yi, zi)[:, :, xi]
+    return np.packbits(np.ascontiguousarray(cells).ravel(), bitorder="little").view("<u4").copy()
+
+
+def stamp_windows(grid_size: int, words, windows, mode: str = "or") -> np.ndarray:
+    """`ca3d_stamp_windows` on a packed G^3 state: `windows` is a list of (universe_words u32[8192], (ox, oy, oz)). "or": every live cell
+    of a universe, mapped as in `cut_window`, is set; "erase": those cells are cleared; "replace": every cell of every window's box is
+    cleared first, then every universe is ORed in. The result does not depend on the order of the windows -> the new words."""
+    G = int(grid_size)
+    if mode not in STAMP_MODES:
+        raise ValueError(f"unknown mode {mode!r}: one of {STAMP_MODES}")
+    out = np.array(words, dtype="<u4").reshape(G, G, G // 32)
+    phases = (("clear", "or") if mode == "replace" else (mode,))
+    for phase in phases:
+        for universe, origin in windows:
+            xi, yi, zi = _window_axes(G, origin)
+            cells = _window_rows(out, yi, zi)
+            if phase == "clear":
+                cells[:, :, xi] = 0
+            else:
+                u = np.unpackbits(np.ascontiguousarray(universe, dtype="<u4").reshape(64, 64, 2).view(np.uint8), axis=-1, bitorder="little")
+                cells[:, :, xi] = cells[:, :, xi] | u if phase == "or" else cells[:, :, xi] & (1 - u)
+            out[np.ix_(zi, yi)] = np.packbits(cells, axis=-1, bitorder="little").view("<u4")
+    return out.reshape(-1)
+
+
 # ------------------------------------------------------------------------------------------------ renderer
 # The 128-float common uniform block (MemoryManager.js; allocation order main_pathtraced.js:166, 467-478 ==
 # struct CommonBufferLayout, pathtraced_fragment_clustered.wgsl:17-34). Matrices are column-major f32.

@@ -1402,6 +1402,39 @@ static napi_value js_ensemble_isolate(napi_env env, napi_callback_info info)
 	return v;
 }
 
+/* cutWindows(engineHandle, ensembleHandle, Uint32Array(4 * n) windows (universe, x, y, z each)) -> gpuMs: universe windows[4 k] of the
+ * ensemble becomes the 64^3 window of the engine's current state at origin windows[4 k + 1 ..] (ca3d_cut_windows);
+ * stampWindows(engineHandle, ensembleHandle, windows, mode) -> gpuMs: those universes are stamped into the engine's state there
+ * (ca3d_stamp_windows; mode CA3D_STAMP_OR / REPLACE / ERASE). `stamp`: which of the two */
+static napi_value windows_call(napi_env env, napi_callback_info info, int stamp)
+{
+	napi_value argv[4];
+	if (!get_args(env, info, stamp ? 4 : 3, argv)) return NULL;
+	ca3d_t *h = get_handle(env, argv[0]);
+	if (!h) return NULL;
+	ca3d_ensemble_t *e = get_ensemble(env, argv[1]);
+	uint32_t mode = 0;
+	void *w;
+	size_t nw;
+	if (!e || !get_typed(env, argv[2], napi_uint32_array, 0, &w, &nw) || (stamp && !get_u32(env, argv[3], &mode))) return NULL;
+	if (nw % 4u || nw / 4u > 0xFFFFFFFFu)
+	{
+		napi_throw_range_error(env, NULL, "windows must hold (universe, x, y, z) a window");
+		return NULL;
+	}
+	_Static_assert(sizeof(ca3d_window) == 16, "a window crosses as four words");
+	float ms = 0.f;
+	/* (no window: the library refuses the call and names the reason; it does not read the array) */
+	int rc = stamp ? ca3d_stamp_windows(h, e, (uint32_t)(nw / 4u), (const ca3d_window *)w, mode, &ms)
+	               : ca3d_cut_windows(h, e, (uint32_t)(nw / 4u), (const ca3d_window *)w, &ms);
+	if (rc) return throw_ca3d(env, rc);
+	napi_value v;
+	napi_create_double(env, (double)ms, &v);
+	return v;
+}
+static napi_value js_cut_windows(napi_env env, napi_callback_info info) { return windows_call(env, info, 0); }
+static napi_value js_stamp_windows(napi_env env, napi_callback_info info) { return windows_call(env, info, 1); }
+
 /* ensembleCompose(dstHandle, dstFirst, srcHandle, Int32Array(6 * nParts) parts (universe, orientation, x, y, z, 0 each),
  * Uint32Array(nDst + 1) partBegin, flags, Uint32Array(4 * nDst) out) -> gpuMs: dst's universe dstFirst + k becomes the union of parts
  * partBegin[k] .. partBegin[k + 1] - 1, src's universes turned and shifted (ca3d_ensemble_compose); out[4 k ..] is ca3d_composed's four
@@ -1850,6 +1883,7 @@ static napi_value init(napi_env env, napi_value exports)
 	    {"ensembleCanonPeriod", js_ensemble_canon_period},
 	    {"ensembleEnvelope", js_ensemble_envelope},
 	    {"ensembleUsage", js_ensemble_usage},
+	    {"cutWindows", js_cut_windows}, {"stampWindows", js_stamp_windows},
 	    {"ensembleDamage", js_ensemble_damage}};
 	for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++)
 	{

@@ -238,6 +238,28 @@ const ENVELOPE_RETURNS = 0x1, ENVELOPE_IMAGES = { envelope: 1, stator: 2, rotor:
 // CA3D_DAMAGE_HEALED, CA3D_DAMAGE_FLIPS, CA3D_DAMAGE_SELF = CA3D_DAMAGE_NO_FLIP, CA3D_DAMAGE_IMAGE_DAMAGE, CA3D_DAMAGE_COPY_RULES (Ensemble.damage)
 const DAMAGE_HEALED = 0x1, DAMAGE_FLIPS = 4, DAMAGE_NONE = 0xFFFFFFFF, DAMAGE_IMAGE_DAMAGE = 0x1, DAMAGE_COPY_RULES = 0x100;
 
+const STAMP_MODES = ["or", "replace", "erase"]; // index = CA3D_STAMP_OR / REPLACE / ERASE (Engine.stampWindows)
+
+// [[universe, [x, y, z]], ...] (or the flat Uint32Array itself) as ca3d_window records: universe, x, y, z a window
+function flatWindows(windows)
+{
+	if (windows instanceof Uint32Array) return windows;
+	return Uint32Array.from(windows.flatMap(([universe, origin]) =>
+	{
+		if (!origin || origin.length !== 3) throw new RangeError("windows: [universe, [x, y, z]] each");
+		return [universe, origin[0], origin[1], origin[2]];
+	}));
+}
+
+// the origins [x, y, z] of ceil(G / 64)^3 windows that tile a grid of G, x fastest (every cell exactly once when 64 divides G)
+function windowTiling(gridSize)
+{
+	if (gridSize < 64) throw new RangeError("a window is 64^3 cells: the grid must be 64 or more a side");
+	const n = Math.ceil(gridSize / 64), out = [];
+	for (let z = 0; z < n; z++) for (let y = 0; y < n; y++) for (let x = 0; x < n; x++) out.push([64 * x, 64 * y, 64 * z]);
+	return out;
+}
+
 class Engine
 {
 	constructor(device)
@@ -294,6 +316,23 @@ class Engine
 	step(n) { this._idle("step"); this._a.step(this._h, n === undefined ? 1 : n); }
 	/** device.queue.submit: submits the steps encoded under setOption("queue", n). */
 	flush() { this._idle("flush"); this._a.flush(this._h); }
+
+	/** Windows (ca3d_cut_windows): universe u of the Ensemble `ens` becomes the 64^3 window of this engine's current state whose cell
+	 *  (0, 0, 0) is grid cell (x, y, z), for every [u, [x, y, z]] of `windows` (or a Uint32Array of u, x, y, z a window) — the grid is
+	 *  a torus, a window may wrap. On the device, one launch behind every step asked for so far; the universes are at step 0
+	 *  afterwards, rules untouched, and must be distinct. windowTiling(gridSize) gives the origins that cover the grid -> gpuMs. */
+	cutWindows(ens, windows) { this._idle("cutWindows"); return this._a.cutWindows(this._h, ens._e, flatWindows(windows)); }
+	/** ca3d_stamp_windows: universe u of `ens` is stamped into this engine's state with its cell (0, 0, 0) at (x, y, z). mode: "or" (the
+	 *  default) sets the universe's live cells, "erase" clears them, "replace" first clears every window's 64^3 box and then sets;
+	 *  windows may overlap and their order does not matter. The step counter stays, the next summary has no previous state, the next
+	 *  frame rebuilds what it derives from the state; an engine that was only configured counts as empty -> gpuMs. */
+	stampWindows(ens, windows, mode)
+	{
+		this._idle("stampWindows");
+		const m = STAMP_MODES.indexOf(mode === undefined ? "or" : mode);
+		if (m < 0) throw new Error(`unknown mode ${JSON.stringify(mode)}: "or", "replace" or "erase"`);
+		return this._a.stampWindows(this._h, ens._e, flatWindows(windows), m);
+	}
 
 	// Z-slab mode (multi-GPU hosts; SURVEY 8(e)): see include/ca3d.h. phase: 0 whole batch, 1 edge zones, 2 interior.
 	configureSlab(gridSize, z0, nz, ghost, layout) { this._a.configureSlab(this._h, gridSize, layout === undefined ? LAYOUT_PACKED32 : layout, z0, nz, ghost); this.gridSize = gridSize; }
@@ -843,5 +882,5 @@ class Ensemble
 module.exports = {
 	Engine, EngineGroup, Ensemble, ENSEMBLE_ALL, ENSEMBLE_WORDS, ENSEMBLE_BOUNDARIES, CONNECTIVITIES, STOP_EXTINCT, STOP_STILL, STOP_PERIODIC, STOP_MOVING, NEIGHBOURHOOD_MAP, DEFAULT_RULES, LAYOUT_PACKED32, LAYOUT_UNPACKED, NEIGHBOURS_STORAGE_LEN,
 	rulesComponentsToValues, recalculateRulesValues, gridSizeUIFormatter, getClusterIdxFromGridCoordinates,
-	initialState, dispatchShape, traceSamples, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint
+	initialState, dispatchShape, traceSamples, randomFill, seededState, loadAddon, saveCheckpoint, loadCheckpoint, STAMP_MODES, windowTiling
 };

@@ -1186,6 +1186,53 @@ int ca3d_ensemble_render_sheet(ca3d_ensemble_t *e, uint32_t first, uint32_t coun
                                uint32_t columns, uint32_t spp, uint8_t *presentation_rgba8, uint16_t *light_rgba16f, uint16_t *depth_rg16f);
 int ca3d_ensemble_get_sheet_stats(ca3d_ensemble_t *e, ca3d_render_stats *out);
 
+/*
+ * Windows (no reference counterpart): 64^3 regions of an engine's grid cut into universes of an ensemble, and universes stamped back
+ * into the grid, without a state leaving the device — what the ensemble's census, isolate, compose and canon found can be put into a
+ * big world and rendered, the objects of a region of a running world can be counted, and a pattern can be pasted. Both calls work
+ * between a PACKED, FULL-GRID engine and an ensemble on the same device, one launch per phase (csrc/ca_window.hip), behind what is
+ * queued. host.cut_window and host.stamp_windows restate them.
+ *
+ * The window map. A window at origin (ox, oy, oz), each below G, maps window cell (i, j, k), each 0 .. 63, to grid cell
+ *   ((ox + i) mod G, (oy + j) mod G, (oz + k) mod G): the grid is addressed as a torus whatever the step's boundary is, and G >= 64
+ *   makes the map injective. G is any grid the engine accepts from 64 up, the multiples of 32 that are no power of two included.
+ * Cut. Universe w[k].universe of `dst` becomes window k of the engine's current state — after every step requested so far: queued steps
+ *   are submitted and a resident launch is settled first, as ca3d_read_state does. Both ping-pong buffers of the universe get the
+ *   words, its record is rebuilt at step 0 with no previous state (the launch ca3d_ensemble_upload_state ends in) and it counts as
+ *   having a state; rules are untouched. The universes of one call must be distinct. The engine is only read.
+ * Stamp. The three modes commute: a call's result does not depend on the order of its windows, and windows may overlap freely.
+ *     CA3D_STAMP_OR       every live cell of universe w[k].universe of `src`, mapped through window k, is set in the grid;
+ *     CA3D_STAMP_ERASE    those cells are cleared;
+ *     CA3D_STAMP_REPLACE  first every cell of every window's box is cleared, then every universe is ORed in (two launches).
+ *   The engine afterwards: the step counter is unchanged; there is no previous state (has_previous is 0, births and deaths are 0 in
+ *   the next summary, until the next step); what the renderer derived from the state is rebuilt by the next frame, and frames in
+ *   flight are joined before the stamp; queued steps are submitted and a resident launch is settled before the stamp. A configured
+ *   engine that has no state yet is taken as all dead, at step 0: a world can be built from objects alone. The ensemble is only read.
+ * Ordering is ca3d_ensemble_isolate's: the launches run on the destination's stream (a cut: the ensemble's, a stamp: the engine's)
+ *   behind what is queued there and behind an event recorded on the source's stream at the call, and the call waits for its own
+ *   result. gpu_ms (nullable) receives the hipEvent time around the launches. The windows are staged in a device array on the
+ *   ensemble's handle (16 bytes a window, grown when a call needs more, freed by a configure and by destroy).
+ *
+ * Errors — a refused call touches neither handle, and names the window where there is one: a NULL handle or array, n == 0 or above
+ * 1 << 20, a universe out of range, an origin >= G, the same destination universe twice in a cut, an unknown mode, handles on
+ * different devices — CA3D_ERR_INVALID_ARGUMENT; either handle not configured, a cut from an engine without a state, a stamp from a
+ * universe without a state — CA3D_ERR_NOT_CONFIGURED; the unpacked layout, a slab engine (ca3d_configure_slab, and so every rank of
+ * a group), G < 64 — CA3D_ERR_UNSUPPORTED.
+ */
+typedef struct ca3d_window
+{
+	uint32_t universe;  /* of the ensemble */
+	uint32_t origin[3]; /* x, y, z of window cell (0, 0, 0) in the grid, each < G */
+} ca3d_window;          /* 16 bytes */
+enum
+{
+	CA3D_STAMP_OR = 0,
+	CA3D_STAMP_REPLACE = 1,
+	CA3D_STAMP_ERASE = 2
+};
+int ca3d_cut_windows(ca3d_t *src, ca3d_ensemble_t *dst, uint32_t n, const ca3d_window *w, float *gpu_ms /* may be NULL */);
+int ca3d_stamp_windows(ca3d_t *dst, ca3d_ensemble_t *src, uint32_t n, const ca3d_window *w, uint32_t mode, float *gpu_ms /* may be NULL */);
+
 /* How many converged frames the engine keeps in flight (option "render_pipeline" below): the number of internal streams — on pairwise
  * different hardware queues, probed when the first pipelined frame is drawn — that such frames alternate between; 0 before that frame,
  * with the option off, or when the runtime gave the engine no two streams that run side by side. Does not wait for the GPU. */
